@@ -29,6 +29,13 @@ What the compact line holds (N=1):
   cpu_baseline ............ the oracle port timed on the host cores (B=4, BASELINE configs[0])
   rccl (N>1) .............. world, backend, all-reduce bytes / ms (HIP events around the collective alone) / bus GB/s,
                             per-rank ms_per_step min / max, ranks_bit_identical (64-bit checksum of the flat buffers)
+
+--dump-outputs DIR (rank 0): what the headline's LAST timed step handed its caller, as DIR/<name>.npy -- the step's
+returned loss / recon_error / perplexity (0-d float32) and every model parameter after that step's update
+(param.<name>.npy, float32).  The whole dump is held to DUMP_BUDGET bytes: when the snapshot is larger, every array is
+cut to at most one shared element count (the largest that fits, see dump_plan) and a cut array is stored as a fixed
+sample of its flattened elements, in index order, drawn by a generator seeded from its name.  Model init, batch and
+jitter are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -67,6 +74,8 @@ MODE_TEXT = {"x3mx_hb": "bf16x3 encoder+pre-VQ forward, f16mx decoder forward, o
 ALL_MODES = ("x3mx_hb", "f16mx_hb", "bf16x3_hb", "f32", "bf16")
 SPEECH_CFG = (201, 1024, 128, 3, 1024, 0.25, 1024)          # scripts/train_speech.py:152-153
 RIR_CFG = (500, 1024, 64, 2, 64, 0.25, 1024)                # scripts/train_rir.py:147-149
+DUMP_BUDGET = 64 * 10 ** 6        # --dump-outputs: bytes of the whole dump, .npy headers included
+DUMP_HEADER = 256                 # bytes allowed per .npy file for its header (numpy writes 128)
 
 
 def conv_gflop_parts(cfg, L, out_channels=None):
@@ -181,6 +190,52 @@ def compact_line(d):
     return out
 
 
+def config_model(kind):
+    """The freshly initialised model of one --config (as constructed: the echoed one moves its sub-models to the GPU when
+    there is one), its ctor and its algorithmic GFLOP per spectrogram.  The caller seeds torch."""
+    from acoustic_locating_vq_vae.vq_vae.convolutional_vq_vae import ConvolutionalVQVAE
+    if kind == "speech":
+        return ConvolutionalVQVAE(*SPEECH_CFG), SPEECH_CFG, algorithmic_gflop_per_spectrogram(SPEECH_CFG, 500)
+    if kind == "rir":
+        return ConvolutionalVQVAE(*RIR_CFG, use_jitter=False, out_channels=1), RIR_CFG, algorithmic_gflop_per_spectrogram(RIR_CFG, 201, 1)
+    # scripts/train_echoed_speech.py:45-46 from two freshly initialised sub-models (no checkpoints ship)
+    from acoustic_locating_vq_vae.vq_vae.echoed_speech_model import EchoedSpeechReconModel
+    rir = ConvolutionalVQVAE(*RIR_CFG, use_jitter=False, out_channels=1)
+    sp = ConvolutionalVQVAE(*SPEECH_CFG)
+    return EchoedSpeechReconModel(rir, sp, 201, 1024, 2, 1024, True), SPEECH_CFG, 61.73   # SURVEY 8(d)
+
+
+def dump_plan(sizes, budget=DUMP_BUDGET):
+    """{name: element count} -> {name: elements to keep}, float32, so that the files fit in ``budget`` bytes: every array
+    is kept whole when that fits, otherwise each is cut to min(size, cap) with the largest cap that fits."""
+    room = (budget - DUMP_HEADER * len(sizes)) // 4
+    if sum(sizes.values()) <= room:
+        return dict(sizes)
+    cap, left = 0, len(sizes)
+    for n in sorted(sizes.values()):
+        if n * left > room:
+            cap = room // left
+            break
+        room, left = room - n, left - 1
+    return {k: min(n, cap) for k, n in sizes.items()}
+
+
+def dump_outputs(snap, out_dir, budget=DUMP_BUDGET):
+    """Write a snapshot {name: array} to out_dir/<name>.npy as float32, within ``budget`` bytes in all (dump_plan); an
+    array that is cut keeps a sample of its flattened elements, in index order, drawn by a generator seeded from the
+    CRC-32 of its name."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    keep = dump_plan({k: int(np.size(v)) for k, v in snap.items()}, budget)
+    for name, a in snap.items():
+        a = np.asarray(a, dtype=np.float32)
+        if keep[name] < a.size:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, keep[name], replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def cpu_baseline(seconds_budget=20.0):
     """The oracle restatement (kind "port") timed on this host: speech ctor, B=4 (BASELINE configs[0])."""
     import numpy as np
@@ -227,7 +282,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the golden parity measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's outputs (loss, recon_error, perplexity, updated parameters) "
+                         "to DIR/<name>.npy, at most 64 MB in all (larger parameters as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -277,16 +337,8 @@ def main():
     def make(kind):
         """Model + per-spectrogram FLOPs of one BASELINE config, fresh init (seeded identically on every rank)."""
         torch.manual_seed(0)
-        if kind == "speech":
-            return ConvolutionalVQVAE(*SPEECH_CFG).cuda().train(), SPEECH_CFG, algorithmic_gflop_per_spectrogram(SPEECH_CFG, 500)
-        if kind == "rir":
-            m = ConvolutionalVQVAE(*RIR_CFG, use_jitter=False, out_channels=1).cuda().train()
-            return m, RIR_CFG, algorithmic_gflop_per_spectrogram(RIR_CFG, 201, 1)
-        # scripts/train_echoed_speech.py:45-46 from two freshly initialised sub-models (no checkpoints ship)
-        from acoustic_locating_vq_vae.vq_vae.echoed_speech_model import EchoedSpeechReconModel
-        rir = ConvolutionalVQVAE(*RIR_CFG, use_jitter=False, out_channels=1)
-        sp = ConvolutionalVQVAE(*SPEECH_CFG)
-        return EchoedSpeechReconModel(rir, sp, 201, 1024, 2, 1024, True).cuda().train(), SPEECH_CFG, 61.73   # SURVEY 8(d)
+        model, cfg, gf = config_model(kind)
+        return model.cuda().train(), cfg, gf
 
     def measure(trainer, raw, wiener, steps, warmup, use_timer):
         for _ in range(warmup):
@@ -311,7 +363,7 @@ def main():
             dt = max(per_rank)                               # the contract's MAX over ranks
         last = float(out[0])
         assert np.isfinite(last), "non-finite loss"
-        return dt, last, (timer.summary() if timer is not None else None), per_rank
+        return dt, last, (timer.summary() if timer is not None else None), per_rank, out
 
     def roofline(summ):
         # the dominant kernel = the convolution / weight-gradient kernel (rocprofv3 name: function + leading template arguments)
@@ -362,10 +414,11 @@ def main():
                 "bus_GBps": (2.0 * (world - 1) / world) * 4 * n / (ms * 1e-3) / 1e9 if world > 1 else 0.0,
                 "ranks_bit_identical": len(set(sums)) == 1, "flat_checksum": sums[0]}
 
-    def run_config(kind, dtype, B, steps, warmup, graph=True, timer=True, grad_buckets=None, want_rccl=False):
+    def run_config(kind, dtype, B, steps, warmup, graph=True, timer=True, grad_buckets=None, want_rccl=False, dump=None):
         """One (config, mode) measurement on a fresh model: K timed steps (graph replay when captured); the per-kernel
         durations behind `roofline` come from an instrumented eager pass of the same steps right after, because HIP
-        events cannot bracket kernels inside a replay."""
+        events cannot bracket kernels inside a replay.  ``dump``: directory for what the last timed step returned and
+        the parameters it left (rank 0), taken before any further step runs."""
         _ops.set_compute_dtype(dtype)
         np.random.seed(1234 + rank)                  # jitter: per-rank numpy stream (SURVEY 8e)
         model, cfg, gf = make(kind)
@@ -385,7 +438,11 @@ def main():
         if _ops.has_fp16_range(dtype):
             N.f16mx_range_flag(reset=True)
             trainer.opt.skipped_steps(reset=True)
-        elapsed, loss, summ, per_rank = measure(trainer, raw, wiener, steps, warmup, timer and trainer._graph is None)
+        elapsed, loss, summ, per_rank, out = measure(trainer, raw, wiener, steps, warmup, timer and trainer._graph is None)
+        if dump is not None and rank == 0:
+            snap = {k: v.detach().float().cpu().numpy() for k, v in zip(("loss", "recon_error", "perplexity"), out)}
+            snap.update(("param." + k, v.detach().float().cpu().numpy()) for k, v in model.named_parameters())
+            dump_outputs(snap, dump)
         value = world * B * steps / elapsed
         oc = 1 if kind == "rir" else None
         peak = step_peak_tflops(dtype, cfg, 201 if kind == "rir" else 500, oc) if kind != "echoed" else None
@@ -408,7 +465,7 @@ def main():
             g_saved, gl_saved = trainer._graph, getattr(trainer, "_graph_late", None)
             trainer._graph = None
             summ_steps = min(steps, 10)
-            _, _, summ, _ = measure(trainer, raw, wiener, summ_steps, 1, True)
+            _, _, summ, _, _ = measure(trainer, raw, wiener, summ_steps, 1, True)
             trainer._graph, trainer._graph_late = g_saved, gl_saved
         else:
             summ_steps = steps
@@ -439,7 +496,7 @@ def main():
 
     kind, B = args.config, args.batch
     head, cfg, gf = run_config(kind, args.dtype, B, args.steps, args.warmup, graph=not args.no_graph,
-                               timer=not args.no_kernel_timer, want_rccl=True)
+                               timer=not args.no_kernel_timer, want_rccl=True, dump=args.dump_outputs)
     full = None
     if rank == 0:
         full = {

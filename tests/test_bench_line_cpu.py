@@ -111,3 +111,50 @@ def test_committed_detail_files_compact_to_a_parsable_line():
         if name.startswith("r04") and name.endswith("bench_detail.json"):
             full = json.load(open(os.path.join(prof, name)))
             assert len(json.dumps(bench.compact_line(full), separators=(",", ":"))) < bench.LINE_LIMIT, name
+
+
+def _snapshot(kind, monkeypatch):
+    """What --dump-outputs writes for one --config: the step's three scalars and the freshly built model's parameters
+    (same names and shapes as after a step), built on the host."""
+    import numpy as np
+    import torch
+    from acoustic_locating_vq_vae.vq_vae import echoed_speech_model
+    monkeypatch.setattr(echoed_speech_model, "device", torch.device("cpu"))   # its constructor would move to the GPU
+    torch.manual_seed(0)
+    model, _, _ = bench.config_model(kind)
+    snap = {k: np.array(1.5, np.float32) for k in ("loss", "recon_error", "perplexity")}
+    snap.update(("param." + k, v.detach().numpy()) for k, v in model.named_parameters())
+    return snap
+
+
+def test_dump_outputs_fits_64mb_for_every_config(tmp_path, monkeypatch):
+    """The whole dump -- not each file -- stays within 64 MB for every --config choice; arrays that fit stay whole, cut ones
+    are an index-ordered sample, and the sample is the same from run to run."""
+    import numpy as np
+    for kind in ("speech", "rir", "echoed"):
+        snap = _snapshot(kind, monkeypatch)
+        out = tmp_path / kind
+        bench.dump_outputs(snap, str(out))
+        files = sorted(os.listdir(out))
+        assert files == sorted(k + ".npy" for k in snap), kind
+        total = sum(os.path.getsize(out / f) for f in files)
+        assert total <= 64 * 10 ** 6, (kind, total)
+        for k, v in snap.items():
+            got = np.load(out / (k + ".npy"))
+            assert got.dtype == np.float32
+            if got.size == v.size:
+                assert got.shape == v.shape and np.array_equal(got, v), (kind, k)
+            else:
+                assert got.ndim == 1 and got.size < v.size and np.isin(got, v.reshape(-1)).all(), (kind, k)
+        if kind == "echoed":
+            again = tmp_path / "again"
+            bench.dump_outputs(snap, str(again))
+            assert all(np.array_equal(np.load(out / f), np.load(again / f)) for f in files)
+
+
+def test_dump_plan_shares_one_cap():
+    budget = 4 * 1000 + bench.DUMP_HEADER * 3
+    assert bench.dump_plan({"a": 10, "b": 500, "c": 400}, budget) == {"a": 10, "b": 500, "c": 400}
+    plan = bench.dump_plan({"a": 10, "b": 5000, "c": 4000}, budget)
+    assert plan == {"a": 10, "b": 495, "c": 495}
+    assert bench.dump_plan({"a": 3000, "b": 3000}, 4 * 1000 + bench.DUMP_HEADER * 2) == {"a": 500, "b": 500}
