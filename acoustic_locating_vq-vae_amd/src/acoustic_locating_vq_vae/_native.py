@@ -110,6 +110,11 @@ _SIGNATURES = {
     "alvq_indices_to_i32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _c_void_p]),
     "alvq_embedding_bag_fwd_f32": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p] * 2),
     "alvq_embedding_bag_bwd_f32": (_i32, [_c_void_p] * 4 + [_i32] * 5 + [_c_void_p] * 2),
+    "alvq_istft_f32": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_istft_f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_griffin_lim_workspace_bytes": (_i64, [_i32] * 4),
+    "alvq_griffin_lim_f32": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_griffin_lim_f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -671,6 +676,49 @@ def spec_rir_wiener(speech_spec, echoed_spec):
                                           _ptr(wiener, torch.float64), _ptr(ws, torch.float64), B, F, T, _stream()),
            "alvq_spec_rir_wiener_f64")
     return speech_pow, echoed_pow, rir_pow, wiener
+
+
+def _spec_dims(spec, n_fft, who):
+    if spec.dim() != 3 or spec.dtype not in (torch.complex64, torch.complex128):
+        raise RuntimeError("%s: expected a complex64 / complex128 (B, F, T) spectrogram (got %s %s)"
+                           % (who, spec.dtype, tuple(spec.shape)))
+    B, F, T = spec.shape
+    if F != n_fft // 2 + 1:
+        raise RuntimeError("%s: %d frequency bins, n_fft=%d has %d" % (who, F, n_fft, n_fft // 2 + 1))
+    return B, T, torch.float64 if spec.dtype == torch.complex128 else torch.float32
+
+
+def istft(spec, n_fft=400, hop=160, length=None):
+    """Inverse of ``stft_complex``: (B, n_fft/2+1, T) complex64 / complex128 -> (B, length) float32 / float64 waveforms
+    (alvq_istft_*; length defaults to hop*(T-1))."""
+    B, T, real = _spec_dims(spec, n_fft, "istft")
+    length = hop * (T - 1) if length is None else int(length)
+    sr = torch.view_as_real(spec.resolve_conj().contiguous())
+    wave = torch.empty((B, length), device=spec.device, dtype=real)
+    ws = torch.empty((B, T, n_fft), device=spec.device, dtype=real)
+    name = "alvq_istft_f64" if real == torch.float64 else "alvq_istft_f32"
+    _check(getattr(lib(), name)(_ptr(sr, real, "spec"), _ptr(wave, real), _ptr(ws, real), B, T, n_fft, hop, length, _stream()),
+           name)
+    return wave
+
+
+def griffin_lim(mag, angles, n_iter, momentum, n_fft, hop, length):
+    """Griffin-Lim (alvq_griffin_lim_*): magnitude mag (B, n_fft/2+1, T) float32 / float64 normalised as ``stft_complex``,
+    complex start phases angles of the matching complex dtype and shape -> (B, length) waveforms."""
+    B, T, real = _spec_dims(angles, n_fft, "griffin_lim")
+    if mag.shape != angles.shape or mag.dtype != real:
+        raise RuntimeError("griffin_lim: mag must be %s of shape %s (got %s %s)" % (real, tuple(angles.shape), mag.dtype,
+                                                                                   tuple(mag.shape)))
+    ar = torch.view_as_real(angles.resolve_conj().contiguous())
+    wave = torch.empty((B, length), device=mag.device, dtype=real)
+    nbytes = lib().alvq_griffin_lim_workspace_bytes(B, T, n_fft, 8 if real == torch.float64 else 4)
+    if nbytes < 0:
+        raise RuntimeError("griffin_lim: bad dims (B=%d T=%d n_fft=%d)" % (B, T, n_fft))
+    ws = torch.empty((nbytes,), device=mag.device, dtype=torch.uint8)
+    name = "alvq_griffin_lim_f64" if real == torch.float64 else "alvq_griffin_lim_f32"
+    _check(getattr(lib(), name)(_ptr(mag, real, "mag"), _ptr(ar, real, "angles"), _ptr(wave, real), _ptr(ws, torch.uint8), B, T,
+                                n_fft, hop, int(length), int(n_iter), float(momentum), _stream()), name)
+    return wave
 
 
 # ----------------------------------------------------------------------------------------------- bf16 path

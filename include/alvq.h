@@ -222,6 +222,36 @@ int alvq_fir_same_f64(const float* wave, const double* h, double* out, int B, in
 int alvq_spec_rir_wiener_f64(const float* speech_spec, const double* echoed_spec, float* speech_pow, double* echoed_pow,
                              double* rir_pow, double* wiener, double* workspace, int B, int F, int T, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Inverse STFT, the exact inverse of alvq_stft_complex_* (torchaudio InverseSpectrogram(n_fft, hop, center=True, pad=0,
+ * normalized=True) semantics): spec (B, n_fft/2+1, T) interleaved (re, im) as alvq_stft_complex_* writes it -> wave (B, length).
+ * One-sided inverse DFT (the imaginary parts of the DC and Nyquist bins are ignored, as irfft), times sqrt(sum(w^2)) and the
+ * periodic Hann window w, overlap-added and divided by the overlap-added w^2, n_fft/2 trimmed at the start; samples past
+ * n_fft/2 + hop*(T-1) are 0 (torch.istft's zero-padding of an explicit length).  length = hop*(T-1) is the default framing.
+ * workspace: B*T*n_fft elements of the spectrum's precision.  Even n_fft >= 4, up to 2048 (f32) / 1024 (f64).  The NOLA
+ * condition (overlap-added w^2 > 1e-11 over the output) is checked on the host: ALVQ_EINVAL with no launch if it fails.
+ * Fixed-order sums throughout: bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+int alvq_istft_f32(const float* spec, float* wave, float* workspace, int B, int T, int n_fft, int hop, int length, void* stream);
+int alvq_istft_f64(const double* spec, double* wave, double* workspace, int B, int T, int n_fft, int hop, int length,
+                   void* stream);
+
+/* Griffin-Lim phase reconstruction (torchaudio.functional.griffinlim, the fast variant with momentum) of a magnitude
+ * spectrogram mag (B, n_fft/2+1, T) normalised as alvq_stft_complex_* (|spec|), from the complex start phases angles (same
+ * shape, interleaved; used as given, not normalised, as torchaudio does):
+ *   tprev = 0; repeat n_iter: inverse = istft(mag * angles); rebuilt = STFT(inverse) (unnormalised);
+ *              a = rebuilt - momentum/(1+momentum) * tprev; angles = a / (|a| + 1e-16); tprev = rebuilt
+ *   wave = istft(mag * angles)                                                          (istft: alvq_istft_*)
+ * -> wave (B, length).  n_iter >= 0, 0 <= momentum < 1; with n_iter > 0, 1 + length/hop == T and length > n_fft/2.
+ * One call enqueues 3*n_iter + 2 launches on stream, with no host sync: a linear chain, capturable in a single-stream graph.
+ * workspace: alvq_griffin_lim_workspace_bytes(B, T, n_fft, sizeof(element)) =
+ *   (4*B*(n_fft/2+1)*T + B*T*n_fft) * elem_bytes   (two complex spectra + the inverse's frames); -1 for bad arguments. */
+int64_t alvq_griffin_lim_workspace_bytes(int B, int T, int n_fft, int elem_bytes);
+int alvq_griffin_lim_f32(const float* mag, const float* angles, float* wave, void* workspace, int B, int T, int n_fft, int hop,
+                         int length, int n_iter, double momentum, void* stream);
+int alvq_griffin_lim_f64(const double* mag, const double* angles, double* wave, void* workspace, int B, int T, int n_fft, int hop,
+                         int length, int n_iter, double momentum, void* stream);
+
 /* ================================================================================================
  * bf16 throughput path (BASELINE configs[1]: "batch=64 bf16").  Storage bf16, accumulation fp32.
  *
