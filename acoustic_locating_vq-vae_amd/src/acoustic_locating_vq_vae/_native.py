@@ -115,6 +115,8 @@ _SIGNATURES = {
     "alvq_griffin_lim_workspace_bytes": (_i64, [_i32] * 4),
     "alvq_griffin_lim_f32": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_griffin_lim_f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_rir_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p] + [ctypes.c_double] * 2
+                     + [_i32] * 2 + [_c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -719,6 +721,24 @@ def griffin_lim(mag, angles, n_iter, momentum, n_fft, hop, length):
     _check(getattr(lib(), name)(_ptr(mag, real, "mag"), _ptr(ar, real, "angles"), _ptr(wave, real), _ptr(ws, torch.uint8), B, T,
                                 n_fft, hop, int(length), int(n_iter), float(momentum), _stream()), name)
     return wave
+
+
+def rir(src, rcv, L, beta, c, fs, nsample, order=-1, hp_filter=True):
+    """Room impulse responses (alvq_rir_f64): src, rcv (B,3) float64 positions on the GPU, room L (3 floats), six wall
+    reflection coefficients beta -> (B, nsample) float64."""
+    if src.dim() != 2 or src.shape[1] != 3 or rcv.shape != src.shape:
+        raise RuntimeError("rir: src and rcv must both be (B, 3) (got %s and %s)" % (tuple(src.shape), tuple(rcv.shape)))
+    L = [float(v) for v in L]
+    beta = [float(v) for v in beta]
+    if len(L) != 3 or len(beta) != 6:
+        raise RuntimeError("rir: need 3 room dimensions and 6 reflection coefficients (got %d and %d)" % (len(L), len(beta)))
+    B = src.shape[0]
+    h = torch.empty((B, int(nsample)), device=src.device, dtype=torch.float64)
+    beta_c = (ctypes.c_double * 6)(*beta)
+    _check(lib().alvq_rir_f64(_ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"), _ptr(h, torch.float64), B,
+                              int(nsample), L[0], L[1], L[2], ctypes.cast(beta_c, _c_void_p), float(c), float(fs), int(order),
+                              int(bool(hp_filter)), _stream()), "alvq_rir_f64")
+    return h
 
 
 # ----------------------------------------------------------------------------------------------- bf16 path

@@ -15,15 +15,32 @@ functional.griffinlim in the reference's notebooks; HIP kernels of csrc/istft.hi
     wave = griffin_lim(power)                                       # power (or magnitude, power=1) -> waveform, 32 iterations
     wave = waveform_from_reconstruction(model(x)[1], raw_power)    # a speech model's standardised output -> waveform
 
-The room impulse response itself comes from the ``rir_generator`` C++ package in the reference
-(genereate_dataset.py:21-29), which is out of scope; any (Nh,) or (B, Nh) float64 response can be passed in.
+The room impulse response, which the reference takes from the ``rir_generator`` C++ package (genereate_dataset.py:21-29), is
+made on the device too (image-source method, csrc/rir.hip), and with it the whole generator: a direction goes in, a sample
+6-tuple comes out, and ``SpecsDataset`` reads what ``write_specs_dataset`` writes:
+
+    h = rir_generate(c=340, fs=16000, r=[2.5, 1.5, 1.5], s=[3, 2, 2.5], L=[4, 5, 3], reverberation_time=0.4)  # (nsample, 1)
+    samples = generate_samples(wave)                          # theta ~ U(-pi, pi) -> source -> RIR -> echoed -> 6-tuple
+    write_specs_dataset("spec_data/train", samples, DATASET_CONFIG)
+
+Parity with ``rir_generator`` itself is unpinned (the package is absent and the reference holds no fixture); the RIR is
+pinned by the closed-form direct path, reciprocity, scipy's lfilter for the high-pass and a float64 restatement.
+Any other (Nh,) or (B, Nh) float64 response can still be passed to ``specs_from_waveform``.
 """
+import math
+import os
+
+import numpy as np
 import torch
 
 from . import _native as N
 from .data_preprocessing import SPEC_FRAMES
 
 N_FFT, HOP = 400, 160        # genereate_dataset.py:73-74 at fs = 16 kHz
+SOUND_SPEED = 340.0          # genereate_dataset.py:54 (C)
+# the generator's __main__ constants under SpecsDataset's CONFIG_KEYS names (genereate_dataset.py:54-84)
+DATASET_CONFIG = {"fs": 16000, "receiver_position": [2.5, 1.5, 1.5], "room_dimensions": [4, 5, 3], "reverberation_time": 0.4,
+                  "n_sample": 6400, "R": 1, "NFFT": 400, "HOP_LENGTH": 160, "Z_LOC_SOURCE": 1}
 
 
 def specs_from_waveform(wave, h_rir, n_fft=N_FFT, hop=HOP):
@@ -97,3 +114,168 @@ def waveform_from_reconstruction(recon, raw_power, **gl_kwargs):
     std = raw.std(dim=1, keepdim=True)
     power = (recon.detach()[:, :, :T].to(raw.dtype) * (std + 1e-8) + mean).clamp_min(0.0)
     return griffin_lim(power.contiguous(), power=2.0, **gl_kwargs)
+
+
+def _sabine_beta(L, c, reverberation_time):
+    V = L[0] * L[1] * L[2]
+    S = 2.0 * (L[0] * L[2] + L[1] * L[2] + L[0] * L[1])
+    alpha = 24.0 * V * math.log(10.0) / (c * S * reverberation_time)
+    if alpha > 1:
+        raise ValueError("the reflection coefficients cannot be calculated for room %s and reverberation time %g (alpha = %g > 1);"
+                         " give beta or change the room" % (list(L), reverberation_time, alpha))
+    return [math.sqrt(1.0 - alpha)] * 6
+
+
+def _room_params(L, c, beta, reverberation_time, nsample, dim, fs):
+    """(L, beta, nsample) after rir_generator's keyword rules; raises before anything is launched."""
+    L = [float(v) for v in np.asarray(L, dtype=np.float64).reshape(-1)]
+    if len(L) != 3 or not all(math.isfinite(v) and v > 0 for v in L):
+        raise ValueError("room dimensions L must be 3 positive lengths, got %r" % (L,))
+    if not (c > 0 and fs > 0):
+        raise ValueError("c and fs must be > 0, got c=%r fs=%r" % (c, fs))
+    if (beta is None) == (reverberation_time is None):
+        raise ValueError("give exactly one of beta and reverberation_time")
+    if reverberation_time is not None:
+        if not reverberation_time > 0:
+            raise ValueError("reverberation_time must be > 0, got %r" % (reverberation_time,))
+        beta = _sabine_beta(L, c, float(reverberation_time))
+        if nsample is None:
+            nsample = int(reverberation_time * fs)
+    else:
+        beta = [float(v) for v in np.asarray(beta, dtype=np.float64).reshape(-1)]
+        if len(beta) != 6 or not all(abs(v) <= 1 for v in beta):
+            raise ValueError("beta must be 6 reflection coefficients with |beta| <= 1, got %r" % (beta,))
+        if nsample is None:
+            raise ValueError("nsample is required with an explicit beta")
+    if dim not in (2, 3):
+        raise ValueError("dim must be 2 or 3, got %r" % (dim,))
+    if dim == 2:
+        beta[4] = beta[5] = 0.0
+    if int(nsample) <= 0:
+        raise ValueError("nsample must be > 0, got %r" % (nsample,))
+    return L, beta, int(nsample)
+
+
+def _positions(x, name, device):
+    """float64 (n, 3) tensor on device from a tensor, array or list of one or more positions."""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+    t = t.to(torch.float64)
+    if t.dim() == 1:
+        t = t.unsqueeze(0)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s must be (3,) or (n, 3) positions, got shape %s" % (name, tuple(t.shape)))
+    return t.to(device).contiguous()
+
+
+def _check_device(t, who):
+    if not t.is_cuda:
+        raise RuntimeError("%s: tensors must live on the GPU (got %s); the HIP path has no CPU fallback" % (who, t.device))
+
+
+def room_impulse_responses(src, receiver, room, reverberation_time=None, beta=None, nsample=None, c=SOUND_SPEED, fs=16000,
+                           order=-1, dim=3, hp_filter=True):
+    """Room impulse responses, (B, nsample) float64 on the GPU, for sources src (B, 3) float64 on the GPU and one receiver (3,)
+    or one per source (B, 3): the batched form of ``rir_generate``, with its keyword rules for beta / reverberation_time /
+    nsample / dim.  When not inside a graph capture the source-receiver distances are checked (one host sync): a source on
+    its receiver raises ValueError; inside a capture there is no check and such a pair gives an infinite response."""
+    L, beta, nsample = _room_params(room, c, beta, reverberation_time, nsample, dim, fs)
+    if not isinstance(src, torch.Tensor) or src.dim() != 2 or src.shape[1] != 3 or src.dtype != torch.float64:
+        raise ValueError("room_impulse_responses: src must be a float64 (B, 3) tensor")
+    _check_device(src, "room_impulse_responses")
+    rcv = _positions(receiver, "receiver", src.device)
+    if rcv.shape[0] == 1:
+        rcv = rcv.expand(src.shape[0], 3).contiguous()
+    elif rcv.shape[0] != src.shape[0]:
+        raise ValueError("room_impulse_responses: %d receivers for %d sources" % (rcv.shape[0], src.shape[0]))
+    src = src.contiguous()
+    if not torch.cuda.is_current_stream_capturing() and bool((src == rcv).all(dim=1).any()):
+        raise ValueError("room_impulse_responses: a source coincides with its receiver (distance 0, infinite gain)")
+    return N.rir(src, rcv, L, beta, c, fs, nsample, order, hp_filter)
+
+
+def rir_generate(c, fs, r, s, L, beta=None, reverberation_time=None, nsample=None, mtype="omnidirectional", order=-1, dim=3,
+                 orientation=None, hp_filter=True, device="cuda"):
+    """``rir_generator.generate`` on the GPU: receivers r (3,) or (M, 3), source s (3,), room L (m) -> (nsample, M) float64 on
+    ``device``, the package's layout.
+
+    Exactly one of beta (6 wall reflection coefficients, x0 x1 y0 y1 z0 z1) and reverberation_time (T60, s) is given.  From
+    T60, Sabine's formula gives alpha = 24 V ln10 / (c S T60) and all six beta = +sqrt(1 - alpha) (alpha > 1 raises
+    ValueError); nsample then defaults to int(T60 fs).  The sign of that beta is this package's choice: the Python package's
+    own choice cannot be checked here, and negative explicit beta values (allowed) give the other convention.  With an
+    explicit beta, nsample is required.  Only the omnidirectional microphone is supported: another mtype or an orientation
+    raises.  dim=2 zeroes beta[4] and beta[5]; order=-1 keeps every reflection order; hp_filter applies the 100 Hz high-pass.
+    """
+    if str(getattr(mtype, "name", mtype)).lower() not in ("omnidirectional", "o"):
+        raise ValueError("rir_generate: only the omnidirectional microphone is supported, got mtype=%r" % (mtype,))
+    if orientation is not None:
+        raise ValueError("rir_generate: microphone orientation is not supported (omnidirectional only)")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("rir_generate: device must be a GPU (got %s); the HIP path has no CPU fallback" % device)
+    L, beta, nsample = _room_params(L, c, beta, reverberation_time, nsample, dim, fs)
+    rcv = _positions(r, "r", "cpu")
+    src = _positions(s, "s", "cpu")
+    if src.shape[0] != 1:
+        raise ValueError("rir_generate: one source position s, got %d" % src.shape[0])
+    if bool((rcv == src).all(dim=1).any()):
+        raise ValueError("rir_generate: the source coincides with a receiver (distance 0, infinite gain)")
+    M = rcv.shape[0]
+    h = N.rir(src.expand(M, 3).contiguous().to(device), rcv.to(device), L, beta, c, fs, nsample, order, hp_filter)
+    return h.t()
+
+
+def source_positions(theta, receiver, room, R, z):
+    """SpecsDataset.get_source_coordinates on the device: theta (B,) float64 -> (B, 3) float64 sources
+    min(receiver + (R cos theta, R sin theta, z), room) (genereate_dataset.py:18-20).  A source on the receiver raises."""
+    if not isinstance(theta, torch.Tensor):
+        raise ValueError("source_positions: theta must be a tensor")
+    _check_device(theta, "source_positions")
+    theta = theta.reshape(-1).to(torch.float64)
+    rcv = _positions(receiver, "receiver", theta.device)
+    ring = torch.stack((R * torch.cos(theta), R * torch.sin(theta), torch.full_like(theta, float(z))), dim=1)
+    room_t = _positions(room, "room", theta.device)
+    src = torch.minimum(rcv + ring, room_t)
+    if bool((src == rcv).all(dim=1).any()):
+        raise ValueError("source_positions: a source coincides with the receiver (distance 0, infinite gain)")
+    return src
+
+
+def generate_samples(wave, theta=None, generator=None, config=DATASET_CONFIG, c=SOUND_SPEED):
+    """The dataset generator on the device (genereate_dataset.py:13-51, batched): wave (B, S) float32 clean speech on the GPU
+    -> (speech_spec (B,F,T) fp32, rir_spec fp64, echoed_spec fp64, sample_rate int, theta (B,) fp64, wiener_est (B,F) fp64).
+    theta: source directions (B,); None draws U(-pi, pi) in float64 on the device (from ``generator`` if given).  config:
+    the generator's constants (``DATASET_CONFIG`` keys): source on the ring of radius R at height Z_LOC_SOURCE above the
+    receiver, clipped to the room; RIR from reverberation_time with n_sample samples; STFT with NFFT / HOP_LENGTH."""
+    if wave.dim() != 2 or wave.dtype != torch.float32:
+        raise ValueError("generate_samples: wave must be float32 (B, S), got %s %s" % (wave.dtype, tuple(wave.shape)))
+    _check_device(wave, "generate_samples")
+    B = wave.shape[0]
+    if theta is None:
+        theta = torch.rand(B, dtype=torch.float64, device=wave.device, generator=generator) * (2.0 * math.pi) - math.pi
+    else:
+        theta = torch.as_tensor(theta, dtype=torch.float64).reshape(-1).to(wave.device)
+        if theta.shape[0] != B:
+            raise ValueError("generate_samples: %d angles for %d waveforms" % (theta.shape[0], B))
+    fs = int(config["fs"])
+    src = source_positions(theta, config["receiver_position"], config["room_dimensions"], config["R"], config["Z_LOC_SOURCE"])
+    h = room_impulse_responses(src, config["receiver_position"], config["room_dimensions"],
+                               reverberation_time=config["reverberation_time"], nsample=config["n_sample"], c=c, fs=fs)
+    speech, rir, echoed, wiener = specs_from_waveform(wave, h, n_fft=int(config["NFFT"]), hop=int(config["HOP_LENGTH"]))
+    return speech, rir, echoed, fs, theta, wiener
+
+
+def write_specs_dataset(dest, samples, config=DATASET_CONFIG, start=0):
+    """Write ``generate_samples`` output as the generator does (genereate_dataset.py:97-103): {start+i}.pt 6-tuples
+    ((201,T) fp32 / fp64 / fp64 powers, int rate, (1,) fp64 theta, (201,) fp64 Wiener estimate) and dataset_config.npy (a
+    pickled dict), so that SpecsDataset and spec_dataset_preprocessing read them unchanged.  Returns the written paths."""
+    speech, rir, echoed, fs, theta, wiener = samples
+    os.makedirs(dest, exist_ok=True)
+    speech, rir, echoed, theta, wiener = (t.detach().cpu() for t in (speech, rir, echoed, theta, wiener))
+    paths = []
+    for i in range(speech.shape[0]):
+        path = os.path.join(dest, "%d.pt" % (start + i))
+        torch.save((speech[i].clone(), rir[i].clone(), echoed[i].clone(), int(fs), theta[i].reshape(1).clone(),
+                    wiener[i].clone()), path)
+        paths.append(path)
+    np.save(os.path.join(dest, "dataset_config.npy"), dict(config))
+    return paths

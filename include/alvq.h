@@ -252,6 +252,22 @@ int alvq_griffin_lim_f32(const float* mag, const float* angles, float* wave, voi
 int alvq_griffin_lim_f64(const double* mag, const double* angles, double* wave, void* workspace, int B, int T, int n_fft, int hop,
                          int length, int n_iter, double momentum, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Room impulse responses by the image-source method (Allen & Berkley 1979 as Habets' RIR generator states it, i.e.
+ * rir_generator.generate with an omnidirectional receiver), float64.  src, rcv: device (B,3) source and receiver positions
+ * (m); h: device (B, nsample).  Shared: the room Lx x Ly x Lz (m), the six wall reflection coefficients beta6_host (host array:
+ * x0, x1, y0, y1, z0, z1; |beta| <= 1, negative allowed), sound speed c (m/s), sample rate fs, order (-1 = every reflection
+ * order) and hp_filter (1 = the generator's 100 Hz high-pass, lfilter([1, A1, R1], [1, -B1, -B2]) per response).
+ * With cTs = c/fs, Tw = 2*round(0.004*fs) and n_a = ceil(nsample / (2*L_a/cTs)), every image (m_a in [-n_a, n_a], q, j, k in
+ * {0,1}) within the order whose distance d (in samples) has floor(d) < nsample adds
+ *   refl / (4 pi d cTs) * 0.5 (1 + cos(2 pi (t-d)/Tw)) * sinc(pi (t-d))   at t = floor(d) - Tw/2 + 1 + n, n in [0, Tw).
+ * A 2-D room is beta[4] = beta[5] = 0.  Fs up to 128 kHz (Tw <= 1024); nsample <= 2^24.  A source on the receiver gives an
+ * infinite gain (callers reject it).  No atomics: each output sample is summed in one fixed image order that depends on the
+ * item's own geometry only, so a response is bitwise the same in any batch.  One or two launches, no host sync, no workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int alvq_rir_f64(const double* src, const double* rcv, double* h, int B, int nsample, double Lx, double Ly, double Lz,
+                 const double* beta6_host, double c, double fs, int order, int hp_filter, void* stream);
+
 /* ================================================================================================
  * bf16 throughput path (BASELINE configs[1]: "batch=64 bf16").  Storage bf16, accumulation fp32.
  *
