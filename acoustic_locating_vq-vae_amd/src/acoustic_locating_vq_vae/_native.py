@@ -117,6 +117,11 @@ _SIGNATURES = {
     "alvq_griffin_lim_f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_rir_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p] + [ctypes.c_double] * 2
                      + [_i32] * 2 + [_c_void_p]),
+    "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
+    "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
+    "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
+    "alvq_tsne_descend_workspace_bytes": (_i64, [_i32]),
+    "alvq_tsne_descend_f64": (_i32, [_c_void_p] * 7 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -739,6 +744,56 @@ def rir(src, rcv, L, beta, c, fs, nsample, order=-1, hp_filter=True):
                               int(nsample), L[0], L[1], L[2], ctypes.cast(beta_c, _c_void_p), float(c), float(fs), int(order),
                               int(bool(hp_filter)), _stream()), "alvq_rir_f64")
     return h
+
+
+# ----------------------------------------------------------------------------------------------- t-SNE
+def tsne_code_sqdist(codes):
+    """int32 (N, L) code sequences -> (N, N) fp32 squared distances of their one-hot expansions (alvq_tsne_code_sqdist_f32)."""
+    if codes.dim() != 2:
+        raise RuntimeError("tsne_code_sqdist: codes must be (N, L) (got %s)" % (tuple(codes.shape),))
+    N, L = codes.shape
+    d2 = torch.empty((N, N), device=codes.device, dtype=torch.float32)
+    _check(lib().alvq_tsne_code_sqdist_f32(_ptr(codes, torch.int32, "codes"), _ptr(d2), N, L, _stream()),
+           "alvq_tsne_code_sqdist_f32")
+    return d2
+
+
+def tsne_affinities(P, perplexity):
+    """In place: (N, N) fp32 distances -> the joint affinities (alvq_tsne_affinities_f32).  Returns (beta, S), (N,) fp64 each."""
+    N = P.shape[0]
+    if P.dim() != 2 or P.shape[1] != N:
+        raise RuntimeError("tsne_affinities: P must be (N, N) (got %s)" % (tuple(P.shape),))
+    nbytes = lib().alvq_tsne_affinities_workspace_bytes(N)
+    if nbytes < 0:
+        raise RuntimeError("tsne_affinities: N=%d out of range" % N)
+    beta = torch.empty((N,), device=P.device, dtype=torch.float64)
+    S = torch.empty((N,), device=P.device, dtype=torch.float64)
+    ws = torch.empty((nbytes,), device=P.device, dtype=torch.uint8)
+    _check(lib().alvq_tsne_affinities_f32(_ptr(P, name="P"), _ptr(beta, torch.float64), _ptr(S, torch.float64),
+                                          _ptr(ws, torch.uint8), N, float(perplexity), _stream()), "alvq_tsne_affinities_f32")
+    return beta, S
+
+
+def tsne_descend(P, Y, update, gains, grad, stats, n_iter, exaggeration, momentum, learning_rate, workspace=None):
+    """n_iter iterations of one t-SNE descent phase (alvq_tsne_descend_f64): Y, update, gains (N, 2) fp64 in place; grad (N, 2)
+    and stats (2,) fp64 out (the last iteration's gained gradient, and its KL and gradient norm)."""
+    N = Y.shape[0]
+    for name, t in (("Y", Y), ("update", update), ("gains", gains), ("grad", grad)):
+        if t.shape != (N, 2):
+            raise RuntimeError("tsne_descend: %s must be (%d, 2) (got %s)" % (name, N, tuple(t.shape)))
+    if P.shape != (N, N) or stats.numel() < 2:
+        raise RuntimeError("tsne_descend: P must be (%d, %d) and stats hold 2 values" % (N, N))
+    nbytes = lib().alvq_tsne_descend_workspace_bytes(N)
+    if nbytes < 0:
+        raise RuntimeError("tsne_descend: N=%d out of range" % N)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((nbytes,), device=Y.device, dtype=torch.uint8)
+    f64 = torch.float64
+    _check(lib().alvq_tsne_descend_f64(_ptr(P, name="P"), _ptr(Y, f64, "Y"), _ptr(update, f64, "update"),
+                                       _ptr(gains, f64, "gains"), _ptr(grad, f64, "grad"), _ptr(stats, f64, "stats"),
+                                       _ptr(workspace, torch.uint8, "workspace"), N, int(n_iter), float(exaggeration),
+                                       float(momentum), float(learning_rate), _stream()), "alvq_tsne_descend_f64")
+    return workspace
 
 
 # ----------------------------------------------------------------------------------------------- bf16 path

@@ -268,6 +268,36 @@ int alvq_griffin_lim_f64(const double* mag, const double* angles, double* wave, 
 int alvq_rir_f64(const double* src, const double* rcv, double* h, int B, int nsample, double Lx, double Ly, double Lz,
                  const double* beta6_host, double c, double fs, int order, int hp_filter, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
+ * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
+ * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
+ *
+ * Code distances: d2[i][j] = 2 * (L - #{l : codes[i][l] == codes[j][l]}), the squared Euclidean distance of the one-hot
+ * expansions (exact; zero diagonal).  codes: int32 (N, L). */
+int alvq_tsne_code_sqdist_f32(const int32_t* codes, float* d2, int N, int L, void* stream);
+
+/* Joint affinities, in place: P (N, N) holds distances on entry (used as given, the diagonal ignored) and the joint P on
+ * return.  Per row, a binary search in fp64 for beta (from 1, <= 100 steps, |H - log(perplexity)| <= 1e-5) makes the
+ * conditional P_ij = exp(-d_ij beta_i) / S_i; then P = (Pc + Pc^T) / max(sum, eps) clamped to >= eps off the diagonal
+ * (eps = 2^-52), exactly symmetric, diagonal 0.  beta, S: (N) doubles out, the beta and sum of each row's last evaluation.
+ * 0 < perplexity < N.  workspace: alvq_tsne_affinities_workspace_bytes(N) = (N + 1) * 8 bytes; -1 for N out of range. */
+int64_t alvq_tsne_affinities_workspace_bytes(int N);
+int alvq_tsne_affinities_f32(float* P, double* beta, double* S, void* workspace, int N, double perplexity, void* stream);
+
+/* n_iter >= 1 iterations of one descent phase on the embedding Y (N, 2) fp64, in place, with the phase's state update and
+ * gains (N, 2) fp64 (the caller zeroes / sets them to 1 at the start of a phase):
+ *   num_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} num_ij, Q_ij = max(num_ij / Z, eps);
+ *   grad_i = 4 sum_{j != i} (e P_ij - Q_ij) num_ij (y_i - y_j)             (e = exaggeration, every y of the iteration's start)
+ *   gains += 0.2 where update * grad < 0, else gains *= 0.8; gains >= 0.01; grad *= gains;
+ *   update = momentum * update - learning_rate * grad;  Y += update.
+ * grad (N, 2) out: the gained gradient of the last iteration.  stats (2 doubles) out, of the last iteration:
+ * KL = sum_{i != j} e P_ij log(max(e P_ij, eps) / Q_ij) and |grad|.  3 * n_iter + 2 launches (and, for odd n_iter, one
+ * device-to-device copy) on stream, no host sync.  workspace: alvq_tsne_descend_workspace_bytes(N) = (5N + 1) * 8 bytes. */
+int64_t alvq_tsne_descend_workspace_bytes(int N);
+int alvq_tsne_descend_f64(const float* P, double* Y, double* update, double* gains, double* grad, double* stats, void* workspace,
+                          int N, int n_iter, double exaggeration, double momentum, double learning_rate, void* stream);
+
 /* ================================================================================================
  * bf16 throughput path (BASELINE configs[1]: "batch=64 bf16").  Storage bf16, accumulation fp32.
  *
