@@ -1,19 +1,23 @@
 // Room impulse responses by the image-source method (Allen & Berkley 1979, as Habets' RIR generator states it), float64,
-// omnidirectional receiver.  Each batch item has its own source and receiver; the room, wall reflection coefficients, c, fs,
-// nsample, order and the high-pass switch are shared.  Lengths are in samples (x / cTs, cTs = c / fs) throughout.
+// omnidirectional receiver.  Each batch item has its own source and receiver.  alvq_rir_f64 shares the room and the wall
+// reflection coefficients across the batch; alvq_rir_rooms_f64 reads a room and six coefficients per item.  c, fs, nsample,
+// order and the high-pass switch are shared.  Lengths are in samples (x / cTs, cTs = c / fs) throughout.
 //
 // Two kernels, no atomics, every output sample a sum in one fixed order (bitwise reproducible, independent of the batch):
 //   rir_gather_kernel  output-stationary.  One workgroup = (item b, a tile of RIR_TILE output samples); lane i of every wave owns
 //                      sample t0 + i.  Only images whose Tw-tap window reaches the tile can contribute, i.e. whose distance lies in
 //                      a spherical shell around the receiver.  The image grid is cut into columns (m_x, q, m_y, j); for each
 //                      column the two m_z intervals of each k that meet the shell are solved in closed form (widened by one), and
-//                      every candidate gets the exact test.  Wave w takes the columns w*64 + lane (+ 256 per round); each
+//                      every candidate gets the exact test.  Templated on where the room and beta come from: the launch's
+//                      parameters, or the item's row of room (B,3) / beta (B,6), from which each workgroup derives the item's
+//                      image ranges with the host's float64 expression (so an item's bits equal a one-room launch's).  Wave w takes the columns w*64 + lane (+ 256 per round); each
 //                      sub-round every lane posts its next accepted image to its LDS slot, and the wave adds the 64 slots in
 //                      slot order to its own partial.  The four partials are added in wave order at the end.
 //                      Per tap there is no cos / sin: sin(pi (t-d)) = -(-1)^(t-fd) sin(pi frac) (one sinpi per image), and the
 //                      window cos(2 pi (m - frac)/Tw) is the rotation of a per-launch table cos / sin(2 pi m/Tw) by frac.
 //   rir_highpass_kernel  the generator's 100 Hz high-pass, a serial recurrence: one thread per response, in place, over the
 //                      response staged in LDS.
+#include <cfloat>
 #include <climits>
 #include <cmath>
 
@@ -71,14 +75,58 @@ struct Image {
   int fd;
 };
 
+// Per-item status bits of alvq_rir_rooms_f64 (an item with any bit set is not summed: its response is left zero).
+constexpr int RIR_BAD_BETA = 1;    // some |beta| > 1, or not a number
+constexpr int RIR_BAD_ROOM = 2;    // a room side not a positive finite length, or an image range above RIR_MAX_N
+constexpr double RIR_MAX_N = 4096.0;
+
+// The image range of one axis: the generator's ceil(nsample / (2 L)), this exact float64 expression (host and device alike).
+__host__ __device__ __forceinline__ double rir_image_range(int nsample, double L) { return ceil((double)nsample / (2.0 * L)); }
+
+struct RirRooms {           // alvq_rir_rooms_f64's per-item inputs (all null for alvq_rir_f64)
+  const double* room;       // (B,3) metres
+  const double* beta;       // (B,6)
+  int* status;              // (B,) RIR_BAD_* bits, written by the item's first tile
+};
+
+__device__ __forceinline__ double wave_uniform(double v) {   // v is the same in every lane: keep it in scalar registers
+  const long long u = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readfirstlane((int)u), hi = __builtin_amdgcn_readfirstlane((int)(u >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+// Item b's room in samples, beta, image ranges and column count into P; returns the item's status bits.
+__device__ __forceinline__ int rir_item_params(RirParams& P, const RirRooms& R, int b) {
+  int st = 0;
+  for (int a = 0; a < 6; ++a) {
+    const double v = R.beta[6 * b + a];
+    if (!(fabs(v) <= 1.0)) st |= RIR_BAD_BETA;
+    P.beta[a] = v;
+  }
+  for (int a = 0; a < 3; ++a) {
+    const double La = R.room[3 * b + a];
+    P.L[a] = wave_uniform(La / P.cTs);
+    const double n = rir_image_range(P.nsample, P.L[a]);
+    if (!(La > 0.0 && La <= DBL_MAX && n <= RIR_MAX_N)) st |= RIR_BAD_ROOM;
+    P.n[a] = (st & RIR_BAD_ROOM) ? 0 : (int)n;
+  }
+  P.ncols = st ? 0 : (2 * P.n[0] + 1) * 2 * (2 * P.n[1] + 1) * 2;
+  return st;
+}
+
+template <bool ROOMS>
 __global__ __launch_bounds__(256) void rir_gather_kernel(const double* __restrict__ src, const double* __restrict__ rcv,
-                                                         double* __restrict__ h, RirParams P) {
+                                                         double* __restrict__ h, RirParams P, RirRooms R) {
   __shared__ double tab_c[RIR_MAX_TW], tab_s[RIR_MAX_TW];     // cos / sin(2 pi m / Tw), m = n - Tw/2 + 1, n in [0, Tw)
   __shared__ double s_frac[256], s_gain[256], s_sf[256], s_cw[256], s_sw[256];
   __shared__ int s_fd[256];
   __shared__ double part[RIR_WAVES][RIR_TILE];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int b = blockIdx.x / P.tiles, t0 = (blockIdx.x % P.tiles) * RIR_TILE;
+  if constexpr (ROOMS) {
+    const int st = rir_item_params(P, R, b);
+    if (t0 == 0 && tid == 0) R.status[b] = st;
+  }
   const int Tw = P.Tw, half = Tw / 2;
   for (int n = tid; n < Tw; n += 256) {
     const double m = (double)(n - half + 1);
@@ -228,32 +276,16 @@ __global__ __launch_bounds__(256) void rir_highpass_kernel(double* __restrict__ 
 
 using namespace alvq;
 
-extern "C" int alvq_rir_f64(const double* src, const double* rcv, double* h, int B, int nsample, double Lx, double Ly, double Lz,
-                            const double* beta6_host, double c, double fs, int order, int hp_filter, void* stream) {
-  const char* who = "alvq_rir_f64";
-  ALVQ_REQUIRE(src && rcv && h && beta6_host, ALVQ_EINVAL, "%s: null pointer", who);
+// The arguments both entry points share, checked before any launch, into P (everything but L, beta, n and ncols).
+static int rir_shared_params(const char* who, const double* src, const double* rcv, double* h, int B, int nsample, double c,
+                             double fs, int order, int hp_filter, RirParams& P) {
+  ALVQ_REQUIRE(src && rcv && h, ALVQ_EINVAL, "%s: null pointer", who);
   ALVQ_REQUIRE(B > 0 && nsample > 0 && nsample <= (1 << 24), ALVQ_EINVAL, "%s: B=%d nsample=%d (need B > 0, 0 < nsample <= 2^24)",
                who, B, nsample);
   ALVQ_REQUIRE(std::isfinite(c) && c > 0.0 && std::isfinite(fs) && fs > 0.0, ALVQ_EINVAL, "%s: c=%g fs=%g must be > 0", who, c, fs);
-  ALVQ_REQUIRE(std::isfinite(Lx) && std::isfinite(Ly) && std::isfinite(Lz) && Lx > 0.0 && Ly > 0.0 && Lz > 0.0, ALVQ_EINVAL,
-               "%s: room %g x %g x %g must be > 0", who, Lx, Ly, Lz);
   ALVQ_REQUIRE(order >= -1, ALVQ_EINVAL, "%s: order=%d (need >= -1)", who, order);
   ALVQ_REQUIRE(hp_filter == 0 || hp_filter == 1, ALVQ_EINVAL, "%s: hp_filter=%d (need 0 or 1)", who, hp_filter);
-  RirParams P;
-  for (int a = 0; a < 6; ++a) {
-    ALVQ_REQUIRE(std::isfinite(beta6_host[a]) && fabs(beta6_host[a]) <= 1.0, ALVQ_EINVAL, "%s: beta[%d]=%g (need |beta| <= 1)",
-                 who, a, beta6_host[a]);
-    P.beta[a] = beta6_host[a];
-  }
   P.cTs = c / fs;
-  const double Ls[3] = {Lx / P.cTs, Ly / P.cTs, Lz / P.cTs};
-  for (int a = 0; a < 3; ++a) {
-    P.L[a] = Ls[a];
-    const double n = ceil((double)nsample / (2.0 * Ls[a]));   // the generator's image range, this exact float64 expression
-    ALVQ_REQUIRE(n <= 4096.0, ALVQ_EINVAL, "%s: nsample=%d spans %g rooms along axis %d (limit 4096)", who, nsample, n, a);
-    P.n[a] = (int)n;
-  }
-  P.ncols = (2 * P.n[0] + 1) * 2 * (2 * P.n[1] + 1) * 2;
   P.Tw = 2 * (int)floor(0.004 * fs + 0.5);
   ALVQ_REQUIRE(P.Tw >= 2 && P.Tw <= RIR_MAX_TW, ALVQ_EINVAL, "%s: fs=%g gives a %d-tap window (need 2..%d)", who, fs, P.Tw,
                RIR_MAX_TW);
@@ -261,8 +293,46 @@ extern "C" int alvq_rir_f64(const double* src, const double* rcv, double* h, int
   P.order = order;
   P.tiles = (nsample + RIR_TILE - 1) / RIR_TILE;
   ALVQ_REQUIRE((long)B * P.tiles < (1L << 31), ALVQ_EINVAL, "%s: B=%d x %d tiles too many workgroups", who, B, P.tiles);
+  return ALVQ_OK;
+}
+
+extern "C" int alvq_rir_f64(const double* src, const double* rcv, double* h, int B, int nsample, double Lx, double Ly, double Lz,
+                            const double* beta6_host, double c, double fs, int order, int hp_filter, void* stream) {
+  const char* who = "alvq_rir_f64";
+  ALVQ_REQUIRE(beta6_host, ALVQ_EINVAL, "%s: null pointer", who);
+  RirParams P;
+  const int rc = rir_shared_params(who, src, rcv, h, B, nsample, c, fs, order, hp_filter, P);
+  if (rc != ALVQ_OK) return rc;
+  ALVQ_REQUIRE(std::isfinite(Lx) && std::isfinite(Ly) && std::isfinite(Lz) && Lx > 0.0 && Ly > 0.0 && Lz > 0.0, ALVQ_EINVAL,
+               "%s: room %g x %g x %g must be > 0", who, Lx, Ly, Lz);
+  for (int a = 0; a < 6; ++a) {
+    ALVQ_REQUIRE(std::isfinite(beta6_host[a]) && fabs(beta6_host[a]) <= 1.0, ALVQ_EINVAL, "%s: beta[%d]=%g (need |beta| <= 1)",
+                 who, a, beta6_host[a]);
+    P.beta[a] = beta6_host[a];
+  }
+  const double Ls[3] = {Lx / P.cTs, Ly / P.cTs, Lz / P.cTs};
+  for (int a = 0; a < 3; ++a) {
+    P.L[a] = Ls[a];
+    const double n = rir_image_range(nsample, Ls[a]);
+    ALVQ_REQUIRE(n <= RIR_MAX_N, ALVQ_EINVAL, "%s: nsample=%d spans %g rooms along axis %d (limit 4096)", who, nsample, n, a);
+    P.n[a] = (int)n;
+  }
+  P.ncols = (2 * P.n[0] + 1) * 2 * (2 * P.n[1] + 1) * 2;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(rir_gather_kernel, dim3(B * P.tiles), dim3(256), 0, s, src, rcv, h, P);
+  hipLaunchKernelGGL(rir_gather_kernel<false>, dim3(B * P.tiles), dim3(256), 0, s, src, rcv, h, P, RirRooms{nullptr, nullptr, nullptr});
+  if (hp_filter) hipLaunchKernelGGL(rir_highpass_kernel, dim3(B), dim3(256), 0, s, h, nsample, fs);
+  return check_launch(who);
+}
+
+extern "C" int alvq_rir_rooms_f64(const double* src, const double* rcv, const double* room, const double* beta, double* h,
+                                  int* status, int B, int nsample, double c, double fs, int order, int hp_filter, void* stream) {
+  const char* who = "alvq_rir_rooms_f64";
+  ALVQ_REQUIRE(room && beta && status, ALVQ_EINVAL, "%s: null pointer", who);
+  RirParams P;
+  const int rc = rir_shared_params(who, src, rcv, h, B, nsample, c, fs, order, hp_filter, P);
+  if (rc != ALVQ_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(rir_gather_kernel<true>, dim3(B * P.tiles), dim3(256), 0, s, src, rcv, h, P, RirRooms{room, beta, status});
   if (hp_filter) hipLaunchKernelGGL(rir_highpass_kernel, dim3(B), dim3(256), 0, s, h, nsample, fs);
   return check_launch(who);
 }

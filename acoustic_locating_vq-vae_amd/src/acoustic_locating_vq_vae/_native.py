@@ -117,6 +117,7 @@ _SIGNATURES = {
     "alvq_griffin_lim_f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_rir_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p] + [ctypes.c_double] * 2
                      + [_i32] * 2 + [_c_void_p]),
+    "alvq_rir_rooms_f64": (_i32, [_c_void_p] * 6 + [_i32] * 2 + [ctypes.c_double] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -744,6 +745,23 @@ def rir(src, rcv, L, beta, c, fs, nsample, order=-1, hp_filter=True):
                               int(nsample), L[0], L[1], L[2], ctypes.cast(beta_c, _c_void_p), float(c), float(fs), int(order),
                               int(bool(hp_filter)), _stream()), "alvq_rir_f64")
     return h
+
+
+def rir_rooms(src, rcv, room, beta, c, fs, nsample, order=-1, hp_filter=True):
+    """Room impulse responses with a room and six reflection coefficients per item (alvq_rir_rooms_f64): src, rcv, room (B,3)
+    and beta (B,6) float64 on the GPU -> (h (B, nsample) float64, status (B,) int32).  status is the kernel's per-item flag
+    (0 = fine; 1 = some |beta| > 1; 2 = a bad room or an image range above 4096) and is not read here."""
+    B = src.shape[0] if src.dim() == 2 else -1
+    if src.dim() != 2 or src.shape[1] != 3 or rcv.shape != src.shape or room.shape != src.shape or tuple(beta.shape) != (B, 6):
+        raise RuntimeError("rir_rooms: src, rcv, room must be (B, 3) and beta (B, 6) (got %s, %s, %s, %s)"
+                           % (tuple(src.shape), tuple(rcv.shape), tuple(room.shape), tuple(beta.shape)))
+    h = torch.empty((B, int(nsample)), device=src.device, dtype=torch.float64)
+    status = torch.empty((B,), device=src.device, dtype=torch.int32)
+    _check(lib().alvq_rir_rooms_f64(_ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"),
+                                    _ptr(room, torch.float64, "room"), _ptr(beta, torch.float64, "beta"), _ptr(h, torch.float64),
+                                    _ptr(status, torch.int32, "status"), B, int(nsample), float(c), float(fs), int(order),
+                                    int(bool(hp_filter)), _stream()), "alvq_rir_rooms_f64")
+    return h, status
 
 
 # ----------------------------------------------------------------------------------------------- t-SNE

@@ -23,10 +23,18 @@ made on the device too (image-source method, csrc/rir.hip), and with it the whol
     samples = generate_samples(wave)                          # theta ~ U(-pi, pi) -> source -> RIR -> echoed -> 6-tuple
     write_specs_dataset("spec_data/train", samples, DATASET_CONFIG)
 
+For data that spans rooms, ``SceneConfig`` / ``sample_scenes`` draw a room, T60, receiver and direction per item, and
+``scene_impulse_responses`` makes all their responses in one launch (each row bitwise its one-room response);
+``rir_dataset_generator.scene_loader.SceneLoader`` builds training batches from them with no files:
+
+    scenes = sample_scenes(64, SceneConfig(), generator)      # rooms 3-8 m, T60 0.25-0.8 s, receivers, theta
+    samples = generate_samples(wave, scenes=scenes)           # the same 6-tuple, a room per item
+
 Parity with ``rir_generator`` itself is unpinned (the package is absent and the reference holds no fixture); the RIR is
 pinned by the closed-form direct path, reciprocity, scipy's lfilter for the high-pass and a float64 restatement.
 Any other (Nh,) or (B, Nh) float64 response can still be passed to ``specs_from_waveform``.
 """
+import collections
 import math
 import os
 
@@ -116,10 +124,16 @@ def waveform_from_reconstruction(recon, raw_power, **gl_kwargs):
     return griffin_lim(power.contiguous(), power=2.0, **gl_kwargs)
 
 
-def _sabine_beta(L, c, reverberation_time):
+def _sabine_alpha(L, c, reverberation_time):
+    """Sabine's absorption 24 V ln10 / (c S T60), in this one expression order for host floats and device tensors alike
+    (L: three sides, floats or (B,) tensors), so that a room's beta has the same bits on either side."""
     V = L[0] * L[1] * L[2]
     S = 2.0 * (L[0] * L[2] + L[1] * L[2] + L[0] * L[1])
-    alpha = 24.0 * V * math.log(10.0) / (c * S * reverberation_time)
+    return 24.0 * V * math.log(10.0) / (c * S * reverberation_time)
+
+
+def _sabine_beta(L, c, reverberation_time):
+    alpha = _sabine_alpha(L, c, reverberation_time)
     if alpha > 1:
         raise ValueError("the reflection coefficients cannot be calculated for room %s and reverberation time %g (alpha = %g > 1);"
                          " give beta or change the room" % (list(L), reverberation_time, alpha))
@@ -224,6 +238,12 @@ def rir_generate(c, fs, r, s, L, beta=None, reverberation_time=None, nsample=Non
     return h.t()
 
 
+def _ring_sources(theta, rcv, room, R, z):
+    """min(rcv + (R cos theta, R sin theta, z), room): theta (B,) float64, rcv and room (1, 3) or (B, 3) float64."""
+    ring = torch.stack((R * torch.cos(theta), R * torch.sin(theta), torch.full_like(theta, float(z))), dim=1)
+    return torch.minimum(rcv + ring, room)
+
+
 def source_positions(theta, receiver, room, R, z):
     """SpecsDataset.get_source_coordinates on the device: theta (B,) float64 -> (B, 3) float64 sources
     min(receiver + (R cos theta, R sin theta, z), room) (genereate_dataset.py:18-20).  A source on the receiver raises."""
@@ -232,24 +252,30 @@ def source_positions(theta, receiver, room, R, z):
     _check_device(theta, "source_positions")
     theta = theta.reshape(-1).to(torch.float64)
     rcv = _positions(receiver, "receiver", theta.device)
-    ring = torch.stack((R * torch.cos(theta), R * torch.sin(theta), torch.full_like(theta, float(z))), dim=1)
-    room_t = _positions(room, "room", theta.device)
-    src = torch.minimum(rcv + ring, room_t)
+    src = _ring_sources(theta, rcv, _positions(room, "room", theta.device), R, z)
     if bool((src == rcv).all(dim=1).any()):
         raise ValueError("source_positions: a source coincides with the receiver (distance 0, infinite gain)")
     return src
 
 
-def generate_samples(wave, theta=None, generator=None, config=DATASET_CONFIG, c=SOUND_SPEED):
+def generate_samples(wave, theta=None, generator=None, config=DATASET_CONFIG, c=SOUND_SPEED, scenes=None):
     """The dataset generator on the device (genereate_dataset.py:13-51, batched): wave (B, S) float32 clean speech on the GPU
     -> (speech_spec (B,F,T) fp32, rir_spec fp64, echoed_spec fp64, sample_rate int, theta (B,) fp64, wiener_est (B,F) fp64).
     theta: source directions (B,); None draws U(-pi, pi) in float64 on the device (from ``generator`` if given).  config:
     the generator's constants (``DATASET_CONFIG`` keys): source on the ring of radius R at height Z_LOC_SOURCE above the
-    receiver, clipped to the room; RIR from reverberation_time with n_sample samples; STFT with NFFT / HOP_LENGTH."""
+    receiver, clipped to the room; RIR from reverberation_time with n_sample samples; STFT with NFFT / HOP_LENGTH.
+    scenes: a ``Scenes`` of B items (``sample_scenes``) instead of theta: each item's room, receiver, source and beta come
+    from it (config then gives fs, n_sample, NFFT and HOP_LENGTH only) and the returned theta is ``scenes.theta``."""
     if wave.dim() != 2 or wave.dtype != torch.float32:
         raise ValueError("generate_samples: wave must be float32 (B, S), got %s %s" % (wave.dtype, tuple(wave.shape)))
+    if scenes is not None and theta is not None:
+        raise ValueError("generate_samples: give theta or scenes, not both")
     _check_device(wave, "generate_samples")
     B = wave.shape[0]
+    if scenes is not None:
+        if scenes.theta.shape[0] != B:
+            raise ValueError("generate_samples: %d scenes for %d waveforms" % (scenes.theta.shape[0], B))
+        return _samples_from_scenes(wave, scenes, config, c, check=not torch.cuda.is_current_stream_capturing())
     if theta is None:
         theta = torch.rand(B, dtype=torch.float64, device=wave.device, generator=generator) * (2.0 * math.pi) - math.pi
     else:
@@ -262,6 +288,211 @@ def generate_samples(wave, theta=None, generator=None, config=DATASET_CONFIG, c=
                                reverberation_time=config["reverberation_time"], nsample=config["n_sample"], c=c, fs=fs)
     speech, rir, echoed, wiener = specs_from_waveform(wave, h, n_fft=int(config["NFFT"]), hop=int(config["HOP_LENGTH"]))
     return speech, rir, echoed, fs, theta, wiener
+
+
+def _samples_from_scenes(wave, scenes, config, c, check):
+    fs = int(config["fs"])
+    h = _scene_rirs(scenes.source, scenes.receiver, scenes.room, scenes.beta, None, int(config["n_sample"]), c, fs, -1, True,
+                    check, "generate_samples")
+    speech, rir, echoed, wiener = specs_from_waveform(wave, h, n_fft=int(config["NFFT"]), hop=int(config["HOP_LENGTH"]))
+    return speech, rir, echoed, fs, scenes.theta, wiener
+
+
+# ------------------------------------------------------------------------------------------------ scenes: a room per item
+def _sabine_beta_device(room, c, reverberation_time):
+    """Per item on the device: room (B, 3), reverberation_time (B,) float64 -> (alpha (B,), beta (B, 6)), all six beta
+    sqrt(1 - alpha) with ``_sabine_beta``'s arithmetic; NaN where alpha > 1 (the kernel flags those items)."""
+    alpha = _sabine_alpha((room[:, 0], room[:, 1], room[:, 2]), c, reverberation_time)
+    return alpha, torch.sqrt(1.0 - alpha).unsqueeze(1).expand(-1, 6).contiguous()
+
+
+def _scene_rirs(src, rcv, room, beta, alpha, nsample, c, fs, order, hp_filter, check, who):
+    h, status = N.rir_rooms(src, rcv, room, beta, c, fs, nsample, order, hp_filter)
+    if check:
+        flags = [(src == rcv).all(dim=1).any(), (status != 0).any()]
+        if alpha is not None:
+            flags.append((alpha > 1).any())
+        coincide, flagged, *over = torch.stack(flags).tolist()          # the one host sync
+        if coincide:
+            raise ValueError("%s: a source coincides with its receiver (distance 0, infinite gain)" % who)
+        if any(over):
+            raise ValueError("%s: the reflection coefficients cannot be calculated for some room and reverberation time "
+                             "(alpha > 1); give beta or change the room" % who)
+        if flagged:
+            items = torch.nonzero(status).reshape(-1).tolist()
+            raise ValueError("%s: items %s have |beta| > 1, a room side that is not a positive length, or more than 4096 "
+                             "images along an axis (status %s)" % (who, items, status[items].tolist()))
+    return h
+
+
+def scene_impulse_responses(src, receiver, room, reverberation_time=None, beta=None, nsample=None, c=SOUND_SPEED, fs=16000,
+                            order=-1, dim=3, hp_filter=True):
+    """Room impulse responses with a room per item, (B, nsample) float64 on the GPU, in one launch (alvq_rir_rooms_f64).
+
+    src (B, 3), room (B, 3) and exactly one of reverberation_time (B,) and beta (B, 6): float64 tensors on the GPU; receiver
+    (3,) or (B, 3).  From reverberation_time, Sabine's beta is computed on the device with ``rir_generate``'s expression, so
+    row b is bitwise ``room_impulse_responses(src[b:b+1], receiver[b], room[b], ...)``.  nsample is required (it is shared).
+    Outside a graph capture, one host sync checks that no source is on its receiver, that alpha <= 1 and the kernel's per-item
+    flag (|beta| <= 1, at most 4096 images along an axis) and raises ValueError otherwise; inside a capture there is no check.
+    order, dim and hp_filter as in ``rir_generate``."""
+    who = "scene_impulse_responses"
+    if (beta is None) == (reverberation_time is None):
+        raise ValueError("%s: give exactly one of beta and reverberation_time" % who)
+    if nsample is None or int(nsample) <= 0:
+        raise ValueError("%s: nsample must be given and > 0, got %r" % (who, nsample))
+    if not (c > 0 and fs > 0):
+        raise ValueError("%s: c and fs must be > 0, got c=%r fs=%r" % (who, c, fs))
+    if dim not in (2, 3):
+        raise ValueError("%s: dim must be 2 or 3, got %r" % (who, dim))
+    for name, t in (("src", src), ("room", room)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float64:
+            raise ValueError("%s: %s must be a float64 (B, 3) tensor" % (who, name))
+    B = src.shape[0]
+    if room.shape[0] != B:
+        raise ValueError("%s: %d rooms for %d sources" % (who, room.shape[0], B))
+    if reverberation_time is not None:
+        t60 = reverberation_time
+        if not isinstance(t60, torch.Tensor) or t60.dtype != torch.float64 or t60.reshape(-1).shape[0] != B:
+            raise ValueError("%s: reverberation_time must be a float64 (B,) tensor" % who)
+    else:
+        if not isinstance(beta, torch.Tensor) or beta.dtype != torch.float64 or tuple(beta.shape) != (B, 6):
+            raise ValueError("%s: beta must be a float64 (B, 6) tensor" % who)
+    _check_device(src, who)
+    _check_device(room, who)
+    rcv = _positions(receiver, "receiver", src.device)
+    if rcv.shape[0] == 1:
+        rcv = rcv.expand(B, 3)
+    elif rcv.shape[0] != B:
+        raise ValueError("%s: %d receivers for %d sources" % (who, rcv.shape[0], B))
+    alpha = None
+    if reverberation_time is not None:
+        _check_device(reverberation_time, who)
+        alpha, beta = _sabine_beta_device(room, float(c), reverberation_time.reshape(-1))
+    else:
+        _check_device(beta, who)
+    if dim == 2:
+        beta = beta.clone()
+        beta[:, 4:] = 0.0
+    return _scene_rirs(src.contiguous(), rcv.contiguous(), room.contiguous(), beta.contiguous(), alpha, int(nsample), c, fs,
+                       order, hp_filter, not torch.cuda.is_current_stream_capturing(), who)
+
+
+Scenes = collections.namedtuple("Scenes", "room receiver source reverberation_time beta theta")
+Scenes.__doc__ = """A batch of scenes, float64 tensors on the device: room (B, 3) m, receiver (B, 3), source (B, 3), reverberation_time
+(B,) s, beta (B, 6) (Sabine's, from room and reverberation_time) and theta (B,), the source's direction seen from the receiver."""
+
+
+def _range(v, name):
+    lo, hi = (v, v) if np.ndim(v) == 0 else tuple(v)
+    lo, hi = float(lo), float(hi)
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError("SceneConfig: %s must be a positive length or a range 0 < lo <= hi, got %r" % (name, v))
+    return lo, hi
+
+
+class SceneConfig:
+    """What ``sample_scenes`` draws from, checked when it is made (no device work): every draw is then a valid scene.
+
+    room_dimensions: three per-axis [lo, hi] ranges in m (a number is a point); reverberation_time: [lo, hi] s.
+    receiver_position: None places the receiver uniformly in the room shrunk by ``margin`` horizontally and by ``margin_z``
+    below and ``Z_LOC_SOURCE + margin_z`` above; three numbers fix it.  The source follows ``source_positions``'s rule
+    min(receiver + (R cos theta, R sin theta, Z_LOC_SOURCE), room), theta ~ U(-pi, pi); the checks make the clip inactive,
+    so every source lies strictly inside its room and theta is its true direction (margin > R is required).  fs, n_sample,
+    NFFT and HOP_LENGTH are the shared signal constants, c the sound speed.  Rejected: a room too small for the margins or
+    the fixed receiver, a reverberation_time lower bound below Sabine's minimum for the largest room (alpha > 1), and a
+    smallest room that needs more than 4096 images along an axis."""
+
+    def __init__(self, room_dimensions=((3.0, 8.0), (3.0, 8.0), (3.0, 8.0)), reverberation_time=(0.25, 0.8),
+                 receiver_position=None, margin=1.25, margin_z=0.5, R=1.0, Z_LOC_SOURCE=1.0, fs=16000, n_sample=6400,
+                 NFFT=N_FFT, HOP_LENGTH=HOP, c=SOUND_SPEED):
+        if len(room_dimensions) != 3:
+            raise ValueError("SceneConfig: room_dimensions needs three ranges, got %r" % (room_dimensions,))
+        self.room = tuple(_range(v, "room_dimensions[%d]" % a) for a, v in enumerate(room_dimensions))
+        self.reverberation_time = _range(reverberation_time, "reverberation_time")
+        self.R, self.z, self.c = float(R), float(Z_LOC_SOURCE), float(c)
+        self.fs, self.n_sample, self.NFFT, self.HOP_LENGTH = int(fs), int(n_sample), int(NFFT), int(HOP_LENGTH)
+        if not (self.R > 0 and math.isfinite(self.R) and self.z >= 0 and math.isfinite(self.z)):
+            raise ValueError("SceneConfig: need R > 0 and Z_LOC_SOURCE >= 0, got %r and %r" % (R, Z_LOC_SOURCE))
+        if not (self.c > 0 and self.fs > 0 and self.n_sample > 0):
+            raise ValueError("SceneConfig: c, fs and n_sample must be > 0")
+        lo = [r[0] for r in self.room]
+        if receiver_position is None:
+            self.receiver, self.margin, self.margin_z = None, float(margin), float(margin_z)
+            if not (self.margin > self.R and self.margin_z > 0):
+                raise ValueError("SceneConfig: need margin > R (%g) and margin_z > 0, got %r and %r" % (self.R, margin, margin_z))
+            if lo[0] < 2 * self.margin or lo[1] < 2 * self.margin or lo[2] < self.z + 2 * self.margin_z:
+                raise ValueError("SceneConfig: the smallest room %s leaves no place for the receiver (horizontal margin %g, "
+                                 "height margin %g + Z_LOC_SOURCE %g)" % (lo, self.margin, self.margin_z, self.z))
+        else:
+            self.receiver = tuple(float(v) for v in receiver_position)
+            self.margin = self.margin_z = None
+            x, y, zr = self.receiver
+            if len(self.receiver) != 3 or not (self.R < x and x + self.R < lo[0] and self.R < y and y + self.R < lo[1]
+                                               and 0 < zr and zr + self.z < lo[2]):
+                raise ValueError("SceneConfig: receiver %r with R %g and Z_LOC_SOURCE %g puts a source outside the smallest "
+                                 "room %s" % (receiver_position, self.R, self.z, lo))
+        hi = [r[1] for r in self.room]
+        alpha = _sabine_alpha(hi, self.c, self.reverberation_time[0])
+        if not alpha <= 1.0 - 1e-9:         # alpha grows with every side: the largest room at the lowest T60 is the worst
+            raise ValueError("SceneConfig: reverberation_time %g is below Sabine's minimum for the largest room %s (alpha = %g)"
+                             % (self.reverberation_time[0], hi, alpha))
+        cTs = self.c / self.fs
+        if max(math.ceil(self.n_sample / (2.0 * (v / cTs))) for v in lo) > 4096:
+            raise ValueError("SceneConfig: n_sample %d needs more than 4096 images along an axis of the room %s"
+                             % (self.n_sample, lo))
+
+    @classmethod
+    def from_dataset_config(cls, config=DATASET_CONFIG, c=SOUND_SPEED):
+        """The degenerate config: every range the point ``config`` holds (by default the generator's one room)."""
+        return cls(room_dimensions=[float(v) for v in config["room_dimensions"]],
+                   reverberation_time=float(config["reverberation_time"]), receiver_position=config["receiver_position"],
+                   R=config["R"], Z_LOC_SOURCE=config["Z_LOC_SOURCE"], fs=config["fs"], n_sample=config["n_sample"],
+                   NFFT=config["NFFT"], HOP_LENGTH=config["HOP_LENGTH"], c=c)
+
+    def _tensors(self, device):
+        """The ranges as float64 tensors on device, made once per device (so that a draw copies nothing from the host)."""
+        cache = self.__dict__.setdefault("_cache", {})
+        if device not in cache:
+            f64 = dict(dtype=torch.float64, device=device)
+            lo = torch.tensor([r[0] for r in self.room], **f64)
+            t = {"lo": lo, "span": torch.tensor([r[1] for r in self.room], **f64) - lo}
+            if self.receiver is None:
+                t["margin"] = torch.tensor([self.margin, self.margin, self.margin_z], **f64)
+                t["reserve"] = torch.tensor([2.0 * self.margin, 2.0 * self.margin, 2.0 * self.margin_z + self.z], **f64)
+            else:
+                t["receiver"] = torch.tensor(self.receiver, **f64)[None]
+            cache[device] = t
+        return cache[device]
+
+    def signal_config(self):
+        """The shared constants under ``DATASET_CONFIG``'s key names, as ``generate_samples`` reads them."""
+        return {"fs": self.fs, "n_sample": self.n_sample, "NFFT": self.NFFT, "HOP_LENGTH": self.HOP_LENGTH}
+
+
+def sample_scenes(B, config, generator=None, device=None):
+    """B scenes drawn from a ``SceneConfig``, as a ``Scenes``; no host sync.  One (B, 8) float64 uniform draw from
+    ``generator`` (whose device is used; else ``device``, default cuda; plain tensor arithmetic, so a CPU generator works
+    too, for inspection): room sides lo + u (hi - lo), T60 likewise, the
+    receiver (unless fixed) and theta = u * 2 pi - pi, ``generate_samples``'s expression."""
+    if not isinstance(config, SceneConfig):
+        raise ValueError("sample_scenes: config must be a SceneConfig")
+    B = int(B)
+    if B <= 0:
+        raise ValueError("sample_scenes: B must be > 0, got %r" % (B,))
+    device = torch.device(generator.device if generator is not None else (device or "cuda"))
+    t = config._tensors(device)
+    u = torch.rand((B, 8), generator=generator, dtype=torch.float64, device=device)
+    room = t["lo"] + u[:, 0:3] * t["span"]
+    t_lo, t_hi = config.reverberation_time
+    t60 = t_lo + u[:, 3] * (t_hi - t_lo)
+    if config.receiver is None:
+        rcv = t["margin"] + u[:, 4:7] * (room - t["reserve"])
+    else:
+        rcv = t["receiver"].expand(B, 3)
+    theta = u[:, 7] * (2.0 * math.pi) - math.pi
+    src = _ring_sources(theta, rcv, room, config.R, config.z)
+    _, beta = _sabine_beta_device(room, config.c, t60)
+    return Scenes(room, rcv.contiguous(), src, t60, beta, theta)
 
 
 def write_specs_dataset(dest, samples, config=DATASET_CONFIG, start=0):

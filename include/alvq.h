@@ -267,6 +267,13 @@ int alvq_griffin_lim_f64(const double* mag, const double* angles, double* wave, 
  * ---------------------------------------------------------------------------------------------- */
 int alvq_rir_f64(const double* src, const double* rcv, double* h, int B, int nsample, double Lx, double Ly, double Lz,
                  const double* beta6_host, double c, double fs, int order, int hp_filter, void* stream);
+/* The same with a room and six reflection coefficients per item: room device (B,3) (m), beta device (B,6).  Each item's image
+ * ranges are computed on the device with the expression above, so row b is bitwise alvq_rir_f64 called with room[b] and
+ * beta[b] alone.  status: device (B,) int, written for every item: 0, or bit 1 = some |beta[b]| > 1 (or NaN), bit 2 = a room
+ * side not a positive finite length, or an image range above 4096; such an item's response is left zero (its taps are not
+ * summed).  The caller reads status when it can sync.  One or two launches, no host sync, no workspace. */
+int alvq_rir_rooms_f64(const double* src, const double* rcv, const double* room, const double* beta, double* h, int* status, int B,
+                       int nsample, double c, double fs, int order, int hp_filter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
