@@ -123,6 +123,15 @@ _SIGNATURES = {
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
     "alvq_tsne_descend_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_descend_f64": (_i32, [_c_void_p] * 7 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p]),
+    "alvq_kmeans_update_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "alvq_kmeans_update_f32": (_i32, [_c_void_p] * 9 + [_i64, _i32, _i32, ctypes.c_double, _c_void_p]),
+    "alvq_kmeans_inertia_workspace_bytes": (_i64, [_i64]),
+    "alvq_kmeans_inertia_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p]),
+    "alvq_kmeans_col_stats_workspace_bytes": (_i64, [_i64, _i32]),
+    "alvq_kmeans_col_stats_f32": (_i32, [_c_void_p] * 4 + [_i64, _i32, _c_void_p]),
+    "alvq_kmeans_add_rows_f32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _f32, _c_void_p]),
+    "alvq_kmeans_plusplus_workspace_bytes": (_i64, [_i64, _i32]),
+    "alvq_kmeans_plusplus_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _i32, _i64, _c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -1241,3 +1250,92 @@ def conv1d_wgrad_bf16_multi(pairs, KW, w_layout=W_OIK, dw_out=None, accumulate=F
     if deferred:
         _defer_descs(defer, ws_ptr, dw_out, None, None, n, x0.B, C, M, x0.L, KW, w_layout)
     return dw_out
+
+
+# ----------------------------------------------------------------------------------------------- k-means
+def _rows(x, name):
+    if x.dim() != 2:
+        raise RuntimeError("%s must be (N, D) (got %s)" % (name, tuple(x.shape)))
+    return x.shape
+
+
+def kmeans_update(x, labels, labels_old, centers_old, centers_new, counts, stats, flags, tol, workspace=None):
+    """One Lloyd update (alvq_kmeans_update_f32): centers_new (K, D) fp32, counts (K,) int32 (or None), stats (1,) fp64 and
+    flags (4,) int32 out.  Returns the workspace (reuse it for the next iteration)."""
+    N, D = _rows(x, "kmeans_update: x")
+    K = centers_old.shape[0]
+    if centers_old.shape != (K, D) or centers_new.shape != (K, D) or labels.shape != (N,):
+        raise RuntimeError("kmeans_update: centres must be (%d, %d) and labels (%d,)" % (K, D, N))
+    if labels_old is not None and labels_old.shape != (N,):
+        raise RuntimeError("kmeans_update: labels_old must be (%d,)" % N)
+    nbytes = lib().alvq_kmeans_update_workspace_bytes(N, K, D)
+    if nbytes < 0:
+        raise RuntimeError("kmeans_update: N=%d, K=%d, D=%d out of range" % (N, K, D))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+    i64 = torch.int64
+    _check(lib().alvq_kmeans_update_f32(_ptr(x, name="x"), _ptr(labels, i64, "labels"), _ptr(labels_old, i64, "labels_old"),
+                                        _ptr(centers_old, name="centers_old"), _ptr(centers_new, name="centers_new"),
+                                        _ptr(counts, torch.int32, "counts"), _ptr(stats, torch.float64, "stats"),
+                                        _ptr(flags, torch.int32, "flags"), _ptr(workspace, torch.uint8, "workspace"), N, K, D,
+                                        float(tol), _stream()), "alvq_kmeans_update_f32")
+    return workspace
+
+
+def kmeans_inertia(x, labels, centers):
+    """(1,) fp64 device tensor: sum_n |x_n - centers[labels_n]|^2 (alvq_kmeans_inertia_f32)."""
+    N, D = _rows(x, "kmeans_inertia: x")
+    K = centers.shape[0]
+    if centers.shape != (K, D) or labels.shape != (N,):
+        raise RuntimeError("kmeans_inertia: centres must be (K, %d) and labels (%d,)" % (D, N))
+    out = torch.empty((1,), device=x.device, dtype=torch.float64)
+    ws = torch.empty((lib().alvq_kmeans_inertia_workspace_bytes(N),), device=x.device, dtype=torch.uint8)
+    _check(lib().alvq_kmeans_inertia_f32(_ptr(x, name="x"), _ptr(labels, torch.int64, "labels"), _ptr(centers, name="centers"),
+                                         _ptr(out, torch.float64), _ptr(ws, torch.uint8), N, K, D, _stream()),
+           "alvq_kmeans_inertia_f32")
+    return out
+
+
+def kmeans_col_stats(x):
+    """(mean (D,) fp32, var_mean (1,) fp64) of the rows of x (alvq_kmeans_col_stats_f32)."""
+    N, D = _rows(x, "kmeans_col_stats: x")
+    nbytes = lib().alvq_kmeans_col_stats_workspace_bytes(N, D)
+    if nbytes < 0:
+        raise RuntimeError("kmeans_col_stats: N=%d, D=%d out of range" % (N, D))
+    mean = torch.empty((D,), device=x.device, dtype=torch.float32)
+    var_mean = torch.empty((1,), device=x.device, dtype=torch.float64)
+    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+    _check(lib().alvq_kmeans_col_stats_f32(_ptr(x, name="x"), _ptr(mean), _ptr(var_mean, torch.float64), _ptr(ws, torch.uint8),
+                                           N, D, _stream()), "alvq_kmeans_col_stats_f32")
+    return mean, var_mean
+
+
+def kmeans_add_rows(x, v, alpha, out=None):
+    """out = x + alpha * v[None, :] (alvq_kmeans_add_rows_f32); out may be x."""
+    N, D = _rows(x, "kmeans_add_rows: x")
+    if v.shape != (D,):
+        raise RuntimeError("kmeans_add_rows: v must be (%d,)" % D)
+    out = torch.empty_like(x) if out is None else out
+    _check(lib().alvq_kmeans_add_rows_f32(_ptr(x, name="x"), _ptr(v, name="v"), _ptr(out, name="out"), N, D, float(alpha),
+                                          _stream()), "alvq_kmeans_add_rows_f32")
+    return out
+
+
+def kmeans_plusplus(x, K, first, uniforms):
+    """Greedy k-means++ seeding (alvq_kmeans_plusplus_f32) -> (centers (K, D) fp32, indices (K,) int64); uniforms (K-1, T)
+    fp64 on the device."""
+    N, D = _rows(x, "kmeans_plusplus: x")
+    T = uniforms.shape[1] if uniforms is not None and uniforms.dim() == 2 else 0
+    if K > 1 and (uniforms is None or uniforms.shape[0] != K - 1):
+        raise RuntimeError("kmeans_plusplus: uniforms must be (%d, T)" % (K - 1))
+    T = max(T, 1)
+    nbytes = lib().alvq_kmeans_plusplus_workspace_bytes(N, T)
+    if nbytes < 0:
+        raise RuntimeError("kmeans_plusplus: N=%d, T=%d out of range" % (N, T))
+    centers = torch.empty((K, D), device=x.device, dtype=torch.float32)
+    indices = torch.empty((K,), device=x.device, dtype=torch.int64)
+    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+    _check(lib().alvq_kmeans_plusplus_f32(_ptr(x, name="x"), _ptr(uniforms if K > 1 else None, torch.float64, "uniforms"),
+                                          _ptr(centers), indices.data_ptr(), _ptr(ws, torch.uint8), N, K, D, T, int(first),
+                                          _stream()), "alvq_kmeans_plusplus_f32")
+    return centers, indices

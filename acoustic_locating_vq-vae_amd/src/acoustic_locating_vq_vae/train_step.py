@@ -511,6 +511,42 @@ class Trainer:
         self._finish(early)
         return self._static_out
 
+    def init_codebook(self, raw_batches, wiener_batches=None, **kmeans_kwargs):
+        """Initialise the model's codebook by k-means (``ConvolutionalVQVAE.init_codebook``) on raw batches preprocessed
+        as ``step`` preprocesses them; returns the fitted ``KMeans`` (None on ranks other than 0).
+
+        ``raw_batches``: one raw batch or an iterable of them (``wiener_batches`` alongside for kind="rir").  The codebook
+        is written in place (the flat buffer's slice, so an already captured graph replays against it), and its slice of
+        the Adam moments is zeroed.  Nothing else caches the codebook: the quantiser recomputes its norms on every call and
+        no packed image of it exists.  Under data parallelism rank 0 fits on its own batches and broadcasts the codebook,
+        so every rank ends with the same one."""
+        if self.kind == "echoed":
+            raise NotImplementedError("init_codebook: the echoed model's frozen sub-codebooks are out of scope")
+        single = isinstance(raw_batches, torch.Tensor)
+        raws = [raw_batches] if single else list(raw_batches)
+        if wiener_batches is None:
+            wieners = [None] * len(raws)
+        else:
+            wieners = [wiener_batches] if isinstance(wiener_batches, torch.Tensor) else list(wiener_batches)
+        if self.kind == "rir" and (len(wieners) != len(raws) or any(w is None for w in wieners)):
+            raise ValueError("init_codebook: kind='rir' needs one Wiener batch per raw batch")
+        world, rank = 1, 0
+        if dist.is_available() and dist.is_initialized():
+            world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        weight = self.model._vq._embedding.weight
+        km = None
+        if rank == 0:
+            km = self.model.init_codebook([self.preprocess(r, w)[0] for r, w in zip(raws, wieners)], **kmeans_kwargs)
+        if world > 1:
+            dist.broadcast(weight.data, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0,
+                           group=self.group)
+        ids = {id(p): i for i, p in enumerate(self.buffers.params)}
+        if id(weight) in ids:
+            off = self.buffers.offsets[ids[id(weight)]]
+            self.opt.exp_avg[off:off + weight.numel()].zero_()
+            self.opt.exp_avg_sq[off:off + weight.numel()].zero_()
+        return km
+
     def evaluate(self, raw, wiener=None):
         """The loops' validation step (train_speech.py:57-59,76-86; train_rir.py:36-40,60-70): ``model.eval()`` -- so no jitter and
         no draw from ``np.random`` -- the same preprocessing, forward and losses, no backward, no update; the model's mode is

@@ -66,6 +66,32 @@ class ConvolutionalVQVAE(nn.Module):
         """(loss, quantized, perplexity, indices[N] int64): the sparse form of get_latent_representation."""
         return self._vq.quantize(self._latent(x))
 
+    @torch.no_grad()
+    def init_codebook(self, x, **kmeans_kwargs):
+        """Initialise the quantiser's codebook by k-means on the model's own pre-VQ outputs and return the fitted
+        ``acoustic_locating_vq_vae.kmeans.KMeans``.
+
+        ``x``: one input batch, shaped as ``forward`` takes it, or an iterable of such batches.  The latent path runs as
+        ``forward`` runs it (current compute mode, ``encoder_average_pooling`` honoured) under no_grad; its rows are taken
+        exactly as the quantiser takes them (``view(-1, D)`` of the contiguous buffer, no permute), and
+        ``KMeans(n_clusters=num_embeddings, **kmeans_kwargs)`` is fitted on them.  The centres are copied in place into
+        ``_vq._embedding.weight`` (same storage).  ``_train_vq`` is left as it is."""
+        from ..kmeans import KMeans
+        batches = [x] if isinstance(x, torch.Tensor) else list(x)
+        if not batches:
+            raise ValueError("init_codebook: no input batch")
+        D = self._vq.get_embedding_dim()
+        rows = []
+        for xb in batches:
+            z = self._latent(xb)
+            if self.encoder_average_pooling:
+                z = _ops.MeanPoolFn.apply(z)
+            rows.append(_ops.dense(z).view(-1, D))
+        flat = rows[0] if len(rows) == 1 else torch.cat(rows)
+        km = KMeans(n_clusters=self._vq._num_embeddings, **kmeans_kwargs).fit(flat)
+        self._vq._embedding.weight.data.copy_(km.cluster_centers_)
+        return km
+
     def train_on_data(self, optimizer: optim, dataloader: DataLoader, num_training_updates, data_variance):
         """The alternative loop the reference keeps on the class (convolutional_vq_vae.py:58-91): a fresh loader
         iterator per update, MSE scaled by 1/data_variance, a crop of one trailing frame when shapes differ, progress

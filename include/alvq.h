@@ -305,6 +305,48 @@ int64_t alvq_tsne_descend_workspace_bytes(int N);
 int alvq_tsne_descend_f64(const float* P, double* Y, double* update, double* gains, double* grad, double* stats, void* workspace,
                           int N, int n_iter, double exaggeration, double momentum, double learning_rate, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * k-means (sklearn.cluster.KMeans(algorithm="lloyd") semantics; the contract in full: the docstring of
+ * acoustic_locating_vq_vae/kmeans.py).  x (N, D) fp32 rows, centres (K, D) fp32; N < 2^30, K <= 16384, D <= 512.  The
+ * assignment step is alvq_vq_argmin_f32.  Fixed-order fp64 sums, no floating-point atomics: bitwise reproducible.
+ *
+ * One Lloyd update from labels (int64, in [0, K)) assigned with centers_old: the rows sorted by label stably (counts,
+ * exclusive scan, stable scatter), each cluster's rows summed in fp64 in row order (segments of 128 rows, in order),
+ * empty clusters relocated (sklearn's _relocate_empty_clusters_dense: distances to the OLD centre of each row's label; the
+ * farthest rows, distance descending and ties to the lower row, go to the empty clusters in ascending order; nothing
+ * moves when the largest distance is 0), centers_new = fl32(sum * (1 / count)) (an empty cluster keeps its sum).
+ * labels_old may be NULL (no previous labels).  counts (K) int32 out, may be NULL.  stats[0] = center_shift_tot =
+ * sum_k |c_new - c_old|^2.  flags[0] = 1 labels unchanged since labels_old, 2 center_shift_tot <= tol, 0 otherwise;
+ * flags[1] labels changed, flags[2] empty clusters before relocation, flags[3] clusters relocated.  9 launches, no host
+ * sync.  workspace: alvq_kmeans_update_workspace_bytes(N, K, D) bytes (-1 out of range). */
+int64_t alvq_kmeans_update_workspace_bytes(int64_t N, int K, int D);
+int alvq_kmeans_update_f32(const float* x, const int64_t* labels, const int64_t* labels_old, const float* centers_old,
+                           float* centers_new, int32_t* counts, double* stats, int32_t* flags, void* workspace,
+                           int64_t N, int K, int D, double tol, void* stream);
+
+/* inertia[0] = sum_n |x_n - c_{labels_n}|^2 in fp64.  workspace: alvq_kmeans_inertia_workspace_bytes(N) bytes. */
+int64_t alvq_kmeans_inertia_workspace_bytes(int64_t N);
+int alvq_kmeans_inertia_f32(const float* x, const int64_t* labels, const float* centers, double* inertia, void* workspace,
+                            int64_t N, int K, int D, void* stream);
+
+/* Column statistics: mean (D) = fl32 of the fp64 column means; var_mean[0] = mean over d of the fp64 column variances
+ * (sum (x - mean)^2 / N).  workspace: alvq_kmeans_col_stats_workspace_bytes(N, D) bytes. */
+int64_t alvq_kmeans_col_stats_workspace_bytes(int64_t N, int D);
+int alvq_kmeans_col_stats_f32(const float* x, float* mean, double* var_mean, void* workspace, int64_t N, int D, void* stream);
+
+/* y[n][d] = x[n][d] + alpha * v[d] (fp32; y may alias x). */
+int alvq_kmeans_add_rows_f32(const float* x, const float* v, float* y, int64_t N, int D, float alpha, void* stream);
+
+/* Greedy k-means++ (sklearn's _kmeans_plusplus): centre 0 = x[first]; closest_dist_sq in fp64; per round c >= 1, T
+ * candidates r_t = uniforms[c-1][t] * current_pot found in the blocked fp64 inclusive cumsum of closest_dist_sq (first
+ * entry >= r_t, clipped to N - 1), their fp64 distances to every row, min with closest_dist_sq, the candidate of least
+ * potential (lowest t on ties) kept.  uniforms (K-1, T) fp64 in [0, 1) (may be NULL for K = 1); centers (K, D) and
+ * indices (K) int64 out.  3 launches a round, no host sync.  1 <= T <= 16, K <= N.
+ * workspace: alvq_kmeans_plusplus_workspace_bytes(N, T) bytes. */
+int64_t alvq_kmeans_plusplus_workspace_bytes(int64_t N, int T);
+int alvq_kmeans_plusplus_f32(const float* x, const double* uniforms, float* centers, int64_t* indices, void* workspace,
+                             int64_t N, int K, int D, int T, int64_t first, void* stream);
+
 /* ================================================================================================
  * bf16 throughput path (BASELINE configs[1]: "batch=64 bf16").  Storage bf16, accumulation fp32.
  *
