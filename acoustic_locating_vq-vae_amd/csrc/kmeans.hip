@@ -13,6 +13,9 @@
 //   relocate_kernel    one workgroup, only when a cluster is empty: sklearn's _relocate_empty_clusters_dense.
 //   finalize_kernel    one workgroup per cluster: centre = fl32(sum * (1 / count)), the shift |c_new - c_old|.
 //   verdict_kernel     one workgroup: center_shift_tot = sum shift^2 and the convergence verdict.
+// The EMA quantiser (VectorQuantizerEMA) takes its per-code statistics from the first five (hist .. clustersum, fp32 out) and
+// updates its state with ema_size_kernel (one workgroup: cluster sizes, their fp64 total, Laplace smoothing) and
+// ema_apply_kernel (elementwise: moving-average sums, codebook = sums / sizes).
 // k-means++ (greedy, sklearn's _kmeans_plusplus): per round, pick_kernel (one workgroup: the candidates by a blocked fp64
 // inclusive cumsum of closest_dist_sq), ppdist_kernel (64 rows per workgroup: candidate-to-row distances, min with the
 // closest, per-block potentials) and select_kernel (one workgroup: the candidate of least potential).  Three launches a round,
@@ -207,17 +210,19 @@ __global__ __launch_bounds__(128) void segsum_kernel(const float* __restrict__ x
   }
 }
 
+// TS, TC: double / int for the Lloyd update; float / float for the EMA quantiser's statistics (the fp64 sum rounded once)
+template <typename TS, typename TC>
 __global__ __launch_bounds__(128) void clustersum_kernel(const double* __restrict__ part, const int* __restrict__ seg_start,
-                                                         const int* __restrict__ cnt, double* __restrict__ sums,
-                                                         int* __restrict__ wcnt, int D) {
+                                                         const int* __restrict__ cnt, TS* __restrict__ sums,
+                                                         TC* __restrict__ wcnt, int D) {
   const int k = blockIdx.x, tid = threadIdx.x;
   const int g0 = seg_start[k], g1 = seg_start[k + 1];
   for (int d = tid; d < D; d += 128) {
     double s = 0.0;
     for (int g = g0; g < g1; ++g) s += part[(long)g * D + d];
-    sums[(long)k * D + d] = s;
+    sums[(long)k * D + d] = (TS)s;
   }
-  if (tid == 0) wcnt[k] = cnt[k];
+  if (tid == 0) wcnt[k] = (TC)cnt[k];
 }
 
 // dist[r] = |x_r - c[label_r]|^2 in fp64; skipped entirely when gate != NULL and *gate == 0
@@ -387,6 +392,43 @@ __global__ __launch_bounds__(1024) void sum_kernel(const double* __restrict__ v,
     double t = 0.0;
     for (int w = 0; w < 16; ++w) t += sh[w];
     out[0] = t;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- EMA codebook
+// Steps 1-3 of the update (include/alvq.h): cs = decay cs + (1 - decay) c; n = sum_k cs in fp64 (per thread in code order,
+// the wave butterflies, the waves in order); cs = (cs + eps) / (n + K eps) n.  The unsmoothed value is recomputed in the
+// second pass instead of being kept (K <= 16384 doubles would not fit LDS).  Nothing is written when *skip != 0.
+__global__ __launch_bounds__(1024) void ema_size_kernel(const float* __restrict__ counts, float* __restrict__ cs, const float* skip,
+                                                        int K, double decay, double eps) {
+  __shared__ double sh[16];
+  if (skip && *skip != 0.f) return;
+  const int tid = threadIdx.x;
+  const double omd = 1.0 - decay;
+  double s = 0.0;
+  for (int k = tid; k < K; k += 1024) s += decay * (double)cs[k] + omd * (double)counts[k];
+  s = km_wave_sum(s);
+  if ((tid & 63) == 0) sh[tid >> 6] = s;
+  __syncthreads();
+  double n = 0.0;
+  for (int w = 0; w < 16; ++w) n += sh[w];
+  const double den = n + (double)K * eps;
+  for (int k = tid; k < K; k += 1024) {
+    const double v = decay * (double)cs[k] + omd * (double)counts[k];
+    cs[k] = (float)((v + eps) / den * n);
+  }
+}
+
+// Steps 4-5: W = decay W + (1 - decay) s (fp64, rounded once); E = W / cs (fp32).  Nothing is written when *skip != 0.
+__global__ __launch_bounds__(256) void ema_apply_kernel(const float* __restrict__ sums, const float* __restrict__ cs,
+                                                        float* __restrict__ W, float* __restrict__ E, const float* skip, long n,
+                                                        int D, double decay) {
+  if (skip && *skip != 0.f) return;
+  const double omd = 1.0 - decay;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    const float w = (float)(decay * (double)W[e] + omd * (double)sums[e]);
+    W[e] = w;
+    E[e] = w / cs[e / D];
   }
 }
 
@@ -673,12 +715,57 @@ extern "C" int alvq_kmeans_update_f32(const float* x, const int64_t* labels, con
   hipLaunchKernelGGL(scatter_kernel, dim3(km_grid(N, 256)), dim3(256), 0, s, labels, w.HO, w.rank, w.perm, (long)N, K, nb);
   const int nseg_max = (int)((N + KM_SEG - 1) / KM_SEG + K);
   hipLaunchKernelGGL(segsum_kernel, dim3(nseg_max), dim3(128), 0, s, x, w.perm, w.start, w.cnt, w.seg_start, w.state, w.part, K, D);
-  hipLaunchKernelGGL(clustersum_kernel, dim3(K), dim3(128), 0, s, w.part, w.seg_start, w.cnt, w.sums, w.wcnt, D);
+  hipLaunchKernelGGL((clustersum_kernel<double, int>), dim3(K), dim3(128), 0, s, w.part, w.seg_start, w.cnt, w.sums, w.wcnt, D);
   hipLaunchKernelGGL(rowdist_kernel, dim3(km_grid(N, 4, 2048)), dim3(256), 0, s, x, labels, centers_old, w.dist,
                      (const int*)(w.state + 1), (long)N, K, D);
   hipLaunchKernelGGL(relocate_kernel, dim3(1), dim3(1024), 0, s, x, labels, w.dist, w.sums, w.wcnt, w.elist, w.state, (long)N, K, D);
   hipLaunchKernelGGL(finalize_kernel, dim3(K), dim3(128), 0, s, w.sums, w.wcnt, centers_old, centers_new, w.shift, counts, D);
   hipLaunchKernelGGL(verdict_kernel, dim3(1), dim3(256), 0, s, w.shift, w.state, flags, stats, K, tol);
+  return check_launch(who);
+}
+
+// EMA statistics: the Lloyd update's sort and fp64 cluster sums (the same layout and launches up to clustersum), written as
+// fp32 counts / sums into the caller's buffers.  Counts are exact in fp32 below 2^24 rows.
+extern "C" int64_t alvq_vq_ema_stats_workspace_bytes(int64_t N, int K, int D) {
+  if (N <= 0 || K <= 0 || D <= 0 || N >= (1L << 24) || K > KM_MAX_K || D > KM_MAX_D) return -1;
+  return update_layout(N, K, D, nullptr, nullptr);
+}
+
+extern "C" int alvq_vq_ema_stats_f32(const float* x, const int64_t* idx, float* counts, float* sums, void* workspace, int64_t N,
+                                     int K, int D, void* stream) {
+  const char* who = "alvq_vq_ema_stats_f32";
+  ALVQ_REQUIRE(x && idx && counts && sums && workspace, ALVQ_EINVAL, "%s: null pointer", who);
+  if (int rc = km_check(N, K, D, who)) return rc;
+  ALVQ_REQUIRE(N < (1L << 24), ALVQ_EUNSUPPORTED, "%s: N=%ld >= 2^24 rows (counts travel as fp32)", who, (long)N);
+  const int64_t NB = (N + KM_SB - 1) / KM_SB;
+  hipStream_t s = (hipStream_t)stream;
+  UpdateWs w;
+  update_layout(N, K, D, (char*)workspace, &w);
+  const int nb = (int)NB;
+  hipLaunchKernelGGL(hist_kernel, dim3(nb), dim3(64), (size_t)K * sizeof(int), s, idx, (const int64_t*)nullptr, w.HO, w.rank,
+                     w.blk_changed, (long)N, K, nb);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.HO, w.blk_changed, w.start, w.cnt, w.seg_start, w.state, K, nb);
+  hipLaunchKernelGGL(scatter_kernel, dim3(km_grid(N, 256)), dim3(256), 0, s, idx, w.HO, w.rank, w.perm, (long)N, K, nb);
+  const int nseg_max = (int)((N + KM_SEG - 1) / KM_SEG + K);
+  hipLaunchKernelGGL(segsum_kernel, dim3(nseg_max), dim3(128), 0, s, x, w.perm, w.start, w.cnt, w.seg_start, w.state, w.part, K, D);
+  hipLaunchKernelGGL((clustersum_kernel<float, float>), dim3(K), dim3(128), 0, s, w.part, w.seg_start, w.cnt, sums, counts, D);
+  return check_launch(who);
+}
+
+extern "C" int alvq_vq_ema_update_f32(const float* counts, const float* sums, float* cluster_size, float* ema_w, float* codebook,
+                                      const float* skip, int K, int D, double decay, double epsilon, void* stream) {
+  const char* who = "alvq_vq_ema_update_f32";
+  ALVQ_REQUIRE(counts && sums && cluster_size && ema_w && codebook, ALVQ_EINVAL, "%s: null pointer", who);
+  ALVQ_REQUIRE(K > 0 && D > 0, ALVQ_EINVAL, "%s: bad dims K=%d D=%d", who, K, D);
+  ALVQ_REQUIRE(K <= KM_MAX_K && D <= KM_MAX_D, ALVQ_EUNSUPPORTED, "%s: K=%d D=%d outside K <= %d, D <= %d", who, K, D, KM_MAX_K,
+               KM_MAX_D);
+  ALVQ_REQUIRE(decay > 0.0 && decay < 1.0 && epsilon > 0.0, ALVQ_EINVAL, "%s: decay=%g outside (0, 1) or epsilon=%g <= 0", who,
+               decay, epsilon);
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)K * D;
+  hipLaunchKernelGGL(ema_size_kernel, dim3(1), dim3(1024), 0, s, counts, cluster_size, skip, K, decay, epsilon);
+  hipLaunchKernelGGL(ema_apply_kernel, dim3(km_grid(n, 256, 1024)), dim3(256), 0, s, sums, (const float*)cluster_size, ema_w,
+                     codebook, skip, n, D, decay);
   return check_launch(who);
 }
 

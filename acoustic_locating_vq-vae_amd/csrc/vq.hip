@@ -359,6 +359,9 @@ __global__ __launch_bounds__(256) void vq_gather_loss_kernel(const float* x, con
   if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// QLAT: the loss carries the q-latent term (VectorQuantizer); without it, beta * m alone (VectorQuantizerEMA, whose codebook
+// follows moving averages instead of a gradient)
+template <bool QLAT>
 __global__ __launch_bounds__(256) void vq_finalize_kernel(const float* partials, int nparts, const int32_t* hist,
                                                           float* out, long N, int K, int D, float beta) {
   __shared__ float red[256];
@@ -386,7 +389,7 @@ __global__ __launch_bounds__(256) void vq_finalize_kernel(const float* partials,
   }
   if (t == 0) {
     const float m = sq / (float)((double)N * (double)D);
-    out[0] = m + beta * m;  // q_latent + beta * e_latent, both equal m in value (:46-52)
+    out[0] = QLAT ? m + beta * m : beta * m;  // q_latent + beta * e_latent, both equal m in value (:46-52)
     out[1] = expf(-red[0]);
   }
 }
@@ -581,9 +584,18 @@ extern "C" int alvq_vq_finalize_f32(const float* sq_partials, const int32_t* his
                                     float beta, void* stream) {
   ALVQ_REQUIRE(sq_partials && hist && out, ALVQ_EINVAL, "alvq_vq_finalize_f32: null pointer");
   ALVQ_REQUIRE(N > 0 && K > 0 && D > 0, ALVQ_EINVAL, "alvq_vq_finalize_f32: bad dims");
-  hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sq_partials, VQ_PARTIALS, hist,
+  hipLaunchKernelGGL(vq_finalize_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, sq_partials, VQ_PARTIALS, hist,
                      out, (long)N, K, D, beta);
   return check_launch("alvq_vq_finalize_f32");
+}
+
+extern "C" int alvq_vq_finalize_ema_f32(const float* sq_partials, const int32_t* hist, float* out, int64_t N, int K, int D,
+                                        float beta, void* stream) {
+  ALVQ_REQUIRE(sq_partials && hist && out, ALVQ_EINVAL, "alvq_vq_finalize_ema_f32: null pointer");
+  ALVQ_REQUIRE(N > 0 && K > 0 && D > 0, ALVQ_EINVAL, "alvq_vq_finalize_ema_f32: bad dims");
+  hipLaunchKernelGGL(vq_finalize_kernel<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, sq_partials, VQ_PARTIALS, hist,
+                     out, (long)N, K, D, beta);
+  return check_launch("alvq_vq_finalize_ema_f32");
 }
 
 constexpr int VQ_PARTS_MAX = 16;   // row segments a code's gather is split over

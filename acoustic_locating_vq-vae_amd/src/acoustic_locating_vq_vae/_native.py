@@ -38,6 +38,7 @@ _SIGNATURES = {
     "alvq_vq_argmin_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p]),
     "alvq_vq_gather_loss_f32": (_i32, [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p]),
     "alvq_vq_finalize_f32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _i32, _f32, _c_void_p]),
+    "alvq_vq_finalize_ema_f32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _i32, _f32, _c_void_p]),
     "alvq_vq_backward_workspace_bytes": (_i64, [_i32, _i32]),
     "alvq_vq_backward_f32": (_i32, [_c_void_p] * 8 + [_i64, _i32, _i32, _f32, _c_void_p]),
     "alvq_onehot_f32": (_i32, [_c_void_p, _c_void_p, _i64, _i32, _c_void_p]),
@@ -132,6 +133,9 @@ _SIGNATURES = {
     "alvq_kmeans_add_rows_f32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _f32, _c_void_p]),
     "alvq_kmeans_plusplus_workspace_bytes": (_i64, [_i64, _i32]),
     "alvq_kmeans_plusplus_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _i32, _i64, _c_void_p]),
+    "alvq_vq_ema_stats_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "alvq_vq_ema_stats_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p]),
+    "alvq_vq_ema_update_f32": (_i32, [_c_void_p] * 6 + [_i32, _i32, ctypes.c_double, ctypes.c_double, _c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -417,8 +421,8 @@ def vq_argmin(flat, codebook, want_dist=False):
     return (idx, dist) if want_dist else idx
 
 
-def vq_gather_loss(flat, codebook, idx, beta):
-    """-> (q_st (N,D), out[2] = (loss, perplexity))."""
+def vq_gather_loss(flat, codebook, idx, beta, ema=False):
+    """-> (q_st (N,D), out[2] = (loss, perplexity)).  ``ema``: the loss is beta * m alone (VectorQuantizerEMA)."""
     N, D = flat.shape
     K = codebook.shape[0]
     q_st = torch.empty_like(flat)
@@ -431,9 +435,35 @@ def vq_gather_loss(flat, codebook, idx, beta):
     _check(L.alvq_vq_gather_loss_f32(_ptr(flat, name="x"), _ptr(codebook, name="codebook"),
                                      _ptr(idx, torch.int64, "idx"), _ptr(q_st), _ptr(partials),
                                      _ptr(hist, torch.int32), N, K, D, _stream()), "alvq_vq_gather_loss_f32")
-    _check(L.alvq_vq_finalize_f32(_ptr(partials), _ptr(hist, torch.int32), _ptr(out), N, K, D, float(beta), _stream()),
-           "alvq_vq_finalize_f32")
+    fin = "alvq_vq_finalize_ema_f32" if ema else "alvq_vq_finalize_f32"
+    _check(getattr(L, fin)(_ptr(partials), _ptr(hist, torch.int32), _ptr(out), N, K, D, float(beta), _stream()), fin)
     return q_st, out
+
+
+def vq_ema_stats(flat, idx, counts, sums):
+    """Per-code statistics of one step into the caller's buffers (alvq_vq_ema_stats_f32): counts (K,) fp32 = rows per code,
+    sums (K, D) fp32 = their sum (fp64 in row order, rounded once)."""
+    N, D = flat.shape
+    K = counts.numel()
+    if idx.shape != (N,) or sums.shape != (K, D):
+        raise RuntimeError("vq_ema_stats: idx must be (%d,) and sums (%d, %d)" % (N, K, D))
+    nbytes = lib().alvq_vq_ema_stats_workspace_bytes(N, K, D)
+    if nbytes < 0:
+        raise RuntimeError("vq_ema_stats: N=%d, K=%d, D=%d out of range (N < 2^24, K <= 16384, D <= 512)" % (N, K, D))
+    ws = _workspace(nbytes, flat.device)
+    _check(lib().alvq_vq_ema_stats_f32(_ptr(flat, name="x"), _ptr(idx, torch.int64, "idx"), _ptr(counts, name="counts"),
+                                       _ptr(sums, name="sums"), ws.data_ptr(), N, K, D, _stream()), "alvq_vq_ema_stats_f32")
+
+
+def vq_ema_update(counts, sums, cluster_size, ema_w, codebook, decay, epsilon, skip=None):
+    """The EMA update of steps 1-5 (alvq_vq_ema_update_f32), in place; ``skip``: the Trainer's skip slot (non-zero: no write)."""
+    K, D = codebook.shape
+    if counts.numel() != K or cluster_size.numel() != K or sums.shape != (K, D) or ema_w.shape != (K, D):
+        raise RuntimeError("vq_ema_update: counts / cluster_size must be (%d,) and sums / ema_w (%d, %d)" % (K, K, D))
+    _check(lib().alvq_vq_ema_update_f32(_ptr(counts, name="counts"), _ptr(sums, name="sums"),
+                                        _ptr(cluster_size, name="cluster_size"), _ptr(ema_w, name="ema_w"),
+                                        _ptr(codebook, name="codebook"), _ptr(skip, name="skip"), K, D, float(decay),
+                                        float(epsilon), _stream()), "alvq_vq_ema_update_f32")
 
 
 def vq_backward(g, grad_loss, flat, codebook, idx, beta, want_dx=True, want_dE=True, dE_out=None):

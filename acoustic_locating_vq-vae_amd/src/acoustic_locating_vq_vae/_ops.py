@@ -918,6 +918,69 @@ class VQFn(torch.autograd.Function):
         return dx, (None if sink is not None else dE), None, None
 
 
+class VQEMAFn(torch.autograd.Function):
+    """VectorQuantizerEMA's quantisation -> (loss = beta * m, q_st, perplexity, idx).  Always fp32.  ``stats``: None, or the
+    (counts (K,), sums (K, D)) buffers that receive the step's per-code statistics.  The backward is VQFn's dx (the e-latent
+    term and the straight-through gradient) with ``codebook`` -- which must therefore still hold the codebook the forward
+    quantised with -- and no codebook gradient."""
+
+    @staticmethod
+    def forward(ctx, z, codebook, beta, stats):
+        z = dense(z)
+        d = codebook.shape[1]
+        flat = z.view(-1, d)                       # memory-order rows, no permute, as VQFn
+        idx = N.vq_argmin(flat, codebook)
+        q_st, out = N.vq_gather_loss(flat, codebook, idx, beta, ema=True)
+        if stats is not None:
+            N.vq_ema_stats(flat, idx, *stats)
+        ctx.beta, ctx.zshape = beta, z.shape
+        ctx.save_for_backward(flat, codebook, idx)
+        ctx.mark_non_differentiable(idx)
+        return out[0], q_st.view(z.shape), out[1], idx
+
+    @staticmethod
+    def backward(ctx, dloss, dq, dperp, _):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        flat, codebook, idx = ctx.saved_tensors
+        d = codebook.shape[1]
+        g = dq.contiguous().view(-1, d) if dq is not None else None
+        if dloss is None:
+            dloss = torch.zeros((), device=flat.device)
+        dx, _ = N.vq_backward(g, dloss.reshape(1).contiguous(), flat, codebook, idx, ctx.beta, want_dx=True, want_dE=False)
+        return dx.view(ctx.zshape), None, None, None
+
+
+# train_step.Trainer: while a dict {id(VectorQuantizerEMA): EMASink} is installed here, those quantisers write their per-code
+# statistics into the sink (a span of the flat gradient buffer) and leave the update to the Trainer
+_EMA_SINKS = None
+
+
+class EMASink:
+    """The statistics buffers of one quantiser in a Trainer; ``world``: ranks whose rows are summed into them; ``written``:
+    the last forward under the sink filled them."""
+
+    def __init__(self, counts, sums, world):
+        self.counts, self.sums, self.world, self.written = counts, sums, world, False
+
+
+class use_ema_sinks:
+    def __init__(self, sinks):
+        self.sinks = sinks
+
+    def __enter__(self):
+        global _EMA_SINKS
+        self.prev, _EMA_SINKS = _EMA_SINKS, self.sinks
+
+    def __exit__(self, *exc):
+        global _EMA_SINKS
+        _EMA_SINKS = self.prev
+
+
+def ema_sink(module):
+    return _EMA_SINKS.get(id(module)) if _EMA_SINKS else None
+
+
 class MeanPoolFn(torch.autograd.Function):
     """torch.mean(z, dim=2, keepdim=True): the optional pooling of the latent (convolutional_vq_vae.py:96-97)."""
 

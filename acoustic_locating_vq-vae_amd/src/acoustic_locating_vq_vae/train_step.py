@@ -46,9 +46,13 @@ class FlatBuffers:
     Both buffers start with a header of ``_ALIGN`` floats.  Element 0 of the GRADIENT buffer is the step's SKIP SLOT: the
     last launch of a backward writes 1.0 there if the step saturated an fp16-range format (``N.range_flag_to_slot``), the
     step's all-reduce sums it over the ranks with the gradients -- so every rank reaches the same verdict -- and the
-    optimiser launches leave everything untouched when it is non-zero (``FlatAdam``)."""
+    optimiser launches leave everything untouched when it is non-zero (``FlatAdam``).
 
-    def __init__(self, params):
+    ``extra``: floats of a non-parameter span appended to both buffers (``extra_span`` = [lo, hi)).  Its gradient-buffer side
+    travels with the step's all-reduce and is zeroed with the gradients; no parameter points into it and the optimiser
+    leaves it alone (the Trainer passes it in the skip list): the EMA quantisers' per-code statistics."""
+
+    def __init__(self, params, extra=0):
         self.params = unique_trainable(params)
         if not self.params:
             raise ValueError("no trainable parameters")
@@ -59,6 +63,8 @@ class FlatBuffers:
                 raise ValueError("all parameters must be fp32 on one device")
             self.offsets.append(total)
             total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+        self.extra_span = (total, total + extra) if extra else None
+        total += (extra + _ALIGN - 1) // _ALIGN * _ALIGN
         self.numel = sum(p.numel() for p in self.params)
         self.flat = torch.zeros(total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -284,7 +290,14 @@ class Trainer:
         # The caller's sub-models are left as they are (no requires_grad mutation).
         self._echoed_train_encoder = bool(getattr(model, "flag_train_encoder", False)) if kind == "echoed" else None
         params = model._decoder.parameters() if (kind == "echoed" and not self._echoed_train_encoder) else model.parameters()
-        self.buffers = FlatBuffers(params)
+        # EMA quantisers (decay > 0): their forward writes the per-code statistics into a span at the end of the flat gradient
+        # buffer, which the step's all-reduce sums over the ranks; _finish applies the update.  The echoed loop's quantisers
+        # are frozen by the model (set_train_vq(False)) and are not updated.
+        from .vq_vae.vector_quantizer import VectorQuantizerEMA
+        self._ema = [m for m in model.modules() if isinstance(m, VectorQuantizerEMA)] if kind != "echoed" else []
+        ema_lens = [(m._num_embeddings + _ALIGN - 1) // _ALIGN * _ALIGN + m._num_embeddings * m._embedding_dim
+                    for m in self._ema]
+        self.buffers = FlatBuffers(params, extra=sum(ema_lens))
         self._trainable = [p.requires_grad for p in self.buffers.params]
         if self.buffers.flat.is_cuda:
             _ops.register_grad_sinks(self.buffers.params)     # weight-grad launches accumulate straight into the flat buffer
@@ -296,6 +309,15 @@ class Trainer:
         self.opt = FlatAdam(self.buffers, lr=lr, guard=os.environ.get("ALVQ_SKIP_SATURATED", "1") != "0")
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         self.grad_scale = 1.0 / world
+        self._ema_sinks = {}
+        off = self.buffers.extra_span[0] if self._ema else 0
+        for m, n in zip(self._ema, ema_lens):
+            K, D = m._num_embeddings, m._embedding_dim
+            kp = (K + _ALIGN - 1) // _ALIGN * _ALIGN
+            self._ema_sinks[id(m)] = _ops.EMASink(self.buffers.grad[off:off + K], self.buffers.grad[off + kp:off + kp + K * D].view(K, D),
+                                                  world)
+            off += n
+        self._broadcast_ema()
         self._graph = None
         # Two gradient buckets for the VQ-VAE loops: "late" = encoder + pre-VQ conv (a prefix of the flat buffer, its
         # gradients are produced last), "early" = quantiser + decoder.  The backward runs in two parts so the early
@@ -310,6 +332,9 @@ class Trainer:
             if late and early:
                 self._late_params, self._early_params = late, early
                 self._buckets = (self.buffers.span(early), self.buffers.span(late))
+                xs = self.buffers.extra_span
+                if xs is not None and not any(lo <= xs[0] and xs[1] <= hi for lo, hi in self._buckets):
+                    raise RuntimeError("the EMA statistics span is not inside one gradient bucket")
         self._cut = None
 
     def preprocess(self, raw, wiener=None):
@@ -347,8 +372,8 @@ class Trainer:
 
     def _adam_skip(self):
         """Ranges of the flat buffer whose parameter gets no gradient this step: the codebook when its quantiser
-        runs with ``set_train_vq(False)`` (vector_quantizer.py:46-50 detaches both MSE terms)."""
-        skip = []
+        runs with ``set_train_vq(False)`` (vector_quantizer.py:46-50 detaches both MSE terms); the EMA statistics span."""
+        skip = [self.buffers.extra_span] if self.buffers.extra_span is not None else []
         ids = {id(p): i for i, p in enumerate(self.buffers.params)}
         for m in self.model.modules():
             if hasattr(m, "_train_vq") and not m._train_vq and id(m._embedding.weight) in ids:
@@ -363,7 +388,10 @@ class Trainer:
         RCCL call is ever recorded into a graph."""
         if self.buffers.flat.is_cuda:
             N.arena_reset(self.buffers.flat.device)          # scratch of the deferred split reductions: a step's worth
-        with _ops.use_pack_pool(self.pack_pool), _ops.use_grad_sinks(), _ops.deferred_reduce() as reductions:
+        for sink in self._ema_sinks.values():
+            sink.written = False
+        with _ops.use_pack_pool(self.pack_pool), _ops.use_grad_sinks(), _ops.deferred_reduce() as reductions, \
+                _ops.use_ema_sinks(self._ema_sinks):
             # one batched re-pack of every conv weight, then lookups; the weight-gradient launches leave their split
             # partials behind and ONE launch sums them all once the backward has been queued
             x, target = self.preprocess(raw, wiener)
@@ -418,6 +446,21 @@ class Trainer:
             self.opt.apply(self._adam_skip(), pack_pool=self.pack_pool)
         else:
             self.opt.apply(self._adam_skip())                  # one Adam launch over the flat buffer
+        skip = self.buffers.skip_slot if getattr(self.opt, "guard", False) else None
+        for m in self._ema:                                    # the EMA codebooks, from the statistics summed over the ranks
+            sink = self._ema_sinks[id(m)]
+            if sink.written:                                   # (a replay repeats what its capture wrote)
+                N.vq_ema_update(sink.counts, sink.sums, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data, m._decay,
+                                m._epsilon, skip=skip)
+
+    def _broadcast_ema(self):
+        """Rank 0's EMA state (cluster sizes, moving-average sums, codebook) to every rank of the group."""
+        if not self._ema or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.group) == 1:
+            return
+        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        for m in self._ema:
+            for t in (m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data):
+                dist.broadcast(t, src=src, group=self.group)
 
     # ------------------------------------------------------------------------------------------- checkpoint / resume
     def state_dict(self):
@@ -517,7 +560,7 @@ class Trainer:
 
         ``raw_batches``: one raw batch or an iterable of them (``wiener_batches`` alongside for kind="rir").  The codebook
         is written in place (the flat buffer's slice, so an already captured graph replays against it), and its slice of
-        the Adam moments is zeroed.  Nothing else caches the codebook: the quantiser recomputes its norms on every call and
+        the Adam moments is zeroed (an EMA quantiser's codebook has none; its moving averages are set as well).  Nothing else caches the codebook: the quantiser recomputes its norms on every call and
         no packed image of it exists.  Under data parallelism rank 0 fits on its own batches and broadcasts the codebook,
         so every rank ends with the same one."""
         if self.kind == "echoed":
@@ -540,6 +583,8 @@ class Trainer:
         if world > 1:
             dist.broadcast(weight.data, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0,
                            group=self.group)
+            if self._ema:
+                self._broadcast_ema()                          # the moving averages the k-means fit set alongside
         ids = {id(p): i for i, p in enumerate(self.buffers.params)}
         if id(weight) in ids:
             off = self.buffers.offsets[ids[id(weight)]]

@@ -12,7 +12,7 @@ from torch.utils.data import DataLoader
 
 from acoustic_locating_vq_vae.vq_vae.convolutional_encoder import ConvolutionalEncoder
 from acoustic_locating_vq_vae.vq_vae.deconvolutional_decoder import DeconvolutionalDecoder
-from acoustic_locating_vq_vae.vq_vae.vector_quantizer import VectorQuantizer
+from acoustic_locating_vq_vae.vq_vae.vector_quantizer import VectorQuantizer, VectorQuantizerEMA
 
 from . import _init
 from .. import _native, _ops
@@ -23,13 +23,21 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 class ConvolutionalVQVAE(nn.Module):
     def __init__(self, in_channels: int, num_hiddens: int, embedding_dim: int, num_residual_layers: int,
                  num_residual_hiddens: int, commitment_cost: float, num_embeddings: int, use_jitter: bool = True,
-                 encoder_average_pooling: bool = False, out_channels: int = None):
+                 encoder_average_pooling: bool = False, out_channels: int = None, decay: float = 0.0,
+                 epsilon: float = 1e-5):
+        """``decay`` > 0 (typically 0.99): the codebook follows exponential moving averages (``VectorQuantizerEMA(...,
+        decay, epsilon)``); 0 (the default): the reference's gradient-trained ``VectorQuantizer``."""
         out_channels = in_channels if out_channels is None else out_channels
+        if decay != 0 and not 0.0 < decay < 1.0:
+            raise ValueError("ConvolutionalVQVAE: decay must be 0 or lie in (0, 1), got %r" % (decay,))
         super().__init__()
         self.encoder_average_pooling = encoder_average_pooling
         self._encoder = ConvolutionalEncoder(in_channels, num_hiddens, num_residual_layers, num_residual_hiddens)
         self._pre_vq_conv = _init.kaiming_conv(nn.Conv1d(num_hiddens, embedding_dim, kernel_size=3, padding=1))
-        self._vq = VectorQuantizer(num_embeddings, embedding_dim, commitment_cost)
+        if decay > 0:
+            self._vq = VectorQuantizerEMA(num_embeddings, embedding_dim, commitment_cost, decay, epsilon)
+        else:
+            self._vq = VectorQuantizer(num_embeddings, embedding_dim, commitment_cost)
         self._decoder = DeconvolutionalDecoder(embedding_dim, out_channels, num_hiddens, num_residual_layers,
                                                num_residual_hiddens, use_jitter, 0.25)
 
@@ -75,7 +83,9 @@ class ConvolutionalVQVAE(nn.Module):
         ``forward`` runs it (current compute mode, ``encoder_average_pooling`` honoured) under no_grad; its rows are taken
         exactly as the quantiser takes them (``view(-1, D)`` of the contiguous buffer, no permute), and
         ``KMeans(n_clusters=num_embeddings, **kmeans_kwargs)`` is fitted on them.  The centres are copied in place into
-        ``_vq._embedding.weight`` (same storage).  ``_train_vq`` is left as it is."""
+        ``_vq._embedding.weight`` (same storage).  ``_train_vq`` is left as it is.  With an EMA quantiser the moving averages
+        start where those centres are: ``_ema_cluster_size`` = the mean number of rows per batch that carry each label,
+        ``_ema_w`` = the centres times those counts (so that ``_ema_w / _ema_cluster_size`` is the codebook)."""
         from ..kmeans import KMeans
         batches = [x] if isinstance(x, torch.Tensor) else list(x)
         if not batches:
@@ -89,7 +99,16 @@ class ConvolutionalVQVAE(nn.Module):
             rows.append(_ops.dense(z).view(-1, D))
         flat = rows[0] if len(rows) == 1 else torch.cat(rows)
         km = KMeans(n_clusters=self._vq._num_embeddings, **kmeans_kwargs).fit(flat)
-        self._vq._embedding.weight.data.copy_(km.cluster_centers_)
+        vq = self._vq
+        vq._embedding.weight.data.copy_(km.cluster_centers_)
+        if isinstance(vq, VectorQuantizerEMA):
+            K = vq._num_embeddings
+            counts = torch.empty((K,), device=flat.device, dtype=torch.float32)
+            sums = torch.empty((K, D), device=flat.device, dtype=torch.float32)
+            _native.vq_ema_stats(flat, km.labels_, counts, sums)
+            counts /= len(batches)
+            vq._ema_cluster_size.copy_(counts)
+            vq._ema_w.data.copy_(km.cluster_centers_ * counts[:, None])
         return km
 
     def train_on_data(self, optimizer: optim, dataloader: DataLoader, num_training_updates, data_variance):

@@ -111,6 +111,10 @@ int alvq_vq_gather_loss_f32(const float* x, const float* codebook, const int64_t
 int alvq_vq_finalize_f32(const float* sq_partials, const int32_t* hist, float* out, int64_t N, int K, int D,
                          float beta, void* stream);
 
+/* The same for VectorQuantizerEMA, whose loss has no q-latent term: out[0] = beta*m, out[1] = perplexity. */
+int alvq_vq_finalize_ema_f32(const float* sq_partials, const int32_t* hist, float* out, int64_t N, int K, int D,
+                             float beta, void* stream);
+
 /* Backward:  dx = g + gl*(2*beta/(N*D))*(x - E[idx]);
  * dE[k] += gl*(2/(N*D)) * sum_{n: idx_n = k} (E[k] - x_n)  (skipped when dE == NULL, i.e. _train_vq False);
  * g = grad wrt q_st (may be NULL = 0), gl = *grad_loss (device scalar, may be NULL = 1).  dE is accumulated into
@@ -336,6 +340,22 @@ int alvq_kmeans_col_stats_f32(const float* x, float* mean, double* var_mean, voi
 
 /* y[n][d] = x[n][d] + alpha * v[d] (fp32; y may alias x). */
 int alvq_kmeans_add_rows_f32(const float* x, const float* v, float* y, int64_t N, int D, float alpha, void* stream);
+
+/* EMA codebook (VectorQuantizerEMA).  Per-code statistics of one step: counts[k] = #rows with idx == k and sums[k][:] = the
+ * sum of those rows, accumulated in fp64 in row order (the Lloyd update's sort: counts, scan, stable scatter, 128-row
+ * segments summed in order) and rounded once to fp32.  Every code is written (zeros for an unused one).  idx int64 in
+ * [0, K); N < 2^24 (fp32 counts are exact), K <= 16384, D <= 512.  5 launches, no floating-point atomics, no host sync.
+ * workspace: alvq_vq_ema_stats_workspace_bytes(N, K, D) bytes (-1 out of range). */
+int64_t alvq_vq_ema_stats_workspace_bytes(int64_t N, int K, int D);
+int alvq_vq_ema_stats_f32(const float* x, const int64_t* idx, float* counts, float* sums, void* workspace, int64_t N, int K,
+                          int D, void* stream);
+
+/* The EMA update, in order (fp64 arithmetic, fp32 state):  1. cs = decay*cs + (1-decay)*counts;  2. n = sum_k cs (fixed
+ * order);  3. cs = (cs + eps) / (n + K*eps) * n (stored);  4. W = decay*W + (1-decay)*sums;  5. codebook = W / cs[:, None].
+ * cluster_size (K), ema_w and codebook (K, D) are updated in place.  skip (nullable): a device float; non-zero leaves all
+ * three untouched (the Trainer's skip slot).  0 < decay < 1, epsilon > 0.  2 launches, no host sync. */
+int alvq_vq_ema_update_f32(const float* counts, const float* sums, float* cluster_size, float* ema_w, float* codebook,
+                           const float* skip, int K, int D, double decay, double epsilon, void* stream);
 
 /* Greedy k-means++ (sklearn's _kmeans_plusplus): centre 0 = x[first]; closest_dist_sq in fp64; per round c >= 1, T
  * candidates r_t = uniforms[c-1][t] * current_pot found in the blocked fp64 inclusive cumsum of closest_dist_sq (first
