@@ -7,7 +7,9 @@ raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import functools
 import os
 
 import torch
@@ -854,42 +856,109 @@ def tsne_descend(P, Y, update, gains, grad, stats, n_iter, exaggeration, momentu
 
 
 # ----------------------------------------------------------------------------------------------- bf16 path
+# KernelTimer names follow rocprofv3's kernel names -- function plus its leading template arguments -- so that bench.py's
+# per-kernel figures can be laid beside `rocprofv3 --kernel-trace --stats` line by line: conv1d_f16mx_kernel<OUT, KW, ...>,
+# conv1d_bf16x3_kernel<OUT, KW, ...>, conv1d_bf16_k3_kernel<OUT, F16>, conv1d_bf16_v2_kernel<OUT, F16>,
+# conv1d_bf16_kernel<KW, OUT, F16> (OUT: 0 = NLC output, 1 = fp32 NCL; F16: the fp16 opcodes of the bf16 kernels)
+def _conv16_name(f16, out, KW, M, rows):
+    """Mirrors the dispatch in csrc/conv1d_bf16.hip: wide layers go to the 256x256-tile kernels (k3 for width 3)."""
+    min_tiles = get_option("wide_min_tiles")
+    if ((M + 255) // 256 * 256 - M) <= 32 and (rows // 256) * ((M + 255) // 256) >= min_tiles:
+        return ("conv1d_bf16_k3_kernel<%d, %d>" if KW == 3 else "conv1d_bf16_v2_kernel<%d, %d>") % (out, f16)
+    return "conv1d_bf16_kernel<%d, %d, %d>" % (KW, out, f16)
+
+
+def _wgrad16_name(KW, with_bias, f16):
+    """rocprofv3's name of the 16-bit weight-gradient kernel a launch gets (mirrors csrc/conv1d_wgrad_bf16_v2.hip: the v3
+    kernels serve the launches without a bias gradient, option wgrad_v3)."""
+    sel = get_option("wgrad_v3")
+    if not with_bias and ((KW == 1 and sel & 1) or (KW == 3 and sel & 2)):
+        return "conv1d_wgrad_bf16_v3_kernel<%s, %d>" % ("3, 1, 2" if KW == 3 else "1, 2, 4", f16)
+    return "conv1d_wgrad_bf16_v2_kernel<%s, %d>" % ("3, 2" if KW == 3 else "1, 4", f16)
+
+
+# One row per activation format: everything the functions below need to know about it.
+#   planes       planes of an activation (the second one at +alvq_nlc_plane_bytes)
+#   bits         the buffer ends in rows*Cp/8 bytes for the sign bits a ReLU'd convolution can leave behind; the forward
+#                conv then takes (mask_bits, bits_out)
+#   scaled       fp16 range: gradients carry a loss scale (NLC.gscale); every launch then takes one more pointer to S or 1/S
+#   defer        the weight gradient may leave its split reduction to wgrad_reduce_batch
+#   wcode/wreads packed-weight code the format packs to (alvq_pack_weights_bf16_batch) / the codes a launch may read: an f16
+#                launch reads the H image of an f16mx weight, a bf16 launch may read the hi image of a bf16x3 one
+#   operands     formats whose tensors serve as an operand: an f16 launch reads an f16mx tensor through its H plane, a bf16
+#                launch a bf16x3 tensor through its hi plane (the backward of the _hb modes)
+#   rows_code    format code of alvq_rows_to_nlc, None where it does not serve the format
+#   relu_flat    the ReLU mask takes a flat element count (else B, C, L); pack: None = only the batched launch packs it
+#   *_family     KernelTimer family of a launch (bench.py keys its roofline on them)
+_Format = collections.namedtuple("_Format", (
+    "name", "planes", "bits", "scaled", "defer", "wcode", "wreads", "operands", "rows_code", "to_nlc", "to_ncl", "relu",
+    "relu_flat", "pack", "conv", "wgrad", "wgrad_multi", "wgrad_ws", "conv_family", "wgrad_family"))
+_FORMATS = {f.name: f for f in (
+    _Format("bf16", planes=1, bits=True, scaled=False, defer=True, wcode=1, wreads=(1, 2), operands=("bf16", "bf16x3"),
+            rows_code=1, to_nlc="alvq_ncl_to_nlc_bf16", to_ncl="alvq_nlc_to_ncl_f32", relu="alvq_relu_mask_bf16",
+            relu_flat=True, pack="alvq_pack_weight_bf16", conv="alvq_conv1d_bf16", wgrad="alvq_conv1d_wgrad_bf16",
+            wgrad_multi="alvq_conv1d_wgrad_bf16_multi", wgrad_ws="alvq_conv1d_wgrad_bf16_workspace_bytes",
+            conv_family=functools.partial(_conv16_name, 0),
+            wgrad_family=lambda KW, with_bias: _wgrad16_name(KW, with_bias, 0)),
+    _Format("bf16x3", planes=2, bits=False, scaled=False, defer=False, wcode=2, wreads=(2,), operands=("bf16x3",),
+            rows_code=2, to_nlc="alvq_ncl_to_nlc_bf16x3", to_ncl="alvq_nlc_to_ncl_bf16x3", relu="alvq_relu_mask_bf16x3",
+            relu_flat=False, pack="alvq_pack_weight_bf16x3", conv="alvq_conv1d_bf16x3", wgrad="alvq_conv1d_wgrad_bf16x3",
+            wgrad_multi="alvq_conv1d_wgrad_bf16x3_multi", wgrad_ws="alvq_conv1d_wgrad_bf16x3_workspace_bytes",
+            conv_family=lambda out, KW, M, rows: "conv1d_bf16x3_kernel<%d, %d, ...>" % (out, KW),
+            wgrad_family=lambda KW, with_bias: "conv1d_wgrad_bf16x3_kernel"),
+    _Format("f16mx", planes=2, bits=True, scaled=True, defer=False, wcode=3, wreads=(3,), operands=("f16mx",),
+            rows_code=3, to_nlc="alvq_ncl_to_nlc_f16mx", to_ncl="alvq_nlc_to_ncl_f16mx", relu="alvq_relu_mask_f16mx",
+            relu_flat=False, pack=None, conv="alvq_conv1d_f16mx", wgrad="alvq_conv1d_wgrad_f16mx",
+            wgrad_multi="alvq_conv1d_wgrad_f16mx_multi", wgrad_ws="alvq_conv1d_wgrad_f16mx_workspace_bytes",
+            conv_family=lambda out, KW, M, rows: "conv1d_f16mx_kernel<%d, %d, ...>" % (out, KW),
+            wgrad_family=lambda KW, with_bias: "conv1d_wgrad_f16mx_kernel"),
+    # one fp16 plane: the bf16 kernels with fp16 opcodes (their ReLU mask tests the sign of a 16-bit pattern, whichever type)
+    _Format("f16", planes=1, bits=True, scaled=True, defer=True, wcode=3, wreads=(3,), operands=("f16", "f16mx"),
+            rows_code=None, to_nlc="alvq_ncl_to_nlc_f16", to_ncl="alvq_nlc_to_ncl_f16", relu="alvq_relu_mask_bf16",
+            relu_flat=True, pack=None, conv="alvq_conv1d_f16", wgrad="alvq_conv1d_wgrad_f16",
+            wgrad_multi="alvq_conv1d_wgrad_f16_multi", wgrad_ws="alvq_conv1d_wgrad_bf16_workspace_bytes",
+            conv_family=functools.partial(_conv16_name, 1),
+            wgrad_family=lambda KW, with_bias: _wgrad16_name(KW, with_bias, 1)))}
+_PACKERS = {f.wcode: f.pack for f in _FORMATS.values()}      # by weight code: what pack_weight launches
+
+
+def _format(planes, fmt):
+    """The door: the (planes, fmt) pair of the public signatures -> the row.  Without a name the plane count picks the bf16 family."""
+    f = _FORMATS[fmt or ("bf16x3" if planes == 2 else "bf16")]
+    if f.planes != planes:
+        raise ValueError("format %s has %d plane(s), not %d" % (f.name, f.planes, planes))
+    return f
+
+
 class NLC:
     """An activation in the NLC-padded layout (see include/alvq.h): storage = guard rows + matrix + guard rows.
 
     ``fmt``: "bf16" (one plane), "bf16x3" (hi + lo bf16 planes), "f16mx" (fp16 H plane + fp8 Q plane; same bytes and
-    geometry as bf16x3) or "f16" (one fp16 plane: the gradients of the f16mx_hb mode; an f16mx tensor serves wherever an
-    "f16" operand is expected -- its H plane is one).  ``gscale``: for a gradient in the f16mx / f16 formats, the 4-float
-    device state of its loss scale ({S, 1/S, ...}, alvq_grad_scale_f32) -- inherited by everything computed from it and
-    divided out where the chain leaves the format; None for forward tensors."""
+    geometry as bf16x3) or "f16" (one fp16 plane: the gradients of the f16mx_hb mode) -- a row of ``_FORMATS``.
+    ``has_bits``: the sign bits behind the planes are valid.  ``gscale``: for a gradient in the f16mx / f16 formats, the
+    4-float device state of its loss scale ({S, 1/S, ...}, alvq_grad_scale_f32) -- inherited by everything computed from it
+    and divided out where the chain leaves the format; None for forward tensors."""
     __slots__ = ("storage", "B", "L", "C", "Cp", "rows", "guard", "planes", "has_bits", "fmt", "gscale")
 
-    def __init__(self, B, L, C, device, planes=1, fmt=None, gscale=None):
-        """planes=2: the split forms (hi / H plane, then the lo / Q plane at +alvq_nlc_plane_bytes).
-        bf16 and f16mx buffers carry a tail of rows*Cp/8 bytes for the sign bits a ReLU'd convolution can leave behind
-        (see alvq_conv1d_bf16 / alvq_conv1d_f16mx); ``has_bits`` says whether they are valid."""
+    def _shape(self, B, L, C, planes, fmt):
+        """Sets the geometry; returns (format row, elements of a buffer of it, the sign-bit tail included)."""
+        f = _format(planes, fmt)
         L_ = lib()
-        self.B, self.L, self.C, self.planes = B, L, C, planes
-        self.fmt = fmt or ("bf16x3" if planes == 2 else "bf16")
-        self.gscale = gscale
-        self.Cp = L_.alvq_nlc_channels(C)
-        self.rows = L_.alvq_nlc_rows(B, L)
-        self.guard = L_.alvq_nlc_guard_rows()
-        self.has_bits = False
-        n = planes * (self.rows + 2 * self.guard) * self.Cp + (self.rows * self.Cp // 16 if self.fmt != "bf16x3" else 0)
+        self.B, self.L, self.C, self.planes, self.fmt = B, L, C, f.planes, f.name
+        self.Cp, self.rows, self.guard = L_.alvq_nlc_channels(C), L_.alvq_nlc_rows(B, L), L_.alvq_nlc_guard_rows()
+        return f, f.planes * (self.rows + 2 * self.guard) * self.Cp + (self.rows * self.Cp // 16 if f.bits else 0)
+
+    def __init__(self, B, L, C, device, planes=1, fmt=None, gscale=None):
+        _, n = self._shape(B, L, C, planes, fmt)
+        self.gscale, self.has_bits = gscale, False
         self.storage = torch.empty((n,), device=device, dtype=torch.bfloat16)
 
     @classmethod
     def wrap(cls, storage, B, L, C, planes=1, has_bits=False, fmt=None):
         self = cls.__new__(cls)
-        L_ = lib()
-        self.B, self.L, self.C, self.planes = B, L, C, planes
-        self.fmt = fmt or ("bf16x3" if planes == 2 else "bf16")
-        self.gscale = None
-        self.Cp, self.rows, self.guard = L_.alvq_nlc_channels(C), L_.alvq_nlc_rows(B, L), L_.alvq_nlc_guard_rows()
-        self.storage = storage
-        self.has_bits = bool(has_bits) and self.fmt != "bf16x3" and \
-            storage.numel() >= planes * (self.rows + 2 * self.guard) * self.Cp + self.rows * self.Cp // 16
+        f, n = self._shape(B, L, C, planes, fmt)
+        self.gscale, self.storage = None, storage
+        self.has_bits = bool(has_bits) and f.bits and storage.numel() >= n
         return self
 
     @property
@@ -898,7 +967,7 @@ class NLC:
 
     @property
     def bits_ptr(self):
-        """Sign-bit area behind the plane(s) (bf16 and f16mx)."""
+        """Sign-bit area behind the plane(s)."""
         return self.storage.data_ptr() + self.planes * (self.rows + 2 * self.guard) * self.Cp * 2
 
     def matrix(self, plane=0):
@@ -946,9 +1015,8 @@ def f16mx_range_flag(reset=True, device="cuda"):
 
 
 def _fmt_serves(t, ref):
-    """Can ``t`` be read as an operand of ``ref``'s format?  Same format, or an f16mx tensor read through its H plane."""
-    return (t.planes, t.fmt) == (ref.planes, ref.fmt) or (ref.fmt == "f16" and t.fmt == "f16mx") or \
-        (ref.fmt == "bf16" and t.fmt == "bf16x3")           # ... or a bf16x3 tensor through its hi plane (bf16x3_hb's backward)
+    """Can ``t`` be read as an operand of ``ref``'s format?"""
+    return t.fmt in _FORMATS[ref.fmt].operands
 
 
 def _nlc_ptr(t, ref, C, name):
@@ -960,23 +1028,18 @@ def _nlc_ptr(t, ref, C, name):
 
 
 def ncl_to_nlc(x, planes=1, fmt=None, gscale=None):
-    """(B,C,L) fp32 dense -> NLC bf16 (planes=2: split hi/lo; fmt="f16mx": fp16 + fp8 planes, multiplied by the loss
-    scale S of ``gscale`` when given)."""
+    """(B,C,L) fp32 dense -> NLC (planes=2: split hi/lo; fmt="f16mx": fp16 + fp8 planes; the loss-scaled formats multiply
+    by the S of ``gscale`` when given)."""
     B, C, L = x.shape
     out = NLC(B, L, C, x.device, planes, fmt, gscale)
-    if out.fmt == "f16":
-        _check(lib().alvq_ncl_to_nlc_f16(_ptr(x, name="x"), out.ptr, B, C, L, _sptr(gscale, 0), _stream()), "alvq_ncl_to_nlc_f16")
-    elif out.fmt == "f16mx":
-        _check(lib().alvq_ncl_to_nlc_f16mx(_ptr(x, name="x"), out.ptr, B, C, L, _sptr(gscale, 0), _stream()), "alvq_ncl_to_nlc_f16mx")
-    elif planes == 2:
-        _check(lib().alvq_ncl_to_nlc_bf16x3(_ptr(x, name="x"), out.ptr, B, C, L, _stream()), "alvq_ncl_to_nlc_bf16x3")
-    else:
-        _check(lib().alvq_ncl_to_nlc_bf16(_ptr(x, name="x"), out.ptr, B, C, L, _stream()), "alvq_ncl_to_nlc_bf16")
+    f = _FORMATS[out.fmt]
+    _check(getattr(lib(), f.to_nlc)(_ptr(x, name="x"), out.ptr, B, C, L, *((_sptr(gscale, 0),) if f.scaled else ()), _stream()),
+           f.to_nlc)
     return out
 
 
 def rows_to_nlc_supported(fmt, L, standardise=False):
-    return fmt in ("bf16", "bf16x3", "f16mx") and (not standardise or 2 <= L <= lib().alvq_rows_to_nlc_max_std_rows())
+    return _FORMATS[fmt].rows_code is not None and (not standardise or 2 <= L <= lib().alvq_rows_to_nlc_max_std_rows())
 
 
 def rows_to_nlc(x_blc, planes=1, fmt=None, standardise=False, take_abs=False):
@@ -987,41 +1050,31 @@ def rows_to_nlc(x_blc, planes=1, fmt=None, standardise=False, take_abs=False):
     out = NLC(B, L, C, x_blc.device, planes, fmt)
     if not rows_to_nlc_supported(out.fmt, L, standardise):
         raise RuntimeError("rows_to_nlc: format %s / L = %d not supported" % (out.fmt, L))
-    code = {"bf16": 1, "bf16x3": 2, "f16mx": 3}[out.fmt]
-    _check(lib().alvq_rows_to_nlc(_ptr(x_blc, name="x"), out.ptr, B, C, L, code, int(bool(standardise)), int(bool(take_abs)), _stream()),
-           "alvq_rows_to_nlc")
+    _check(lib().alvq_rows_to_nlc(_ptr(x_blc, name="x"), out.ptr, B, C, L, _FORMATS[out.fmt].rows_code, int(bool(standardise)),
+                                  int(bool(take_abs)), _stream()), "alvq_rows_to_nlc")
     return out
 
 
 def nlc_to_ncl(a):
-    """NLC bf16 -> (B,C,L) fp32 dense."""
+    """NLC -> (B,C,L) fp32 dense (a loss-scaled gradient: divided by its S)."""
+    f = _FORMATS[a.fmt]
     y = torch.empty((a.B, a.C, a.L), device=a.storage.device, dtype=torch.float32)
-    if a.fmt == "f16":
-        _check(lib().alvq_nlc_to_ncl_f16(a.ptr, _ptr(y), a.B, a.C, a.L, _sptr(a.gscale, 1), _stream()), "alvq_nlc_to_ncl_f16")
-    elif a.fmt == "f16mx":
-        _check(lib().alvq_nlc_to_ncl_f16mx(a.ptr, _ptr(y), a.B, a.C, a.L, _sptr(a.gscale, 1), _stream()), "alvq_nlc_to_ncl_f16mx")
-    elif a.planes == 2:
-        _check(lib().alvq_nlc_to_ncl_bf16x3(a.ptr, _ptr(y), a.B, a.C, a.L, _stream()), "alvq_nlc_to_ncl_bf16x3")
-    else:
-        _check(lib().alvq_nlc_to_ncl_f32(a.ptr, _ptr(y), a.B, a.C, a.L, _stream()), "alvq_nlc_to_ncl_f32")
+    _check(getattr(lib(), f.to_ncl)(a.ptr, _ptr(y), a.B, a.C, a.L, *((_sptr(a.gscale, 1),) if f.scaled else ()), _stream()),
+           f.to_ncl)
     return y
 
 
 def pack_weight(w, w_layout, planes=1):
-    """fp32 weight (M,C,KW) [OIK] or (C,M,KW) [IOK] -> packed bf16 image(s) + (M, C, KW, planes)."""
-    if w_layout == W_OIK:
-        M, C, KW = w.shape
+    """fp32 weight (M,C,KW) [OIK] or (C,M,KW) [IOK] -> packed bf16 image(s) + (M, C, KW, planes).  ``planes``: the weight
+    code of the format that will read it (``wcode`` in _FORMATS)."""
+    wp, tag = packed_weight_alloc(w, w_layout, planes)
+    symbol = _PACKERS[planes]
+    if symbol is None:
+        pack_weights_batch([(w, wp, w_layout)], planes)
     else:
-        C, M, KW = w.shape
-    n = lib().alvq_packed_weight_elems(M, C, KW)
-    wp = torch.empty((min(planes, 2) * n,), device=w.device, dtype=torch.bfloat16)
-    if planes == 3:                                  # f16mx: H + Q images
-        pack_weights_batch([(w, wp, w_layout)], 3)
-    elif planes == 2:
-        _check(lib().alvq_pack_weight_bf16x3(_ptr(w, name="w"), wp.data_ptr(), M, C, KW, w_layout, _stream()), "alvq_pack_weight_bf16x3")
-    else:
-        _check(lib().alvq_pack_weight_bf16(_ptr(w, name="w"), wp.data_ptr(), M, C, KW, w_layout, _stream()), "alvq_pack_weight_bf16")
-    return wp, (M, C, KW, planes)
+        M, C, KW, _ = tag
+        _check(getattr(lib(), symbol)(_ptr(w, name="w"), wp.data_ptr(), M, C, KW, w_layout, _stream()), symbol)
+    return wp, tag
 
 
 class PackDesc(ctypes.Structure):
@@ -1094,19 +1147,10 @@ def adam_segments(param, grad, exp_avg, exp_avg_sq, segments, scalars, beta1=0.9
 
 
 def relu_mask_bf16(dy, t):
+    f = _FORMATS[dy.fmt]
     out = nlc_like(dy, dy.C)
-    if dy.fmt == "f16":                  # t: fp16, or an f16mx activation through its H plane (sign test on the int16 pattern)
-        n = dy.rows * dy.Cp
-        _check(lib().alvq_relu_mask_bf16(dy.ptr, _nlc_ptr(t, dy, dy.C, "t"), out.ptr, n, _stream()), "alvq_relu_mask_bf16")
-    elif dy.fmt == "f16mx":
-        _check(lib().alvq_relu_mask_f16mx(dy.ptr, _nlc_ptr(t, dy, dy.C, "t"), out.ptr, dy.B, dy.C, dy.L, _stream()),
-               "alvq_relu_mask_f16mx")
-    elif dy.planes == 2:
-        _check(lib().alvq_relu_mask_bf16x3(dy.ptr, _nlc_ptr(t, dy, dy.C, "t"), out.ptr, dy.B, dy.C, dy.L, _stream()),
-               "alvq_relu_mask_bf16x3")
-    else:
-        n = dy.rows * dy.Cp
-        _check(lib().alvq_relu_mask_bf16(dy.ptr, _nlc_ptr(t, dy, dy.C, "t"), out.ptr, n, _stream()), "alvq_relu_mask_bf16")
+    dims = (dy.rows * dy.Cp,) if f.relu_flat else (dy.B, dy.C, dy.L)
+    _check(getattr(lib(), f.relu)(dy.ptr, _nlc_ptr(t, dy, dy.C, "t"), out.ptr, *dims, _stream()), f.relu)
     return out
 
 
@@ -1115,13 +1159,12 @@ USE_SIGN_BITS = os.environ.get("ALVQ_SIGN_BITS", "1") != "0"
 
 def conv1d_bf16(x, packed, bias=None, skip1=None, skip2=None, mask=None, post=None, relu=False, out_ncl=False):
     """x: NLC; packed = pack_weight(...).  Returns NLC y, (y, y2) with post, or a (B,M,L) fp32 tensor if out_ncl."""
-    wp, (M, C, KW, wplanes) = packed
+    f = _FORMATS[x.fmt]
+    wp, (M, C, KW, wcode) = packed
     if C != x.C:
         raise RuntimeError("conv1d_bf16: weight expects %d input channels, x has %d" % (C, x.C))
-    # an f16 launch reads the H image of an f16mx packed weight, a bf16 launch may read the hi image of a bf16x3 one
-    if wplanes != (3 if x.fmt in ("f16mx", "f16") else x.planes) and not (x.fmt == "bf16" and wplanes == 2):
-        raise RuntimeError("conv1d_bf16: weight packed for format %d, activation is %s" % (wplanes, x.fmt))
-    split = x.planes == 2
+    if wcode not in f.wreads:
+        raise RuntimeError("conv1d_bf16: weight packed for format %d, activation is %s" % (wcode, x.fmt))
     if bias is not None and bias.numel() != M:
         raise RuntimeError("conv1d_bf16: bias has %d elements, expected %d" % (bias.numel(), M))
     y = y2 = y_ncl = None
@@ -1130,155 +1173,100 @@ def conv1d_bf16(x, packed, bias=None, skip1=None, skip2=None, mask=None, post=No
     else:
         y = nlc_like(x, M)
         y2 = nlc_like(x, M) if post is not None else None
-    # KernelTimer names follow rocprofv3's kernel names -- function plus its leading template arguments -- so that bench.py's
-    # per-kernel figures can be laid beside `rocprofv3 --kernel-trace --stats` line by line: conv1d_f16mx_kernel<OUT, KW, ...>,
-    # conv1d_bf16x3_kernel<OUT, KW, ...>, conv1d_bf16_k3_kernel<OUT, F16>, conv1d_bf16_v2_kernel<OUT, F16>,
-    # conv1d_bf16_kernel<KW, OUT, F16> (OUT: 0 = NLC output, 1 = fp32 NCL; F16: the fp16 opcodes of the bf16 kernels)
-    o_ = int(bool(out_ncl))
-    if x.fmt == "f16mx":
-        family, fn = "conv1d_f16mx_kernel<%d, %d, ...>" % (o_, KW), lib().alvq_conv1d_f16mx
-    elif split:
-        family, fn = "conv1d_bf16x3_kernel<%d, %d, ...>" % (o_, KW), lib().alvq_conv1d_bf16x3
-    else:
-        # mirrors the dispatch in csrc/conv1d_bf16.hip: wide layers go to the 256x256-tile kernels (k3 for width 3)
-        f16 = int(x.fmt == "f16")
-        min_tiles = get_option("wide_min_tiles")
-        wide = ((M + 255) // 256 * 256 - M) <= 32 and (x.rows // 256) * ((M + 255) // 256) >= min_tiles
-        if wide:
-            family = ("conv1d_bf16_k3_kernel<%d, %d>" if KW == 3 else "conv1d_bf16_v2_kernel<%d, %d>") % (o_, f16)
-        else:
-            family = "conv1d_bf16_kernel<%d, %d, %d>" % (KW, o_, f16)
-        fn = lib().alvq_conv1d_f16 if f16 else lib().alvq_conv1d_bf16
-    # sign bits: a ReLU'd bf16 output records them; a mask operand that carries valid bits is passed as bits
+    family = f.conv_family(int(bool(out_ncl)), KW, M, x.rows)
+    # sign bits: a ReLU'd output records them; a mask operand that carries valid bits is passed as bits
     extra = ()
     mask_ptr = _nlc_ptr(mask, x, M, "mask")
-    with_bits = x.fmt != "bf16x3"
-    if with_bits:
+    bits_out = f.bits and y is not None and relu and USE_SIGN_BITS
+    if f.bits:
         mask_bits = None
         if mask is not None and mask.has_bits and USE_SIGN_BITS:
             mask_bits, mask_ptr = mask.bits_ptr, None
-        bits_out = y.bits_ptr if (y is not None and relu and USE_SIGN_BITS) else None
-        extra = (mask_bits, bits_out)
-    if x.fmt in ("f16mx", "f16"):
+        extra = (mask_bits, y.bits_ptr if bits_out else None)
+    if f.scaled:
         extra += (_sptr(x.gscale, 1) if out_ncl else None,)     # a gradient leaving the format: divide the loss scale out
     with _timed(family, 2.0 * x.B * x.L * M * C * KW):
-        rc = fn(x.ptr, wp.data_ptr(), _ptr(bias, name="bias"), _nlc_ptr(skip1, x, M, "skip1"),
-                                    _nlc_ptr(skip2, x, M, "skip2"), mask_ptr,
-                                    _nlc_ptr(post, x, M, "post"), y.ptr if y is not None else None,
-                                    y2.ptr if y2 is not None else None, _ptr(y_ncl), x.B, C, M, x.L, KW,
-                                    int(bool(relu)), *extra, _stream())
-    if with_bits and y is not None and relu and USE_SIGN_BITS:
+        rc = getattr(lib(), f.conv)(x.ptr, wp.data_ptr(), _ptr(bias, name="bias"), _nlc_ptr(skip1, x, M, "skip1"),
+                                    _nlc_ptr(skip2, x, M, "skip2"), mask_ptr, _nlc_ptr(post, x, M, "post"),
+                                    y.ptr if y is not None else None, y2.ptr if y2 is not None else None, _ptr(y_ncl),
+                                    x.B, C, M, x.L, KW, int(bool(relu)), *extra, _stream())
+    if bits_out:
         y.has_bits = True
-    _check(rc, "alvq_conv1d_bf16")
+    _check(rc, f.conv)
     if out_ncl:
         return y_ncl
     return (y, y2) if post is not None else y
 
 
-def _wgrad16_name(KW, with_bias, f16):
-    """rocprofv3's name of the 16-bit weight-gradient kernel a launch gets (mirrors csrc/conv1d_wgrad_bf16_v2.hip: the v3
-    kernels serve the launches without a bias gradient, option wgrad_v3)."""
-    sel = get_option("wgrad_v3")
-    if not with_bias and ((KW == 1 and sel & 1) or (KW == 3 and sel & 2)):
-        return "conv1d_wgrad_bf16_v3_kernel<%s, %d>" % ("3, 1, 2" if KW == 3 else "1, 2, 4", f16)
-    return "conv1d_wgrad_bf16_v2_kernel<%s, %d>" % ("3, 2" if KW == 3 else "1, 4", f16)
+def _wgrad_out(who, dy, x, KW, w_layout, dw_out, accumulate):
+    """fp32 dw in the weight's native layout -> (the caller's, shape-checked, or a fresh one; whether the launch adds to it)."""
+    shape = (dy.C, x.C, KW) if w_layout == W_OIK else (x.C, dy.C, KW)
+    if dw_out is None:
+        return torch.empty(shape, device=x.storage.device, dtype=torch.float32), False
+    if tuple(dw_out.shape) != shape:
+        raise RuntimeError("%s: dw_out has shape %s, expected %s" % (who, tuple(dw_out.shape), shape))
+    return dw_out, accumulate
+
+
+def _wgrad_scratch(f, dy, x, KW, deferred):
+    """The split partials of one launch: arena scratch, which lives until the batch reduction, when the reduction is deferred,
+    else the grow-only workspace."""
+    nbytes = getattr(lib(), f.wgrad_ws)(x.B, x.C, dy.C, x.L, KW)
+    dev = x.storage.device
+    return arena_alloc(nbytes, dev) if deferred else _workspace(nbytes, dev).data_ptr()
+
+
+def _wgrad_launch(f, symbol, family, head, ws_ptr, nseg, dy, x, KW, w_layout, dw, dbias, accumulate, defer):
+    """``head``: the operands in front of the workspace -- all that differs between the single- and the multi-segment ABI.
+    ``defer``: None, or the list that receives the descriptors of the reduction this launch leaves undone."""
+    B, C, M, L = x.B, x.C, dy.C, x.L
+    scale = dy.gscale if f.scaled else None
+    with _timed(family, 2.0 * nseg * B * L * M * C * KW):
+        rc = getattr(lib(), symbol)(*head, ws_ptr, B, C, M, L, KW, w_layout,
+                                    WGRAD_DEFER if defer is not None else int(bool(accumulate)),
+                                    *((_sptr(scale, 1),) if f.scaled else ()), _stream())
+    _check(rc, symbol)
+    if defer is not None:
+        _defer_descs(defer, ws_ptr, dw, dbias, scale, nseg, B, C, M, L, KW, w_layout)
 
 
 def conv1d_wgrad_bf16(dy, x, KW, w_layout=W_OIK, want_bias=False, dw_out=None, dbias_out=None, accumulate=False, defer=None):
     """dy, x: NLC.  fp32 dw in the weight's native layout (and dbias).  ``defer`` (a list; bf16 / fp16 formats, with
     ``accumulate`` into caller-owned dw_out / dbias_out): launch the contraction only and append the reduction's descriptors
     -- the caller sums them all later with ``wgrad_reduce_batch``."""
-    M, C = dy.C, x.C
-    shape = (M, C, KW) if w_layout == W_OIK else (C, M, KW)
-    dev = x.storage.device
-    if dw_out is None:
-        dw_out = torch.empty(shape, device=dev, dtype=torch.float32)
-        accumulate = False
-    elif tuple(dw_out.shape) != shape:
-        raise RuntimeError("conv1d_wgrad_bf16: dw_out has shape %s, expected %s" % (tuple(dw_out.shape), shape))
+    f = _FORMATS[dy.fmt]
+    dw_out, accumulate = _wgrad_out("conv1d_wgrad_bf16", dy, x, KW, w_layout, dw_out, accumulate)
     if want_bias and dbias_out is None:
-        dbias_out = torch.empty((M,), device=dev, dtype=torch.float32)
+        dbias_out = torch.empty((dy.C,), device=x.storage.device, dtype=torch.float32)
     if not _fmt_serves(x, dy):
         raise RuntimeError("conv1d_wgrad_bf16: dy and x differ in format")
-    extra = ()
-    if dy.fmt == "f16":                  # x: fp16, or the H plane of a saved f16mx activation
-        family, fn, wsfn = _wgrad16_name(KW, want_bias, 1), lib().alvq_conv1d_wgrad_f16, lib().alvq_conv1d_wgrad_bf16_workspace_bytes
-        extra = (_sptr(dy.gscale, 1),)
-    elif x.fmt == "f16mx":
-        family, fn, wsfn = "conv1d_wgrad_f16mx_kernel", lib().alvq_conv1d_wgrad_f16mx, lib().alvq_conv1d_wgrad_f16mx_workspace_bytes
-        extra = (_sptr(dy.gscale, 1),)
-    elif x.planes == 2 and dy.planes == 2:
-        family, fn, wsfn = "conv1d_wgrad_bf16x3_kernel", lib().alvq_conv1d_wgrad_bf16x3, lib().alvq_conv1d_wgrad_bf16x3_workspace_bytes
-    else:
-        family, fn, wsfn = _wgrad16_name(KW, want_bias, 0), lib().alvq_conv1d_wgrad_bf16, lib().alvq_conv1d_wgrad_bf16_workspace_bytes
-    deferred = defer is not None and accumulate and dy.fmt in ("bf16", "f16")
-    ws_ptr = arena_alloc(wsfn(x.B, C, M, x.L, KW), dev) if deferred else _workspace(wsfn(x.B, C, M, x.L, KW), dev).data_ptr()
-    with _timed(family, 2.0 * x.B * x.L * M * C * KW):
-        rc = fn(dy.ptr, x.ptr, _ptr(dw_out, name="dw"),
-                                          _ptr(dbias_out, name="dbias") if want_bias else None, ws_ptr,
-                                          x.B, C, M, x.L, KW, w_layout, WGRAD_DEFER if deferred else int(bool(accumulate)), *extra,
-                                          _stream())
-    _check(rc, "alvq_conv1d_wgrad_bf16")
-    if deferred:
-        _defer_descs(defer, ws_ptr, dw_out, dbias_out if want_bias else None, dy.gscale if dy.fmt == "f16" else None, 1, x.B, C, M,
-                     x.L, KW, w_layout)
+    if not (accumulate and f.defer):
+        defer = None
+    family = f.wgrad_family(KW, want_bias)
+    dbias = dbias_out if want_bias else None
+    _wgrad_launch(f, f.wgrad, family, (dy.ptr, x.ptr, _ptr(dw_out, name="dw"), _ptr(dbias, name="dbias")),
+                  _wgrad_scratch(f, dy, x, KW, defer is not None), 1, dy, x, KW, w_layout, dw_out, dbias, accumulate, defer)
     return (dw_out, dbias_out) if want_bias else dw_out
 
 
 def conv1d_wgrad_bf16_multi(pairs, KW, w_layout=W_OIK, dw_out=None, accumulate=False, defer=None):
     """dw (+)= sum_i wgrad(dy_i, x_i) in one launch (shared residual weights).  pairs: [(dy NLC, x NLC), ...] (1..4)."""
     dy0, x0 = pairs[0]
-    M, C = dy0.C, x0.C
-    fx, x3, h16 = dy0.fmt == "f16mx", dy0.fmt == "bf16x3", dy0.fmt == "f16"
+    f = _FORMATS[dy0.fmt]
     for dy, x in pairs:
-        if (dy.B, dy.L, dy.C, dy.fmt, dy.planes, x.B, x.L, x.C) != (dy0.B, dy0.L, M, dy0.fmt, dy0.planes, x0.B, x0.L, C) or \
-                not _fmt_serves(x, dy):
+        if (dy.B, dy.L, dy.C, dy.fmt, x.B, x.L, x.C) != (dy0.B, dy0.L, dy0.C, dy0.fmt, x0.B, x0.L, x0.C) or not _fmt_serves(x, dy):
             raise RuntimeError("conv1d_wgrad_bf16_multi: all segments must share one shape and format")
-        if (fx or h16) and dy.gscale is not dy0.gscale:
+        if f.scaled and dy.gscale is not dy0.gscale:
             raise RuntimeError("conv1d_wgrad_bf16_multi: the segments belong to different loss-scale chains")
-    shape = (M, C, KW) if w_layout == W_OIK else (C, M, KW)
-    dev = x0.storage.device
-    if dw_out is None:
-        dw_out = torch.empty(shape, device=dev, dtype=torch.float32)
-        accumulate = False
-    elif tuple(dw_out.shape) != shape:
-        raise RuntimeError("conv1d_wgrad_bf16_multi: dw_out has shape %s, expected %s" % (tuple(dw_out.shape), shape))
+    dw_out, accumulate = _wgrad_out("conv1d_wgrad_bf16_multi", dy0, x0, KW, w_layout, dw_out, accumulate)
     n = len(pairs)
     dys = (ctypes.c_void_p * n)(*[dy.ptr for dy, _ in pairs])
     xs = (ctypes.c_void_p * n)(*[x.ptr for _, x in pairs])
-    deferred = defer is not None and accumulate and dy0.fmt in ("bf16", "f16")
-    if deferred or h16 or not (fx or x3):
-        nbytes = lib().alvq_conv1d_wgrad_bf16_workspace_bytes(x0.B, C, M, x0.L, KW)
-        ws_ptr = arena_alloc(nbytes, dev) if deferred else _workspace(nbytes, dev).data_ptr()
-        acc = WGRAD_DEFER if deferred else int(bool(accumulate))
-    if h16:
-        with _timed(_wgrad16_name(KW, False, 1), 2.0 * n * x0.B * x0.L * M * C * KW):
-            rc = lib().alvq_conv1d_wgrad_f16_multi(dys, xs, n, _ptr(dw_out, name="dw"), ws_ptr, x0.B, C, M, x0.L, KW,
-                                                   w_layout, acc, _sptr(dy0.gscale, 1), _stream())
-        _check(rc, "alvq_conv1d_wgrad_f16_multi")
-        if deferred:
-            _defer_descs(defer, ws_ptr, dw_out, None, dy0.gscale, n, x0.B, C, M, x0.L, KW, w_layout)
-        return dw_out
-    if fx:
-        ws = _workspace(lib().alvq_conv1d_wgrad_f16mx_workspace_bytes(x0.B, C, M, x0.L, KW), dev)
-        with _timed("conv1d_wgrad_f16mx_kernel", 2.0 * n * x0.B * x0.L * M * C * KW):
-            rc = lib().alvq_conv1d_wgrad_f16mx_multi(dys, xs, n, _ptr(dw_out, name="dw"), ws.data_ptr(), x0.B, C, M, x0.L, KW,
-                                                     w_layout, int(bool(accumulate)), _sptr(dy0.gscale, 1), _stream())
-        _check(rc, "alvq_conv1d_wgrad_f16mx_multi")
-        return dw_out
-    if x3:
-        ws = _workspace(lib().alvq_conv1d_wgrad_bf16x3_workspace_bytes(x0.B, C, M, x0.L, KW), dev)
-        with _timed("conv1d_wgrad_bf16x3_kernel", 2.0 * n * x0.B * x0.L * M * C * KW):
-            rc = lib().alvq_conv1d_wgrad_bf16x3_multi(dys, xs, n, _ptr(dw_out, name="dw"), ws.data_ptr(), x0.B, C, M, x0.L, KW,
-                                                      w_layout, int(bool(accumulate)), _stream())
-        _check(rc, "alvq_conv1d_wgrad_bf16x3_multi")
-        return dw_out
-    with _timed(_wgrad16_name(KW, False, 0), 2.0 * n * x0.B * x0.L * M * C * KW):
-        rc = lib().alvq_conv1d_wgrad_bf16_multi(dys, xs, n, _ptr(dw_out, name="dw"), ws_ptr, x0.B, C, M, x0.L, KW,
-                                                w_layout, acc, _stream())
-    _check(rc, "alvq_conv1d_wgrad_bf16_multi")
-    if deferred:
-        _defer_descs(defer, ws_ptr, dw_out, None, None, n, x0.B, C, M, x0.L, KW, w_layout)
+    if not (accumulate and f.defer):
+        defer = None
+    ws_ptr = _wgrad_scratch(f, dy0, x0, KW, defer is not None)
+    _wgrad_launch(f, f.wgrad_multi, f.wgrad_family(KW, False), (dys, xs, n, _ptr(dw_out, name="dw")), ws_ptr, n, dy0, x0, KW,
+                  w_layout, dw_out, None, accumulate, defer)
     return dw_out
 
 

@@ -6,51 +6,40 @@ epilogue and the ReLU-backward masks live in the data-grad conv's epilogue.
 
 Notation follows SURVEY App. A:  t_r = relu(h_{r-1}),  u_r = relu(W1 *3 t_r),  h_r = t_r + W2 *1 u_r.
 
-Two precisions share these chains through a small "engine" object:
+The chains are written once and run by an "engine" object.  ``_F32Engine`` keeps activations (B,C,L) fp32 exactly as the
+reference lays them out and multiplies with the exact-fp32 MFMA.  Every other engine is an ``_NLCEngine``: activations in
+the NLC-padded 16-bit layout between convs, described by two rows of ``_native._FORMATS`` -- the format activations enter
+the forward in and the format gradients enter a backward chain in; module inputs/outputs, the quantiser, losses, gradients
+of parameters and the optimiser state stay fp32.  The formats (DESIGN.md has the measurements):
 
-* ``f32``  -- activations (B,C,L) fp32 exactly as the reference lays them out, exact-fp32 MFMA (parity mode);
-* ``bf16`` -- activations in the NLC-padded bf16 layout between convs, bf16 MFMA with fp32 accumulation
-  (BASELINE configs[1]); module inputs/outputs, the quantiser, losses, gradients of parameters and the
-  optimiser state stay fp32;
-* ``bf16x3`` -- the same pipeline with every tensor split into two bf16 planes (hi, lo) and every product
-  evaluated as hi*hi + hi*lo + lo*hi: fp32-grade parity (~1e-5) at a third of the bf16 MFMA rate, i.e. several
-  times the exact-fp32 MFMA that gfx950 offers (it has no TF32/xf32).
+* ``bf16``   -- one bf16 plane, one bf16 MFMA per product (fp32 accumulation);
+* ``bf16x3`` -- two bf16 planes (hi, lo), every product hi*hi + hi*lo + lo*hi: fp32-grade (~6e-6) at a third of the bf16 rate;
+* ``f16mx``  -- an fp16 plane plus an fp8 (hi, lo) plane, products fp16*fp16 + one block-scaled fp8 MFMA: ~1.5e-5, two
+  matrix-pipe units per product; fp16's range, so gradients run under a power-of-two loss scale chosen on the device;
+* ``f16``    -- one fp16 plane under the loss scale: reads the H plane of an f16mx tensor / packed weight as it is.
 
-* ``f16mx`` -- the split pipeline at TWO matrix-pipe units per product: every tensor is an fp16 plane plus an fp8
-  (hi, lo) plane, products are fp16*fp16 (one fp16 MFMA) + hi8*lo8 + lo8*hi8 (one block-scaled fp8 MFMA at twice the
-  rate); ~1.5e-5 per product, same parity class as bf16x3 at ~2/3 of its matrix time.  Gradients run under a
-  power-of-two loss scale chosen on the device (csrc/f16mx_common.h).
+A mode says which engine runs which role (``_MODE_ENGINES``; the decoder is the only role a mode singles out):
 
-* ``f16mx_hb`` -- f16mx forward + fp16 ("half") backward: the forward is f16mx's bit for bit; every backward product is
-  one fp16 MFMA on the H planes of the saved activations / packed weights and of gradients kept as ONE fp16 plane under the
-  loss scale.  Measured against f32 at the speech config (tests/analysis/gate_flips.py): gradient rel-L2 4.8e-4 median (f16mx:
-  4.3e-4) -- in both modes the gradient error is set by the ~1e-5 forward noise flipping ReLU gates, not by the backward
-  products -- at 0.72x the f16mx step time.
+    mode         every role: forward / gradients     decoder, where it differs
+    x3mx_hb      bf16x3 / bf16                        f16mx / f16                 (the DEFAULT)
+    f16mx_hb     f16mx / f16
+    bf16x3_hb    bf16x3 / bf16
+    f32          exact fp32 (strict gradient parity)
+    bf16         bf16 / bf16 (throughput; ~1 % of the indices differ)
+    f16mx        f16mx / f16mx
+    bf16x3       bf16x3 / bf16x3
+    f16mx_hd     f16mx / f16                          f16 / f16
 
-* ``bf16x3_hb`` -- bf16x3 forward + bf16 ("half") backward: the forward is bf16x3's bit for bit -- the most accurate split
-  format: 6e-6, i.e. 2.3x fewer flipped near-ties than the f16mx family (expected 14 against 33 per million codebook rows,
-  tests/analysis/near_ties.py; none in the 47 834 rows of the reference goldens, where f16mx flips one) -- and every backward product
-  is ONE bf16 MFMA on the hi planes (no loss scale: bf16 has fp32's range).  Gradient rel-L2 ~2e-3 per tensor (the bf16
-  operands), 0.94x f16mx_hb's rate.
+In the ``_hb`` ("half backward") modes the forward -- everything the reference's outputs, codebook indices and
+reconstructions depend on -- is the split format's bit for bit, and every backward product is ONE 16-bit MFMA on the first
+planes of the saved activations and packed weights.  ``x3mx_hb`` runs everything the indices depend on (encoder, pre-VQ
+convolution) in the most accurate split format and the decoder in the cheaper one.
 
-* ``f16mx_hd`` -- (opt-in) f16mx_hb with the DECODER's forward on fp16 operands too (one fp16 plane per activation, one fp16
-  MFMA per product; the H image of the same packed weights).  Encoder, pre-VQ convolution and quantiser are f16mx_hb's bit
-  for bit, so the codebook indices stay bit-exact; the reconstruction carries fp16's operand rounding through ~10 layers:
-  5e-4 ... 7e-4 of the fp32 result at the default configs, 1.3e-3 measured on a 48-channel model -- at the north star's 1e-3,
-  not safely inside it -- and the decoder-side gradients see ~30x the ReLU gate flips.  0.87x the f16mx_hb step time.
-
-* ``x3mx_hb`` -- (round 4; the DEFAULT) per-role arithmetic: everything the codebook indices depend on -- the encoder
-  and the pre-VQ convolution -- runs the bf16x3 forward (6.6e-6: every index of every reference golden, the 1.8e-6 RIR
-  near-tie included), the decoder's forward runs f16mx (2e-5 on the reconstruction), and every backward product is ONE 16-bit
-  MFMA: bf16 on the hi planes of the encoder's saved activations, fp16 under the loss scale on the H planes of the decoder's.
-
-Select with ``set_compute_dtype(...)`` or the environment variable ``ALVQ_DTYPE``.  User-selectable modes (``MODES``):
-``x3mx_hb`` (default), ``f16mx_hb`` (2-3 % faster; resolves reference near-ties down to ~4e-6 relative), ``bf16x3_hb``,
-``f32`` (exact-fp32 MFMA: strict gradient parity, 1e-6), ``bf16`` (throughput; ~1 % of the indices differ).  ``f16mx``,
-``bf16x3`` and ``f16mx_hd`` are INTERNAL engines since round 4 (their forwards live on inside the ``_hb`` modes; the
-kernel-level tests reach them with ``set_compute_dtype(name, internal=True)``).  The f16mx-range modes carry fp16's range:
-activations must stay below 65504; a step whose values saturate is SKIPPED by the Trainer's optimiser launch (csrc/
-pack_weights.hip) and counted (``_native.f16mx_range_state()``).
+Select with ``set_compute_dtype(...)`` or the environment variable ``ALVQ_DTYPE``.  The first five rows are user-selectable
+(``MODES``); ``f16mx``, ``bf16x3`` and ``f16mx_hd`` are INTERNAL (``INTERNAL_MODES``: the kernel-level tests reach them with
+``set_compute_dtype(name, internal=True)``).  A mode that touches ``f16mx`` or ``f16`` carries fp16's range
+(``has_fp16_range``): activations must stay below 65504; a step whose values saturate is SKIPPED by the Trainer's optimiser
+launch (csrc/pack_weights.hip) and counted (``_native.f16mx_range_state()``).
 """
 from __future__ import annotations
 
@@ -80,8 +69,8 @@ def set_compute_dtype(name, internal=False):
 
 
 def has_fp16_range(mode=None):
-    """Does the mode keep any tensor in an fp16-range format (f16mx planes, fp16 gradients)?"""
-    return (mode or _DTYPE) in ("x3mx_hb", "f16mx_hb", "f16mx", "f16mx_hd")
+    """Does the mode keep any tensor in an fp16-range format (f16mx planes, fp16 gradients -- the loss-scaled formats)?"""
+    return any(f is not None and f.scaled for e in _MODE_ENGINES[mode or _DTYPE].values() for f in (e.fwd, e.grad))
 
 
 def get_compute_dtype():
@@ -353,6 +342,12 @@ class use_pack_pool:
         _ACTIVE_POOL = self.prev
 
 
+def _defer_kw(eng, sink):
+    """The ``defer`` argument of a weight-gradient launch that accumulates into ``sink``, where it may leave its reduction
+    to the step's batch launch (the fp32 engine's launch has no such argument)."""
+    return {"defer": _DEFERRED} if (_DEFERRED is not None and sink is not None and eng.can_defer) else {}
+
+
 def _wgrad(eng, dy, x, kw, layout, w, b=None, dw_prev=None):
     """(dw, db) of one conv use.  Sinked tensors come back as None (already accumulated in place); otherwise dw is
     accumulated onto ``dw_prev`` (shared residual weights) or freshly allocated.  A frozen weight
@@ -365,10 +360,7 @@ def _wgrad(eng, dy, x, kw, layout, w, b=None, dw_prev=None):
         raise RuntimeError("a convolution with a frozen weight and a trainable bias is not supported on the HIP path")
     sw, sb = _sink(w), _sink(b)
     if sw is not None and (b is None or sb is not None):
-        if _DEFERRED is not None and getattr(eng, "can_defer", False):
-            eng.wgrad(dy, x, kw, layout, want_bias=b is not None, dw_out=sw, dbias_out=sb, accumulate=True, defer=_DEFERRED)
-        else:
-            eng.wgrad(dy, x, kw, layout, want_bias=b is not None, dw_out=sw, dbias_out=sb, accumulate=True)
+        eng.wgrad(dy, x, kw, layout, want_bias=b is not None, dw_out=sw, dbias_out=sb, accumulate=True, **_defer_kw(eng, sw))
         return None, None
     if b is not None:
         dw, db = eng.wgrad(dy, x, kw, layout, want_bias=True, dw_out=dw_prev, accumulate=dw_prev is not None)
@@ -436,6 +428,9 @@ def _need_gpu(x, who):
 # --------------------------------------------------------------------------------------------------
 class _F32Engine:
     name = "f32"
+    fwd = grad = None           # no NLC format: activations stay (B,C,L) fp32
+    can_defer = False
+    wgrad_multi = None
 
     def enter(self, x, grad=False):
         return dense(x)
@@ -460,53 +455,60 @@ class _F32Engine:
         return tensor
 
 
-class _BF16Engine:
-    name = "bf16"
-    planes = 1          # planes of an activation
-    wplanes = 1         # format code of a packed weight (alvq_pack_weights_bf16_batch)
-    fmt = "bf16"
+class _NLCEngine:
+    """The 16-bit pipeline: activations enter the NLC layout in the ``fwd`` format, gradients enter their backward chain in
+    the ``grad`` format (rows of ``_native._FORMATS``, which say the rest: planes, loss scale, what may read what).  The
+    launches dispatch on their operands' format, so a half-backward engine reads its saved split activations and packed
+    weights through their first plane / image: nothing is converted or stored twice."""
+    can_defer = True     # the launch defers only where the gradient's format allows; the others reduce at once
+    wgrad_multi = staticmethod(N.conv1d_wgrad_bf16_multi)     # sum_i wgrad(dy_i, x_i) in one launch
+
+    def __init__(self, name, fwd, grad):
+        self.name, self.fwd, self.grad = name, N._FORMATS[fwd], N._FORMATS[grad]
 
     def _w(self, w, layout):
+        wcode = self.fwd.wcode          # one packed image per weight: the gradient format reads the forward's
         if _ACTIVE_POOL is not None:
-            hit = _ACTIVE_POOL.lookup(w, layout, self.wplanes)
+            hit = _ACTIVE_POOL.lookup(w, layout, wcode)
             if hit is not None:
                 return hit
         if torch.cuda.is_current_stream_capturing():
             # inside a user's own graph capture a cache hit would freeze a packed image into the graph while later
             # replays expect fresh weights: pack in the graph, every time
-            return N.pack_weight(w.detach(), layout, self.wplanes)
-        return _cached_pack(w, layout, self.wplanes)
+            return N.pack_weight(w.detach(), layout, wcode)
+        return _cached_pack(w, layout, wcode)
 
-    def _enter_rows(self, x, planes, fmt):
+    def _enter_rows(self, x, f):
         """The input boundary without a transposition: a permuted view of a contiguous tensor (train_rir.py:45) or the
-        Trainer's not-yet-standardised batch has its channel axis contiguous already -- one pass, straight into the layout."""
+        Trainer's not-yet-standardised batch has its channel axis contiguous already -- one pass, straight into the layout
+        (the formats with a rows code)."""
         if os.environ.get("ALVQ_ROWS_BOUNDARY", "1") == "0":
             return None
         if isinstance(x, StandardisedT):
-            if N.rows_to_nlc_supported(fmt, x.raw.shape[1], True):
-                return N.rows_to_nlc(x.raw, planes, fmt, standardise=True)
+            if N.rows_to_nlc_supported(f.name, x.raw.shape[1], True):
+                return N.rows_to_nlc(x.raw, f.planes, f.name, standardise=True)
             return None
         blc = _as_blc(x)
-        if blc is not None and blc.is_cuda and N.rows_to_nlc_supported(fmt, blc.shape[1]):
-            return N.rows_to_nlc(blc, planes, fmt)
+        if blc is not None and blc.is_cuda and N.rows_to_nlc_supported(f.name, blc.shape[1]):
+            return N.rows_to_nlc(blc, f.planes, f.name)
         return None
 
     def enter(self, x, grad=False):
-        """fp32 (B,C,L) -> the engine's layout.  ``grad``: x is a gradient entering a backward chain (only the f16mx
-        engine cares: it picks the chain's loss scale from x)."""
+        """fp32 (B,C,L) -> the engine's layout.  ``grad``: x is a gradient entering a backward chain -- in a loss-scaled
+        format the chain's scale is picked from x."""
+        f = self.grad if grad else self.fwd
         if not grad:
-            hit = self._enter_rows(x, self.planes, self.fmt)
+            hit = self._enter_rows(x, f)
             if hit is not None:
                 return hit
-        return N.ncl_to_nlc(dense(x), self.planes)
+        x = dense(x)
+        return N.ncl_to_nlc(x, f.planes, f.name, N.grad_scale(x) if grad and f.scaled else None)
 
     def leave(self, a):
         return N.nlc_to_ncl(a)
 
     def conv(self, x, w, layout=OIK, bias=None, skip1=None, skip2=None, mask=None, post=None, relu=False, out_f32=False):
         return N.conv1d_bf16(x, self._w(w, layout), bias, skip1, skip2, mask, post, relu, out_ncl=out_f32)
-
-    can_defer = True     # the launch defers only for the bf16 / fp16 operand formats; the others reduce at once
 
     def wgrad(self, dy, x, kw, layout, want_bias=False, dw_out=None, dbias_out=None, accumulate=False, defer=None):
         return N.conv1d_wgrad_bf16(dy, x, kw, layout, want_bias=want_bias, dw_out=dw_out, dbias_out=dbias_out,
@@ -515,11 +517,6 @@ class _BF16Engine:
     def relu_mask(self, dy, t):
         return N.relu_mask_bf16(dy, t)
 
-    @property
-    def wgrad_multi(self):
-        """sum_i wgrad(dy_i, x_i) in one launch (every NLC mode)."""
-        return N.conv1d_wgrad_bf16_multi
-
     def pack(self, act):
         return act.storage, (act.B, act.L, act.C, act.planes, act.has_bits, act.fmt)
 
@@ -527,100 +524,29 @@ class _BF16Engine:
         return N.NLC.wrap(tensor, *meta)
 
 
-class _BF16x3Engine(_BF16Engine):
-    name = "bf16x3"
-    planes = 2
-    wplanes = 2
-    fmt = "bf16x3"
-
-
-class _F16MXEngine(_BF16Engine):
-    name = "f16mx"
-    planes = 2
-    wplanes = 3
-    fmt = "f16mx"
-
-    def enter(self, x, grad=False):
-        if not grad:
-            hit = self._enter_rows(x, 2, "f16mx")
-            if hit is not None:
-                return hit
-        x = dense(x)
-        return N.ncl_to_nlc(x, 2, "f16mx", N.grad_scale(x) if grad else None)
-
-    @property
-    def wgrad_multi(self):
-        return N.conv1d_wgrad_bf16_multi
-
-
-class _F16MXHBEngine(_F16MXEngine):
-    """f16mx forward, fp16 ("half") backward: the forward pass -- everything the reference's outputs, codebook indices and
-    reconstructions depend on -- is f16mx's, bit for bit; gradients enter their chains as ONE fp16 plane under the
-    device-chosen loss scale and every backward product is fp16 x fp16 with fp32 accumulation (the H planes of the saved
-    f16mx activations and packed weights are the operands: nothing is converted or stored twice).  ~5e-4 per backward
-    product instead of 1.5e-5: mixed-precision-training gradients on top of an fp32-grade forward, at about 0.7x the
-    f16mx step time.  The launches dispatch on their operands' format (_native.conv1d_bf16 / conv1d_wgrad_bf16)."""
-    name = "f16mx_hb"
-
-    def enter(self, x, grad=False):
-        if not grad:
-            hit = self._enter_rows(x, 2, "f16mx")
-            if hit is not None:
-                return hit
-        x = dense(x)
-        if grad:
-            return N.ncl_to_nlc(x, 1, "f16", N.grad_scale(x))
-        return N.ncl_to_nlc(x, 2, "f16mx", None)
-
-
-class _BF16x3HBEngine(_BF16x3Engine):
-    """bf16x3 forward, bf16 ("half") backward -- f16mx_hb's idea on the most accurate split format: the forward is bf16x3's bit
-    for bit (6e-6: 2.3x fewer flipped near-ties than f16mx, none in the goldens' 47 834 rows), gradients enter
-    their chains as ONE bf16 plane (fp32 range: no loss scale) and every backward product is one bf16 MFMA on the hi planes
-    of the saved activations / packed weights."""
-    name = "bf16x3_hb"
-
-    def enter(self, x, grad=False):
-        if not grad:
-            hit = self._enter_rows(x, 2, "bf16x3")
-            if hit is not None:
-                return hit
-        return N.ncl_to_nlc(dense(x), 1 if grad else 2)
-
-
-class _F16MXHDEngine(_F16MXHBEngine):
-    """f16mx_hb with the DECODER's forward in fp16 as well (opt-in; module docstring): encoder, pre-VQ convolution and
-    quantiser -- everything the codebook indices depend on -- stay f16mx bit for bit; the decoder's activations are ONE fp16
-    plane and its products one fp16 MFMA each (the H image of the same packed weights)."""
-    name = "f16mx_hd"
-
-
-class _F16DecoderEngine(_F16MXHBEngine):
-    """The decoder's engine in the f16mx_hd mode: fp16 activations, fp16 gradients."""
-    name = "f16dec"
-    planes = 1
-    fmt = "f16"
-
-    def enter(self, x, grad=False):
-        x = dense(x)
-        return N.ncl_to_nlc(x, 1, "f16", N.grad_scale(x) if grad else None)
-
-
-# x3mx_hb has no engine of its own: its parts run bf16x3_hb's (encoder side, and any module used on its own) and f16mx_hb's
-# (decoder) engines, so a saved node re-wraps its activations by the name of the engine that made them
-_ENGINES = {"f32": _F32Engine, "bf16": _BF16Engine, "bf16x3": _BF16x3Engine, "f16mx": _F16MXEngine, "f16mx_hb": _F16MXHBEngine,
-            "f16mx_hd": _F16MXHDEngine, "bf16x3_hb": _BF16x3HBEngine, "x3mx_hb": _BF16x3HBEngine}
-_ROLE_ENGINES = {("f16mx_hd", "decoder"): _F16DecoderEngine, ("x3mx_hb", "decoder"): _F16MXHBEngine}
-_ENGINES_BY_NAME = dict(_ENGINES, f16dec=_F16DecoderEngine)
-assert set(MODES) | set(INTERNAL_MODES) == set(_ENGINES)
+# engine name (ctx.eng_name: a saved node re-wraps its activations through the engine that ran its forward) -> engine
+_ENGINE_BY_NAME = {e.name: e for e in (
+    _F32Engine(),
+    #          name         forward   gradient
+    _NLCEngine("bf16",      "bf16",   "bf16"),
+    _NLCEngine("bf16x3",    "bf16x3", "bf16x3"),
+    _NLCEngine("f16mx",     "f16mx",  "f16mx"),
+    _NLCEngine("f16mx_hb",  "f16mx",  "f16"),       # "half" backward: one fp16 MFMA per product, under the loss scale
+    _NLCEngine("bf16x3_hb", "bf16x3", "bf16"),      # ... one bf16 MFMA (fp32 range: no loss scale)
+    _NLCEngine("f16dec",    "f16",    "f16"))}      # the f16mx_hd decoder: fp16 activations too
+# mode -> {role: engine}; None = every role the mode does not name ("decoder" is the only one a module asks for)
+_MODE_ENGINES = {m: {None: _ENGINE_BY_NAME[m]} for m in ("f32", "bf16", "bf16x3", "f16mx", "f16mx_hb", "bf16x3_hb")}
+_MODE_ENGINES["x3mx_hb"] = {None: _ENGINE_BY_NAME["bf16x3_hb"], "decoder": _ENGINE_BY_NAME["f16mx_hb"]}
+_MODE_ENGINES["f16mx_hd"] = {None: _ENGINE_BY_NAME["f16mx_hb"], "decoder": _ENGINE_BY_NAME["f16dec"]}
 
 
 def _engine(name=None, role=None):
     """The engine of the current mode (or, in a backward, the one that ran the node's forward); ``role`` lets a mode give
     one part of the model its own arithmetic."""
     if name is not None:
-        return _ENGINES_BY_NAME[name]()
-    return _ROLE_ENGINES.get((_DTYPE, role), _ENGINES[_DTYPE])()
+        return _ENGINE_BY_NAME[name]
+    roles = _MODE_ENGINES[_DTYPE]
+    return roles.get(role, roles[None])
 
 
 _ACT_TAP = None     # analysis hook (tests/analysis/gate_flips.py): a list that receives (engine name, saved activations) per node
@@ -672,7 +598,7 @@ def _stack_backward(eng, dh, ts, us, w1, w2, R, outer=None):
     if w1.requires_grad != w2.requires_grad:
         raise RuntimeError("the two weights of the shared Residual must be frozen or trainable together")
     train = w1.requires_grad
-    fused = train and getattr(eng, "wgrad_multi", None) is not None and 1 < R <= 4
+    fused = train and eng.wgrad_multi is not None and 1 < R <= 4
     pairs1, pairs2 = [], []
     for r in range(R - 1, -1, -1):
         du = eng.conv(dh, w2, IOK, mask=us[r])                                 # k1 data-grad, * (u_r > 0)
@@ -685,10 +611,8 @@ def _stack_backward(eng, dh, ts, us, w1, w2, R, outer=None):
         dh = eng.conv(du, w1, IOK, skip1=dh, skip2=outer if r == 0 else None, mask=ts[r])
     if fused:
         s1, s2 = _sink(w1), _sink(w2)
-        d2 = {"defer": _DEFERRED} if (_DEFERRED is not None and s2 is not None and getattr(eng, "can_defer", False)) else {}
-        d1 = {"defer": _DEFERRED} if (_DEFERRED is not None and s1 is not None and getattr(eng, "can_defer", False)) else {}
-        dw2 = eng.wgrad_multi(pairs2, 1, OIK, dw_out=s2, accumulate=s2 is not None, **d2)
-        dw1 = eng.wgrad_multi(pairs1, 3, OIK, dw_out=s1, accumulate=s1 is not None, **d1)
+        dw2 = eng.wgrad_multi(pairs2, 1, OIK, dw_out=s2, accumulate=s2 is not None, **_defer_kw(eng, s2))
+        dw1 = eng.wgrad_multi(pairs1, 3, OIK, dw_out=s1, accumulate=s1 is not None, **_defer_kw(eng, s1))
         dw1, dw2 = (None if s1 is not None else dw1), (None if s2 is not None else dw2)
     return dh, dw1, dw2
 

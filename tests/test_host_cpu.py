@@ -214,3 +214,84 @@ def test_package_default_mode_is_the_parity_holding_fast_mode():
             "_ops.set_compute_dtype('f16mx', internal=True)\nprint(_ops.get_compute_dtype())")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.split() == ["f16mx"], out.stdout + out.stderr
+
+
+def test_format_and_mode_tables_say_what_the_modes_compute():
+    """The arithmetic of every mode, pinned as data: which engine (forward format, gradient format) runs which role, and per
+    activation format the C symbols a launch calls.  The format flags decide which trailing arguments the launch code
+    appends, so each row must agree with the argument count of its own symbols -- a row paired with a neighbour's symbol is
+    caught here, not on the GPU."""
+    from acoustic_locating_vq_vae import _native as N
+    from acoustic_locating_vq_vae import _ops
+    # engine name -> (forward format, gradient format); mode -> role -> (engine name, forward, gradient)
+    engines = {"f32": (None, None), "bf16": ("bf16", "bf16"), "bf16x3": ("bf16x3", "bf16x3"), "f16mx": ("f16mx", "f16mx"),
+               "f16mx_hb": ("f16mx", "f16"), "bf16x3_hb": ("bf16x3", "bf16")}
+    expect = {m: {None: (m,) + engines[m], "decoder": (m,) + engines[m]} for m in engines}
+    expect["x3mx_hb"] = {None: ("bf16x3_hb", "bf16x3", "bf16"), "decoder": ("f16mx_hb", "f16mx", "f16")}
+    expect["f16mx_hd"] = {None: ("f16mx_hb", "f16mx", "f16"), "decoder": ("f16dec", "f16", "f16")}
+    assert set(expect) == set(_ops.MODES) | set(_ops.INTERNAL_MODES) and len(expect) == 8
+    before = _ops.get_compute_dtype()
+    try:
+        for mode, roles in expect.items():
+            _ops.set_compute_dtype(mode, internal=True)
+            for role, (name, fwd, grad) in roles.items():
+                eng = _ops._engine(role=role)
+                got = (eng.name,) + tuple(f if f is None else f.name for f in (eng.fwd, eng.grad))
+                assert got == (name, fwd, grad), (mode, role, got)
+                assert _ops._engine(name) is eng                  # a saved node finds the engine that ran its forward
+            assert _ops.has_fp16_range(mode) == (mode in ("x3mx_hb", "f16mx_hb", "f16mx", "f16mx_hd")), mode
+            assert _ops.has_fp16_range() == _ops.has_fp16_range(mode)
+    finally:
+        _ops.set_compute_dtype(before, internal=True)
+    for eng, kind in ((_ops._engine("f32"), (False, None)), (_ops._engine("bf16"), (True, N.conv1d_wgrad_bf16_multi))):
+        assert (eng.can_defer, eng.wgrad_multi) == kind
+
+    #            planes bits  scaled defer wcode wreads  operands            rows_code
+    flags = {"bf16":   (1, True,  False, True,  1, (1, 2), ("bf16", "bf16x3"), 1),
+             "bf16x3": (2, False, False, False, 2, (2,),   ("bf16x3",),        2),
+             "f16mx":  (2, True,  True,  False, 3, (3,),   ("f16mx",),         3),
+             "f16":    (1, True,  True,  True,  3, (3,),   ("f16", "f16mx"),   None)}
+    symbols = {"bf16": dict(to_nlc="alvq_ncl_to_nlc_bf16", to_ncl="alvq_nlc_to_ncl_f32", relu="alvq_relu_mask_bf16",
+                            pack="alvq_pack_weight_bf16", conv="alvq_conv1d_bf16", wgrad="alvq_conv1d_wgrad_bf16",
+                            wgrad_multi="alvq_conv1d_wgrad_bf16_multi", wgrad_ws="alvq_conv1d_wgrad_bf16_workspace_bytes"),
+               "bf16x3": dict(to_nlc="alvq_ncl_to_nlc_bf16x3", to_ncl="alvq_nlc_to_ncl_bf16x3", relu="alvq_relu_mask_bf16x3",
+                              pack="alvq_pack_weight_bf16x3", conv="alvq_conv1d_bf16x3", wgrad="alvq_conv1d_wgrad_bf16x3",
+                              wgrad_multi="alvq_conv1d_wgrad_bf16x3_multi",
+                              wgrad_ws="alvq_conv1d_wgrad_bf16x3_workspace_bytes"),
+               "f16mx": dict(to_nlc="alvq_ncl_to_nlc_f16mx", to_ncl="alvq_nlc_to_ncl_f16mx", relu="alvq_relu_mask_f16mx",
+                             pack=None, conv="alvq_conv1d_f16mx", wgrad="alvq_conv1d_wgrad_f16mx",
+                             wgrad_multi="alvq_conv1d_wgrad_f16mx_multi", wgrad_ws="alvq_conv1d_wgrad_f16mx_workspace_bytes"),
+               "f16": dict(to_nlc="alvq_ncl_to_nlc_f16", to_ncl="alvq_nlc_to_ncl_f16", relu="alvq_relu_mask_bf16",
+                           pack=None, conv="alvq_conv1d_f16", wgrad="alvq_conv1d_wgrad_f16",
+                           wgrad_multi="alvq_conv1d_wgrad_f16_multi", wgrad_ws="alvq_conv1d_wgrad_bf16_workspace_bytes")}
+    assert set(N._FORMATS) == set(flags)
+    nargs = lambda symbol: len(N._SIGNATURES[symbol][1])
+    for name, f in N._FORMATS.items():
+        assert (f.name, f.planes, f.bits, f.scaled, f.defer, f.wcode, f.wreads, f.operands, f.rows_code) == (name,) + flags[name]
+        for field, symbol in symbols[name].items():
+            assert getattr(f, field) == symbol, (name, field)
+            assert symbol is None or symbol in N.EXPORTS, symbol
+        # the trailing arguments the launch code appends, against each symbol's own signature
+        assert nargs(f.conv) == 17 + 2 * f.bits + f.scaled, name           # + (mask_bits, bits_out) + out_scale
+        assert nargs(f.wgrad) == nargs(f.wgrad_multi) == 13 + f.scaled, name
+        assert nargs(f.to_nlc) == nargs(f.to_ncl) == 6 + f.scaled, name     # + the loss scale S / 1/S
+        assert nargs(f.relu) == (5 if f.relu_flat else 7), name             # (dy, t, out, n | B, C, L, stream)
+        assert nargs(f.wgrad_ws) == 5 and (f.pack is None or nargs(f.pack) == 7)
+        assert N._PACKERS[f.wcode] == f.pack and f.wcode in f.wreads
+        # the KernelTimer families bench.py keys its roofline on (the bf16 / f16 ones ask the library which kernel it picks)
+        if name in ("bf16x3", "f16mx"):
+            assert f.conv_family(1, 3, 768, 4096) == "conv1d_%s_kernel<1, 3, ...>" % name
+            assert f.wgrad_family(3, False) == "conv1d_wgrad_%s_kernel" % name
+    assert [nargs(N._FORMATS[n].conv) for n in ("bf16", "bf16x3", "f16mx", "f16")] == [19, 17, 20, 20]
+    assert [nargs(N._FORMATS[n].wgrad) for n in ("bf16", "bf16x3", "f16mx", "f16")] == [13, 13, 14, 14]
+
+    # the operand rule: f16 accepts f16mx, bf16 accepts bf16x3, nothing else crosses
+    class T:
+        def __init__(self, fmt):
+            self.fmt, self.planes = fmt, N._FORMATS[fmt].planes
+    crossing = {(t, ref) for t in flags for ref in flags if t != ref and N._fmt_serves(T(t), T(ref))}
+    assert crossing == {("f16mx", "f16"), ("bf16x3", "bf16")}
+    assert all(N._fmt_serves(T(n), T(n)) for n in flags)
+    with pytest.raises(ValueError):
+        N._format(1, "f16mx")                                               # the door refuses a contradicting pair
+    assert [N._format(p, None).name for p in (1, 2)] == ["bf16", "bf16x3"]
