@@ -25,6 +25,20 @@ def update(cs, W, c, s, decay, eps):
     return cs, W, W / cs[:, None]
 
 
+def update_rounded(cs, W, c, s, decay, eps):
+    """Steps 1-5 with the roundings the header states: fp64 arithmetic on the fp32 state, the cluster size rounded to fp32
+    once (after the smoothing), the moving sum rounded once, and the codebook the fp32 quotient of the two stored values.
+    -> (cs, W, E), all fp32."""
+    cs = np.asarray(cs, dtype=np.float32).astype(np.float64)
+    W = np.asarray(W, dtype=np.float32).astype(np.float64)
+    K = cs.shape[0]
+    cs = decay * cs + (1.0 - decay) * np.asarray(c, dtype=np.float32).astype(np.float64)
+    n = cs.sum()
+    cs32 = ((cs + eps) / (n + K * eps) * n).astype(np.float32)
+    W32 = (decay * W + (1.0 - decay) * np.asarray(s, dtype=np.float32).astype(np.float64)).astype(np.float32)
+    return cs32, W32, (W32 / cs32[:, None]).astype(np.float32)
+
+
 def step(cs, W, rows, idx, decay, eps):
     c, s = stats(rows, idx, np.asarray(cs).shape[0])
     return update(cs, W, c, s, decay, eps)
