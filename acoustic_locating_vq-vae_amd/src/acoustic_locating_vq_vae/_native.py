@@ -138,6 +138,8 @@ _SIGNATURES = {
     "alvq_vq_ema_stats_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "alvq_vq_ema_stats_f32": (_i32, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p]),
     "alvq_vq_ema_update_f32": (_i32, [_c_void_p] * 6 + [_i32, _i32, ctypes.c_double, ctypes.c_double, _c_void_p]),
+    "alvq_vq_restart_gather_f32": (_i32, [_c_void_p] * 4 + [_i64, _i32, _i32, _i32, _i32, _c_void_p]),
+    "alvq_vq_restart_dead_f32": (_i32, [_c_void_p] * 6 + [_i32, _i32, _i32, _f32, _c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -466,6 +468,36 @@ def vq_ema_update(counts, sums, cluster_size, ema_w, codebook, decay, epsilon, s
                                         _ptr(cluster_size, name="cluster_size"), _ptr(ema_w, name="ema_w"),
                                         _ptr(codebook, name="codebook"), _ptr(skip, name="skip"), K, D, float(decay),
                                         float(epsilon), _stream()), "alvq_vq_ema_update_f32")
+
+
+def vq_restart_gather(flat, rows, cand, status, first=0, stride=1):
+    """cand[s] = flat[rows[s // stride]] for the slots s % stride == first (alvq_vq_restart_gather_f32); the other slots are
+    left as they are.  ``status``: device int32[1]; bit 1 is raised by a position outside [0, N) (its slot is zeroed)."""
+    N, D = flat.shape
+    R = cand.shape[0]
+    if cand.shape != (R, D) or status.numel() != 1:
+        raise RuntimeError("vq_restart_gather: cand must be (R, %d) and status one int32" % D)
+    if not 0 <= first < stride or rows.numel() < len(range(first, R, stride)):
+        raise RuntimeError("vq_restart_gather: first=%d, stride=%d need 0 <= first < stride and %d positions (got %d)"
+                           % (first, stride, len(range(first, R, stride)), rows.numel()))
+    _check(lib().alvq_vq_restart_gather_f32(_ptr(flat, name="x"), _ptr(rows, torch.int64, "rows"), _ptr(cand, name="cand"),
+                                            _ptr(status, torch.int32, "status"), N, D, R, int(first), int(stride), _stream()),
+           "alvq_vq_restart_gather_f32")
+
+
+def vq_restart_dead(cand, cluster_size, ema_w, codebook, counters, threshold, skip=None):
+    """Move the first R = cand.shape[0] codes whose cluster size is below ``threshold`` onto the candidate rows, in place
+    (alvq_vq_restart_dead_f32); ``counters``: device int64[2] = (restarts so far, dead codes of this step); ``skip``: the
+    Trainer's skip slot (non-zero: nothing is written, the counters included)."""
+    K, D = codebook.shape
+    R = cand.shape[0]
+    if cluster_size.numel() != K or ema_w.shape != (K, D) or cand.shape != (R, D) or counters.numel() != 2:
+        raise RuntimeError("vq_restart_dead: cluster_size must be (%d,), ema_w (%d, %d), cand (R, %d) and counters int64[2]"
+                           % (K, K, D, D))
+    _check(lib().alvq_vq_restart_dead_f32(_ptr(cand, name="cand"), _ptr(cluster_size, name="cluster_size"),
+                                          _ptr(ema_w, name="ema_w"), _ptr(codebook, name="codebook"), _ptr(skip, name="skip"),
+                                          _ptr(counters, torch.int64, "counters"), K, D, R, float(threshold), _stream()),
+           "alvq_vq_restart_dead_f32")
 
 
 def vq_backward(g, grad_loss, flat, codebook, idx, beta, want_dx=True, want_dE=True, dE_out=None):

@@ -882,10 +882,12 @@ _EMA_SINKS = None
 
 class EMASink:
     """The statistics buffers of one quantiser in a Trainer; ``world``: ranks whose rows are summed into them; ``written``:
-    the last forward under the sink filled them."""
+    the last forward under the sink filled them.  With dead-code restarts on, ``cand`` (R, D) is the candidate span and
+    ``rank`` this process's place among the ``world``: its forward fills the slots s % world == rank."""
 
-    def __init__(self, counts, sums, world):
+    def __init__(self, counts, sums, world, rank=0, cand=None):
         self.counts, self.sums, self.world, self.written = counts, sums, world, False
+        self.rank, self.cand = rank, cand
 
 
 class use_ema_sinks:

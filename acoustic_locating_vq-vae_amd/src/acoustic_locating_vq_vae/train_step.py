@@ -50,7 +50,8 @@ class FlatBuffers:
 
     ``extra``: floats of a non-parameter span appended to both buffers (``extra_span`` = [lo, hi)).  Its gradient-buffer side
     travels with the step's all-reduce and is zeroed with the gradients; no parameter points into it and the optimiser
-    leaves it alone (the Trainer passes it in the skip list): the EMA quantisers' per-code statistics."""
+    leaves it alone (the Trainer passes it in the skip list): the EMA quantisers' per-code statistics and, with dead-code
+    restarts on, their candidate rows."""
 
     def __init__(self, params, extra=0):
         self.params = unique_trainable(params)
@@ -297,6 +298,11 @@ class Trainer:
         self._ema = [m for m in model.modules() if isinstance(m, VectorQuantizerEMA)] if kind != "echoed" else []
         ema_lens = [(m._num_embeddings + _ALIGN - 1) // _ALIGN * _ALIGN + m._num_embeddings * m._embedding_dim
                     for m in self._ema]
+        # dead-code restarts: R candidate rows more per quantiser that has them on (rank r fills the slots s % world == r in
+        # its forward, the all-reduce adds the other ranks' zeros: every rank ends with the same R rows)
+        self._restart = [m for m in self._ema if m.restarts_enabled()]
+        ema_lens = [(n + _ALIGN - 1) // _ALIGN * _ALIGN + m._restart_candidates * m._embedding_dim if m.restarts_enabled() else n
+                    for m, n in zip(self._ema, ema_lens)]
         self.buffers = FlatBuffers(params, extra=sum(ema_lens))
         self._trainable = [p.requires_grad for p in self.buffers.params]
         if self.buffers.flat.is_cuda:
@@ -308,6 +314,7 @@ class Trainer:
         self.buffers.broadcast_params(group=group)
         self.opt = FlatAdam(self.buffers, lr=lr, guard=os.environ.get("ALVQ_SKIP_SATURATED", "1") != "0")
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
+        rank = dist.get_rank(group) if world > 1 else 0
         self.grad_scale = 1.0 / world
         self._ema_sinks = {}
         off = self.buffers.extra_span[0] if self._ema else 0
@@ -316,6 +323,12 @@ class Trainer:
             kp = (K + _ALIGN - 1) // _ALIGN * _ALIGN
             self._ema_sinks[id(m)] = _ops.EMASink(self.buffers.grad[off:off + K], self.buffers.grad[off + kp:off + kp + K * D].view(K, D),
                                                   world)
+            if m.restarts_enabled():
+                co = off + kp + (K * D + _ALIGN - 1) // _ALIGN * _ALIGN
+                sink = self._ema_sinks[id(m)]
+                sink.rank, sink.cand = rank, self.buffers.grad[co:co + m._restart_candidates * D].view(m._restart_candidates, D)
+                if world > 1:                                  # the ranks draw different positions
+                    m._restart_gen.manual_seed(m._restart_seed + rank)
             off += n
         self._broadcast_ema()
         self._graph = None
@@ -334,7 +347,7 @@ class Trainer:
                 self._buckets = (self.buffers.span(early), self.buffers.span(late))
                 xs = self.buffers.extra_span
                 if xs is not None and not any(lo <= xs[0] and xs[1] <= hi for lo, hi in self._buckets):
-                    raise RuntimeError("the EMA statistics span is not inside one gradient bucket")
+                    raise RuntimeError("the EMA statistics span (restart candidates included) is not inside one gradient bucket")
         self._cut = None
 
     def preprocess(self, raw, wiener=None):
@@ -452,6 +465,14 @@ class Trainer:
             if sink.written:                                   # (a replay repeats what its capture wrote)
                 N.vq_ema_update(sink.counts, sink.sums, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data, m._decay,
                                 m._epsilon, skip=skip)
+                if sink.cand is not None:                      # dead-code restarts, from the candidates every rank now holds
+                    N.vq_restart_dead(sink.cand, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data,
+                                      m._restart_counters, m._dead_code_threshold, skip=skip)
+
+    def restarted_codes(self):
+        """``VectorQuantizerEMA.restarted_codes()`` of every EMA quantiser of the model, in module order: a list of
+        (codes restarted so far, dead codes of the last step); (0, 0) for one without restarts.  One host sync each."""
+        return [m.restarted_codes() for m in self._ema]
 
     def _broadcast_ema(self):
         """Rank 0's EMA state (cluster sizes, moving-average sums, codebook) to every rank of the group."""
@@ -467,9 +488,12 @@ class Trainer:
         """Everything a resumed run needs beyond ``model.state_dict()``: the Adam moments (flat, in parameter order)
         and the step count.  The reference only ever saves the model (``torch.save(model, ...)``), so its resumed
         runs restart Adam from zero; with this a resumed step is bitwise the step that would have come next."""
-        return {"model": self.model.state_dict(), "exp_avg": self.opt.exp_avg.clone(), "exp_avg_sq": self.opt.exp_avg_sq.clone(),
-                "step": self.opt.applied_steps(),                 # steps APPLIED (a skipped step does not count)
-                "numel": self.buffers.flat.numel(), "kind": self.kind}
+        state = {"model": self.model.state_dict(), "exp_avg": self.opt.exp_avg.clone(), "exp_avg_sq": self.opt.exp_avg_sq.clone(),
+                 "step": self.opt.applied_steps(),                # steps APPLIED (a skipped step does not count)
+                 "numel": self.buffers.flat.numel(), "kind": self.kind}
+        if self._restart:                                         # this rank's restart-position generators (no key when off)
+            state["restart_rng"] = [m._restart_gen.get_state() for m in self._restart]
+        return state
 
     def load_state_dict(self, state):
         if state["numel"] != self.buffers.flat.numel() or state["kind"] != self.kind:
@@ -478,6 +502,12 @@ class Trainer:
         self.opt.exp_avg.copy_(state["exp_avg"])
         self.opt.exp_avg_sq.copy_(state["exp_avg_sq"])
         self.opt.set_step(state["step"])
+        if self._restart:
+            if len(state.get("restart_rng", ())) != len(self._restart):
+                raise ValueError("checkpoint carries no restart generator state for this trainer's %d quantiser(s)"
+                                 % len(self._restart))
+            for m, g in zip(self._restart, state["restart_rng"]):
+                m._restart_gen.set_state(g.cpu())
 
     def _jitters(self):
         from .vq_vae.modules.jitter import Jitter
@@ -535,7 +565,7 @@ class Trainer:
                 for j in self._graph_jitters:
                     j.refresh()
             self.opt.prepare(self.grad_scale)
-            out = self._body(raw, wiener)
+            out = self._body(raw, wiener)                       # (an eager forward draws its own restart positions)
             early = self._sync_early()
             self._body_late()
             self._finish(early)
@@ -546,6 +576,9 @@ class Trainer:
             self._static_wiener.copy_(wiener, non_blocking=True)
         for j in self._graph_jitters:
             j.refresh()
+        for m, (rows, n) in zip(self._restart, self._graph_restart):
+            m.draw_restart_rows(rows, n)               # the draw the captured forward left out: eager and replayed runs
+            #                                            take the same stream from the private generator
         self.opt.prepare(self.grad_scale)
         self._graph.replay()
         early = self._sync_early()
@@ -560,7 +593,9 @@ class Trainer:
 
         ``raw_batches``: one raw batch or an iterable of them (``wiener_batches`` alongside for kind="rir").  The codebook
         is written in place (the flat buffer's slice, so an already captured graph replays against it), and its slice of
-        the Adam moments is zeroed (an EMA quantiser's codebook has none; its moving averages are set as well).  Nothing else caches the codebook: the quantiser recomputes its norms on every call and
+        the Adam moments is zeroed (an EMA quantiser's codebook has none; its moving averages are set as well: the fit sets
+        the cluster sizes to the mean label counts per batch -- ``ConvolutionalVQVAE.init_codebook`` -- so a model with
+        dead-code restarts on does not restart freshly initialised codes that won rows).  Nothing else caches the codebook: the quantiser recomputes its norms on every call and
         no packed image of it exists.  Under data parallelism rank 0 fits on its own batches and broadcasts the codebook,
         so every rank ends with the same one."""
         if self.kind == "echoed":
@@ -646,4 +681,7 @@ class Trainer:
             with torch.cuda.graph(graph_late, pool=graph.pool(), capture_error_mode=mode):
                 self._body_late()
         self._graph, self._graph_late = graph, graph_late
+        # restart positions: (rows of the captured forward, positions this rank supplies) per quantiser
+        self._graph_restart = [(m._restart_nrows, len(range(self._ema_sinks[id(m)].rank, m._restart_candidates,
+                                                            self._ema_sinks[id(m)].world))) for m in self._restart]
         return self

@@ -24,18 +24,32 @@ class ConvolutionalVQVAE(nn.Module):
     def __init__(self, in_channels: int, num_hiddens: int, embedding_dim: int, num_residual_layers: int,
                  num_residual_hiddens: int, commitment_cost: float, num_embeddings: int, use_jitter: bool = True,
                  encoder_average_pooling: bool = False, out_channels: int = None, decay: float = 0.0,
-                 epsilon: float = 1e-5):
+                 epsilon: float = 1e-5, dead_code_threshold: float = 0.0, restart_candidates: int = 64,
+                 restart_seed: int = 0):
         """``decay`` > 0 (typically 0.99): the codebook follows exponential moving averages (``VectorQuantizerEMA(...,
-        decay, epsilon)``); 0 (the default): the reference's gradient-trained ``VectorQuantizer``."""
+        decay, epsilon)``); 0 (the default): the reference's gradient-trained ``VectorQuantizer``.
+        ``dead_code_threshold`` > 0 (needs ``decay`` > 0: the gradient-trained quantiser keeps no usage statistic): codes
+        whose moving-average cluster size falls below it are moved onto encoder rows of the current batch, at most
+        ``restart_candidates`` a step, at positions drawn from a private generator seeded with ``restart_seed``
+        (``VectorQuantizerEMA``'s docstring has the contract)."""
         out_channels = in_channels if out_channels is None else out_channels
         if decay != 0 and not 0.0 < decay < 1.0:
             raise ValueError("ConvolutionalVQVAE: decay must be 0 or lie in (0, 1), got %r" % (decay,))
+        if not dead_code_threshold >= 0.0:
+            raise ValueError("ConvolutionalVQVAE: dead_code_threshold must be >= 0, got %r" % (dead_code_threshold,))
+        if dead_code_threshold > 0.0 and decay == 0:
+            raise ValueError("ConvolutionalVQVAE: dead_code_threshold > 0 needs decay > 0 (the gradient-trained quantiser "
+                             "has no usage state)")
+        if dead_code_threshold > 0.0 and not 1 <= int(restart_candidates) <= num_embeddings:
+            raise ValueError("ConvolutionalVQVAE: restart_candidates must lie in [1, num_embeddings = %d], got %r"
+                             % (num_embeddings, restart_candidates))
         super().__init__()
         self.encoder_average_pooling = encoder_average_pooling
         self._encoder = ConvolutionalEncoder(in_channels, num_hiddens, num_residual_layers, num_residual_hiddens)
         self._pre_vq_conv = _init.kaiming_conv(nn.Conv1d(num_hiddens, embedding_dim, kernel_size=3, padding=1))
         if decay > 0:
-            self._vq = VectorQuantizerEMA(num_embeddings, embedding_dim, commitment_cost, decay, epsilon)
+            self._vq = VectorQuantizerEMA(num_embeddings, embedding_dim, commitment_cost, decay, epsilon, dead_code_threshold,
+                                          restart_candidates, restart_seed)
         else:
             self._vq = VectorQuantizer(num_embeddings, embedding_dim, commitment_cost)
         self._decoder = DeconvolutionalDecoder(embedding_dim, out_channels, num_hiddens, num_residual_layers,

@@ -357,6 +357,24 @@ int alvq_vq_ema_stats_f32(const float* x, const int64_t* idx, float* counts, flo
 int alvq_vq_ema_update_f32(const float* counts, const float* sums, float* cluster_size, float* ema_w, float* codebook,
                            const float* skip, int K, int D, double decay, double epsilon, void* stream);
 
+/* Dead-code restarts of the EMA codebook (VectorQuantizerEMA(dead_code_threshold > 0)), csrc/vq_restart.hip.
+ * Candidates: cand[s][:] = x[rows[s / stride]][:] for every slot s < R with s % stride == first (0 <= first < stride); the
+ * other slots are not written (under data parallelism rank r of W fills the slots s % W == r and the step's all-reduce adds
+ * zeros to them).  x (N, D) fp32, rows int64 with at least ceil((R - first) / stride) entries, cand (R, D) fp32.  A position
+ * outside [0, N) leaves its slot zero and raises bit 1 of *status (a device int the caller reads when it can sync).
+ * D <= 512, R <= 16384.  1 launch, no host sync. */
+int alvq_vq_restart_gather_f32(const float* x, const int64_t* rows, float* cand, int* status, int64_t N, int D, int R, int first,
+                               int stride, void* stream);
+
+/* The restart, after alvq_vq_ema_update_f32 and on the values it stored:  1. dead = the codes k with cluster_size[k] <
+ * threshold (fp32 compare), ascending;  2. n = min(#dead, R); for j < n and k = dead[j]: codebook[k] = cand[j], ema_w[k] =
+ * fl32(cand[j] * threshold), cluster_size[k] = threshold;  3. counters[0] += n, counters[1] = #dead (before the cap).
+ * Nothing else is written: copies and one fp32 product.  counters: device int64[2].  skip (nullable): a device float;
+ * non-zero leaves everything untouched, the counters included.  K <= 16384, D <= 512, 1 <= R <= K, threshold >= 0.
+ * 1 launch (one workgroup: the dead list stays in LDS), no workspace, no host sync. */
+int alvq_vq_restart_dead_f32(const float* cand, float* cluster_size, float* ema_w, float* codebook, const float* skip,
+                             int64_t* counters, int K, int D, int R, float threshold, void* stream);
+
 /* Greedy k-means++ (sklearn's _kmeans_plusplus): centre 0 = x[first]; closest_dist_sq in fp64; per round c >= 1, T
  * candidates r_t = uniforms[c-1][t] * current_pot found in the blocked fp64 inclusive cumsum of closest_dist_sq (first
  * entry >= r_t, clipped to N - 1), their fp64 distances to every row, min with closest_dist_sq, the candidate of least
