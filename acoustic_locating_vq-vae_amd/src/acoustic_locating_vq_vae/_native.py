@@ -140,6 +140,10 @@ _SIGNATURES = {
     "alvq_vq_ema_update_f32": (_i32, [_c_void_p] * 6 + [_i32, _i32, ctypes.c_double, ctypes.c_double, _c_void_p]),
     "alvq_vq_restart_gather_f32": (_i32, [_c_void_p] * 4 + [_i64, _i32, _i32, _i32, _i32, _c_void_p]),
     "alvq_vq_restart_dead_f32": (_i32, [_c_void_p] * 6 + [_i32, _i32, _i32, _f32, _c_void_p]),
+    "alvq_adam_advance_sched_f32": (_i32, [_c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_void_p,
+                                           _c_void_p, _i64, _i64, ctypes.c_double]),
+    "alvq_grad_clip_workspace_bytes": (_i64, [_i64]),
+    "alvq_grad_clip_f32": (_i32, [_c_void_p, _i64, _c_void_p, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -683,16 +687,55 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, scalars, beta1=0.9, beta2=0.
                                    float(beta1), float(beta2), float(eps), _ptr(skip, name="skip"), _stream()), "alvq_adam_dev_f32")
 
 
-ADAM_SCALARS = 8     # floats of the device state: {lr/bc1, sqrt(bc2), grad_scale, step, skipped steps, -, -, -}
+ADAM_SCALARS = 8     # floats of the device state: {lr/bc1, sqrt(bc2), grad_scale, step, skipped steps, grad norm, clip coef,
+#                      clipped steps} -- the last three are written by ``grad_clip`` only
+GRAD_CLIP_PARTIALS = 512   # workgroups of the norm's first pass; the workspace holds that many doubles plus the sum
 
 
-def adam_advance(scalars, lr, beta1=0.9, beta2=0.999, grad_scale=1.0, prev_skip=None):
+def adam_advance(scalars, lr, beta1=0.9, beta2=0.999, grad_scale=1.0, prev_skip=None, warmup_steps=None, total_steps=None,
+                 lr_min=0.0):
     """Device-side ``step += 1`` on the 8-float tensor ``scalars`` = {lr/bc1, sqrt(bc2), grad_scale, step, skipped, ...}.
-    ``prev_skip``: the skip slot still holding the previous step's verdict -- a skipped step does not count."""
+    ``prev_skip``: the skip slot still holding the previous step's verdict -- a skipped step does not count.
+    ``warmup_steps`` / ``total_steps`` / ``lr_min``: a schedule (include/alvq.h: alvq_adam_advance_sched_f32) -- linear warm-up
+    over ``warmup_steps`` applied steps, then cosine annealing to ``lr_min`` at ``total_steps`` (None: constant after the
+    warm-up).  Without them the call is the unscheduled entry point's, as before."""
     if scalars.numel() != ADAM_SCALARS:
         raise RuntimeError("adam_advance: scalars must hold %d floats" % ADAM_SCALARS)
-    _check(lib().alvq_adam_advance_f32(_ptr(scalars, name="scalars"), float(lr), float(beta1), float(beta2),
-                                       float(grad_scale), _ptr(prev_skip, name="prev_skip"), _stream()), "alvq_adam_advance_f32")
+    if warmup_steps is None and total_steps is None:
+        _check(lib().alvq_adam_advance_f32(_ptr(scalars, name="scalars"), float(lr), float(beta1), float(beta2),
+                                           float(grad_scale), _ptr(prev_skip, name="prev_skip"), _stream()), "alvq_adam_advance_f32")
+        return
+    _check(lib().alvq_adam_advance_sched_f32(_ptr(scalars, name="scalars"), float(lr), float(beta1), float(beta2),
+                                             float(grad_scale), _ptr(prev_skip, name="prev_skip"), _stream(),
+                                             int(warmup_steps or 0), int(total_steps or 0), float(lr_min)),
+           "alvq_adam_advance_sched_f32")
+
+
+def grad_clip_workspace(device):
+    """A workspace for ``grad_clip``: float64, GRAD_CLIP_PARTIALS partial sums and, last, their sum."""
+    nbytes = lib().alvq_grad_clip_workspace_bytes(1)
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def grad_clip(grad_span, scalars, max_norm, skip=None, workspace=None):
+    """Global-norm clipping as an update of ``scalars`` (between ``adam_advance`` and the Adam launches): with
+    norm = sqrt(sum(grad_span^2)) * scalars[2] and coef = min(1, max_norm / (norm + 1e-6)),
+    scalars[5] = norm, scalars[6] = coef, scalars[2] *= coef, scalars[7] += 1 if coef < 1.  Deterministic (a fixed grid, float64
+    partial sums added in index order).  ``max_norm`` = inf measures without clipping.  ``skip``: the skip slot; non-zero =
+    only the norm is written.  ``workspace``: a ``grad_clip_workspace`` tensor (its last element is left holding the float64
+    sum of squares); default: the stream's scratch."""
+    if scalars.numel() != ADAM_SCALARS:
+        raise RuntimeError("grad_clip: scalars must hold %d floats" % ADAM_SCALARS)
+    n = grad_span.numel()
+    if workspace is None:
+        workspace = _workspace(lib().alvq_grad_clip_workspace_bytes(max(n, 1)), grad_span.device)
+        ws = _ptr(workspace, torch.uint8)
+    else:
+        if workspace.numel() * workspace.element_size() < (GRAD_CLIP_PARTIALS + 1) * 8:
+            raise RuntimeError("grad_clip: workspace too small")
+        ws = _ptr(workspace, torch.float64, "workspace")
+    _check(lib().alvq_grad_clip_f32(_ptr(grad_span, name="grad_span"), n, _ptr(scalars, name="scalars"), float(max_norm), ws,
+                                    _ptr(skip, name="skip"), _stream()), "alvq_grad_clip_f32")
 
 
 def range_flag_to_slot(slot):

@@ -120,6 +120,38 @@ class FlatBuffers:
             dist.broadcast(self.flat, src=src, group=group)
 
 
+class WarmupCosine:
+    """Learning-rate schedule of ``FlatAdam``: linear warm-up ``lr * t / warmup_steps`` over the first ``warmup_steps`` APPLIED
+    steps (t is 1-based), then -- with ``total_steps`` -- cosine annealing from ``lr`` to ``lr_min`` at step ``total_steps``
+    (``lr_min`` from there on); without ``total_steps`` the rate stays at ``lr`` after the warm-up.  Evaluated on the device
+    from the applied-step counter (``_native.adam_advance``): a step the fp16-range guard skipped does not advance it and a
+    run resumed from ``state_dict`` lands on the same rate."""
+
+    __slots__ = ("warmup_steps", "total_steps", "lr_min")
+
+    def __init__(self, warmup_steps, total_steps=None, lr_min=0.0):
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError("WarmupCosine: warmup_steps=%r must be an integer >= 0" % (warmup_steps,))
+        if total_steps is not None and (int(total_steps) != total_steps or total_steps <= warmup_steps):
+            raise ValueError("WarmupCosine: total_steps=%r must be an integer beyond warmup_steps=%r" % (total_steps, warmup_steps))
+        if not lr_min >= 0:
+            raise ValueError("WarmupCosine: lr_min=%r must be >= 0" % (lr_min,))
+        self.warmup_steps = int(warmup_steps)
+        self.total_steps = None if total_steps is None else int(total_steps)
+        self.lr_min = float(lr_min)
+
+    def __repr__(self):
+        return "WarmupCosine(warmup_steps=%d, total_steps=%r, lr_min=%g)" % (self.warmup_steps, self.total_steps, self.lr_min)
+
+
+def _check_step_controls(max_grad_norm, schedule):
+    """The trainers' ``max_grad_norm`` / ``lr_schedule`` arguments: ValueError / TypeError before anything is built."""
+    if max_grad_norm is not None and not float(max_grad_norm) > 0:          # NaN fails the comparison too; inf passes
+        raise ValueError("max_grad_norm=%r must be > 0 (inf: measure the norm, never clip) or None" % (max_grad_norm,))
+    if schedule is not None and not isinstance(schedule, WarmupCosine):
+        raise TypeError("the learning-rate schedule must be a WarmupCosine or None (got %s)" % type(schedule).__name__)
+
+
 class FlatAdam:
     """Adam over FlatBuffers as HIP launches over the flat buffer.
 
@@ -128,9 +160,23 @@ class FlatAdam:
     staged through host memory, so a host that queues many steps ahead of the device (graph replay does) cannot
     overwrite a step's scalars before that step's Adam launch has read them."""
 
-    def __init__(self, buffers: FlatBuffers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, guard=False):
+    def __init__(self, buffers: FlatBuffers, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, guard=False, max_grad_norm=None,
+                 schedule=None):
         """``guard``: honour the buffers' skip slot -- a step whose slot is non-zero is not applied (parameters, moments,
-        packed images untouched), does not advance the step count and is counted in ``scalars[4]``."""
+        packed images untouched), does not advance the step count and is counted in ``scalars[4]``.
+
+        ``max_grad_norm``: clip the global 2-norm of the (mean over the ranks) gradient to it, as
+        ``torch.nn.utils.clip_grad_norm_`` between ``backward`` and ``Adam.step`` would: ``clip`` scales ``scalars[2]``, the
+        factor every Adam launch multiplies the gradient by, on the device.  ``inf`` measures the norm and never clips.
+        ``schedule``: a ``WarmupCosine``; ``prepare`` then derives ``scalars[0]`` from the scheduled rate.
+        Both are off by default, and a step then issues exactly the launches it issued without them."""
+        _check_step_controls(max_grad_norm, schedule)
+        if (max_grad_norm is not None or schedule is not None) and not buffers.flat.is_cuda:
+            raise NotImplementedError("max_grad_norm / schedule run on the GPU only (the flat buffers are on %s)"
+                                      % buffers.flat.device)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.schedule = schedule
+        self._clip_ws = None                                  # the norm's partial sums, made on first use
         self.b = buffers
         self.lr, self.betas, self.eps = lr, betas, eps
         self.guard = bool(guard) and buffers.flat.is_cuda
@@ -146,8 +192,40 @@ class FlatAdam:
 
     def prepare(self, grad_scale=1.0):
         self.step_count += 1
-        N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale,
-                       prev_skip=self.b.skip_slot if self.guard else None)
+        prev_skip = self.b.skip_slot if self.guard else None
+        if self.schedule is None:
+            N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale, prev_skip=prev_skip)
+        else:
+            N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale, prev_skip=prev_skip,
+                           warmup_steps=self.schedule.warmup_steps, total_steps=self.schedule.total_steps,
+                           lr_min=self.schedule.lr_min)
+
+    def clip(self, lo, hi):
+        """Global-norm clipping over grad[lo:hi) -- after the step's all-reduce, before ``apply``: two launches that scale
+        ``scalars[2]`` (``_native.grad_clip``).  Nothing at all without ``max_grad_norm``."""
+        if self.max_grad_norm is None:
+            return
+        if self._clip_ws is None:
+            self._clip_ws = N.grad_clip_workspace(self.b.grad.device)
+        N.grad_clip(self.b.grad[lo:hi], self.scalars, self.max_grad_norm, skip=self.b.skip_slot if self.guard else None,
+                    workspace=self._clip_ws)
+
+    def grad_norm(self):
+        """(norm, coef) of the last step's ``clip`` as floats (one host sync): the 2-norm of the mean gradient before
+        clipping and the factor it was scaled by (1.0 = not clipped)."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("grad_norm: the optimiser was built without max_grad_norm (inf measures without clipping)")
+        norm, coef = self.scalars[5:7].tolist()
+        return norm, coef
+
+    def clipped_steps(self, reset=True):
+        """Steps whose gradient was clipped (coef < 1) since the counter was last reset (one host sync)."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("clipped_steps: the optimiser was built without max_grad_norm")
+        n = int(self.scalars[7].item())
+        if reset and n:
+            self.scalars[7] = 0.0
+        return n
 
     def applied_steps(self):
         """Optimiser steps actually applied so far (one host sync): the device's step number minus the step in flight if the
@@ -223,15 +301,25 @@ class LocationTrainer:
     sample touched this step still decays its moments and moves by its first moment, exactly as in the reference loop.
     Per step: zero the 850 MB gradient buffer, forward / backward (a few MB), one pass over 4 x 850 MB."""
 
-    def __init__(self, location_model, lr=1e-3, group=None):
+    def __init__(self, location_model, lr=1e-3, group=None, max_grad_norm=None, lr_schedule=None):
+        """``max_grad_norm`` / ``lr_schedule``: as ``Trainer``'s."""
+        _check_step_controls(max_grad_norm, lr_schedule)
         self.model, self.group = location_model, group
         self.buffers = FlatBuffers(location_model.parameters())
         if self.buffers.flat.is_cuda:
             _ops.register_grad_sinks(self.buffers.params)
         self.buffers.broadcast_params(group=group)
-        self.opt = FlatAdam(self.buffers, lr=lr)
+        self.opt = FlatAdam(self.buffers, lr=lr, max_grad_norm=max_grad_norm, schedule=lr_schedule)
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         self.grad_scale = 1.0 / world
+
+    def grad_norm(self):
+        """``FlatAdam.grad_norm``: (norm, coef) of the last step.  One host sync."""
+        return self.opt.grad_norm()
+
+    def clipped_steps(self, reset=True):
+        """``FlatAdam.clipped_steps``.  One host sync."""
+        return self.opt.clipped_steps(reset)
 
     def step(self, codes, theta):
         """codes: (B, L) int indices (``get_latent_indices(...)[3].view(B, L)``) or the dense one-hot (B, L, K) the script
@@ -244,6 +332,7 @@ class LocationTrainer:
             loss = F.mse_loss(location, torch.as_tensor(theta).float().to(location.device) / torch.pi, reduction="mean")
             loss.backward()
         self.buffers.sync_grads(self.group)
+        self.opt.clip(_ALIGN, self.buffers.grad.numel())       # the parameters; the header holds the skip slot
         self.opt.apply()
         return loss.detach()
 
@@ -266,8 +355,14 @@ class Trainer:
     """
 
     def __init__(self, model, kind="speech", lr=1e-3, group=None, grad_buckets=None, force_collective=None,
-                 range_check_every=None, strict_range=None):
-        """``force_collective`` (or ALVQ_FORCE_COLLECTIVE=1): issue the step's all-reduce even in a one-rank process
+                 range_check_every=None, strict_range=None, max_grad_norm=None, lr_schedule=None):
+        """``max_grad_norm``: clip the global 2-norm of the step's gradient (the mean over the ranks, parameters only: the EMA
+        statistics span is not part of it) to this value before Adam, as ``torch.nn.utils.clip_grad_norm_`` would; ``inf``
+        measures the norm without clipping.  ``grad_norm()`` / ``clipped_steps()`` read the results back.
+        ``lr_schedule``: a ``WarmupCosine``.  Both live in the optimiser's device state, outside the captured graphs; without
+        them a step issues exactly the launches it issued before they existed.
+
+        ``force_collective`` (or ALVQ_FORCE_COLLECTIVE=1): issue the step's all-reduce even in a one-rank process
         group, where it is the identity -- so that the RCCL call between the backward and the Adam launch can be
         executed (and is tested, tests/test_rccl_gpu.py) on a single-GPU box.
 
@@ -277,6 +372,7 @@ class Trainer:
         (ALVQ_RANGE_CHECK_EVERY; default 200, 0 = never) the skipped-step counter and the sticky range flag are read back
         -- ONE host sync -- and reported: a RuntimeWarning, or with ``strict_range`` (ALVQ_RANGE_STRICT=1) a
         FloatingPointError when steps were skipped."""
+        _check_step_controls(max_grad_norm, lr_schedule)
         self.model, self.kind, self.group = model, kind, group
         self.range_check_every = int(os.environ.get("ALVQ_RANGE_CHECK_EVERY", "200")) if range_check_every is None \
             else int(range_check_every)
@@ -312,7 +408,8 @@ class Trainer:
         use_pool = self.buffers.flat.is_cuda and os.environ.get("ALVQ_PACK_POOL", "1") != "0"
         self.pack_pool = _ops.PackPool(list(model.parameters()), dynamic=self.buffers.params) if use_pool else None
         self.buffers.broadcast_params(group=group)
-        self.opt = FlatAdam(self.buffers, lr=lr, guard=os.environ.get("ALVQ_SKIP_SATURATED", "1") != "0")
+        self.opt = FlatAdam(self.buffers, lr=lr, guard=os.environ.get("ALVQ_SKIP_SATURATED", "1") != "0",
+                            max_grad_norm=max_grad_norm, schedule=lr_schedule)
         world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         rank = dist.get_rank(group) if world > 1 else 0
         self.grad_scale = 1.0 / world
@@ -455,6 +552,9 @@ class Trainer:
             for w in (early_work, late_work):
                 if w is not None:
                     w.wait()                                   # stream-level wait: the Adam launch queues behind both
+        if getattr(self.opt, "max_grad_norm", None) is not None:
+            xs = self.buffers.extra_span                       # the parameters' gradients only: not the header (skip slot),
+            self.opt.clip(_ALIGN, xs[0] if xs is not None else self.buffers.grad.numel())   # not the EMA statistics span
         if self.pack_pool is not None:                         # Adam + the re-pack of the conv weights' images in one launch
             self.opt.apply(self._adam_skip(), pack_pool=self.pack_pool)
         else:
@@ -468,6 +568,15 @@ class Trainer:
                 if sink.cand is not None:                      # dead-code restarts, from the candidates every rank now holds
                     N.vq_restart_dead(sink.cand, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data,
                                       m._restart_counters, m._dead_code_threshold, skip=skip)
+
+    def grad_norm(self):
+        """(norm, coef) of the last step (``max_grad_norm`` set): the global 2-norm of the gradient Adam was about to see --
+        the mean over the ranks, before clipping -- and the factor it was scaled by.  One host sync."""
+        return self.opt.grad_norm()
+
+    def clipped_steps(self, reset=True):
+        """Steps clipped (coef < 1) since the counter was last reset.  One host sync."""
+        return self.opt.clipped_steps(reset)
 
     def restarted_codes(self):
         """``VectorQuantizerEMA.restarted_codes()`` of every EMA quantiser of the model, in module order: a list of

@@ -199,6 +199,36 @@ int alvq_adam_advance_f32(float* scalars, double lr, double beta1, double beta2,
  * 0.0f.  The last launch of a step's backward; slot is element 0 of the flat gradient buffer. */
 int alvq_range_flag_to_slot(float* slot, void* stream);
 
+/* alvq_adam_advance_f32 with a learning-rate schedule: same counters, same skip rule, but scalars[0] is derived from the rate
+ * of the step t about to be applied (1-based, the APPLIED-step counter: a skipped step does not advance the schedule, a
+ * replayed graph needs no host value, a resumed run lands on the same rate):
+ *   t <= warmup_steps:                  lr_t = lr * t / warmup_steps                                   (linear warm-up)
+ *   else, total_steps > warmup_steps:   lr_t = lr_min + (lr - lr_min) * (1 + cos(pi * p)) / 2,
+ *                                       p = min(1, (t - warmup_steps) / (total_steps - warmup_steps))  (cosine annealing)
+ *   else (total_steps == 0):            lr_t = lr.
+ * All in double.  warmup_steps >= 0; total_steps == 0 or > warmup_steps; lr_min >= 0. */
+int alvq_adam_advance_sched_f32(float* scalars, double lr, double beta1, double beta2, double grad_scale,
+                                const float* prev_skip, void* stream, int64_t warmup_steps, int64_t total_steps, double lr_min);
+
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) as an update of the scalars above; slots 5-7
+ * are {norm, coef, clipped steps}.  Call it between alvq_adam_advance*_f32 (which sets scalars[2] = grad_scale) and the Adam
+ * launches (which read it).  grad: n floats (4-byte aligned; 16-byte aligned buffers are read with 16-byte loads -- the
+ * result does not depend on the alignment).  Two launches:
+ *   1. a FIXED grid of workgroups writes partial sums of grad^2 accumulated in float64 (squares of fp32 values are exact in
+ *      float64 and cannot overflow it);
+ *   2. one workgroup adds the partials in index order: S, and
+ *        norm = sqrt(S) * scalars[2]      -- the buffer is the sum over the ranks, scalars[2] = 1/world: the mean gradient's
+ *        coef = min(1, max_norm / (norm + 1e-6))          -- an infinite norm gives 0, NaN stays NaN, as in torch
+ *        scalars[5] = norm;  scalars[6] = coef;  scalars[2] *= (float)coef;  scalars[7] += 1 if coef < 1.
+ * No atomics and no arrival counter: the result is a function of the buffer's contents alone, bit for bit.
+ * max_norm > 0; +inf measures the norm and never clips (coef is exactly 1, scalars[2] keeps its bits).
+ * skip (nullable): the skip slot; non-zero = only scalars[5] is written and scalars[6] = 1.
+ * workspace: alvq_grad_clip_workspace_bytes(n) bytes, 8-byte aligned; on return its double at index
+ * (bytes / 8 - 1) holds S. */
+int64_t alvq_grad_clip_workspace_bytes(int64_t n);
+int alvq_grad_clip_f32(const float* grad, int64_t n, float* scalars, double max_norm, void* workspace, const float* skip,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * STFT power spectrogram (scripts/genereate_dataset.py:90-91,37,39,47-49; torchaudio Spectrogram semantics:
  * center=True reflect pad, periodic Hann(n_fft), one-sided, window-normalised, |.|^2).
