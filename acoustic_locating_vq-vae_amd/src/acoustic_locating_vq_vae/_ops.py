@@ -881,13 +881,41 @@ _EMA_SINKS = None
 
 
 class EMASink:
-    """The statistics buffers of one quantiser in a Trainer; ``world``: ranks whose rows are summed into them; ``written``:
-    the last forward under the sink filled them.  With dead-code restarts on, ``cand`` (R, D) is the candidate span and
-    ``rank`` this process's place among the ``world``: its forward fills the slots s % world == rank."""
+    """The statistics buffers of one quantiser, as views into a flat fp32 buffer (a Trainer's gradient buffer) from ``offset``:
+    ``counts`` (K,), padded to the flat buffers' granule; ``sums`` (K, D), padded; with dead-code restarts on ``cand`` (R, D),
+    the candidate rows (else None).  ``world``: ranks whose rows are summed into them; ``rank``: this process's place among
+    them -- its forward fills the ``slots`` candidate slots s % world == rank; ``written``: the last forward under the sink
+    filled it."""
 
-    def __init__(self, counts, sums, world, rank=0, cand=None):
-        self.counts, self.sums, self.world, self.written = counts, sums, world, False
-        self.rank, self.cand = rank, cand
+    @staticmethod
+    def _dims(module):
+        return module._num_embeddings, module._embedding_dim, module._restart_candidates if module.restarts_enabled() else 0
+
+    @classmethod
+    def span_len(cls, module):
+        """Floats of the span ``module`` needs (the last part is not padded)."""
+        from .train_step import _round_up
+        K, D, R = cls._dims(module)
+        return _round_up(K) + (_round_up(K * D) + R * D if R else K * D)
+
+    def __init__(self, module, grad, offset, rank=0, world=1):
+        from .train_step import _round_up
+        K, D, R = self._dims(module)
+        sums_at = offset + _round_up(K)
+        cand_at = sums_at + _round_up(K * D)
+        self.counts = grad[offset:offset + K]
+        self.sums = grad[sums_at:sums_at + K * D].view(K, D)
+        self.cand = grad[cand_at:cand_at + R * D].view(R, D) if R else None
+        self.rank, self.world, self.written = rank, world, False
+        self.slots = len(range(rank, R, world))
+
+    @classmethod
+    def local(cls, module, device):
+        """The one-rank sink of a quantiser outside a Trainer: fresh statistics, the candidates in the module's own buffer."""
+        sink = cls(module, torch.empty(cls.span_len(module), device=device, dtype=torch.float32), 0)
+        if sink.cand is not None:
+            sink.cand = module._restart_cand
+        return sink
 
 
 class use_ema_sinks:

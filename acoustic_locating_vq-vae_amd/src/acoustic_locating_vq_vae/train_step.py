@@ -31,6 +31,18 @@ from . import _ops
 _ALIGN = 64  # floats; keeps every parameter 256-byte aligned inside the flat buffer
 
 
+def _round_up(n):
+    """``n`` floats rounded up to the flat buffers' granule."""
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def _world_rank(group=None, without=(1, 0)):
+    """(world size, this process's rank) in ``group``; ``without`` when no process group is initialised."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return without
+    return dist.get_world_size(group), dist.get_rank(group)
+
+
 def unique_trainable(params):
     seen, out = set(), []
     for p in params:
@@ -63,9 +75,9 @@ class FlatBuffers:
             if p.device != dev or p.dtype != torch.float32:
                 raise ValueError("all parameters must be fp32 on one device")
             self.offsets.append(total)
-            total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            total += _round_up(p.numel())
         self.extra_span = (total, total + extra) if extra else None
-        total += (extra + _ALIGN - 1) // _ALIGN * _ALIGN
+        total += _round_up(extra)
         self.numel = sum(p.numel() for p in self.params)
         self.flat = torch.zeros(total, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -90,10 +102,8 @@ class FlatBuffers:
         """All-reduce(sum) of the whole flat gradient buffer, in place, as ONE collective.
         Returns the factor the optimiser must apply (1/world).  A one-rank group skips the call (the sum over one rank
         is the buffer itself) unless ``force`` -- the switch that lets a single-GPU box execute the RCCL path."""
-        if not (dist.is_available() and dist.is_initialized()):
-            return 1.0
-        world = dist.get_world_size(group)
-        if world == 1 and not force:
+        world = _world_rank(group, without=(0, 0))[0]          # 0: no process group, nothing to force
+        if world == 0 or (world == 1 and not force):
             return 1.0
         dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
         return 1.0 / world
@@ -111,12 +121,13 @@ class FlatBuffers:
     def sync_span(self, lo, hi, group=None, force=False):
         """Asynchronous all-reduce(sum) of grad[lo:hi); returns the work handle (None without a process group).  The
         caller ``wait()``s it -- a stream-level wait on the GPU -- before the optimiser reads the buffer."""
-        if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not force):
+        world = _world_rank(group, without=(0, 0))[0]
+        if world == 0 or (world == 1 and not force):
             return None
         return dist.all_reduce(self.grad[lo:hi], op=dist.ReduceOp.SUM, group=group, async_op=True)
 
     def broadcast_params(self, src=0, group=None):
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        if _world_rank(group)[0] > 1:
             dist.broadcast(self.flat, src=src, group=group)
 
 
@@ -185,6 +196,11 @@ class FlatAdam:
         self.step_count = 0                                   # steps ATTEMPTED on the host; scalars[3] = steps applied
         self.scalars = torch.zeros(N.ADAM_SCALARS, device=buffers.flat.device, dtype=torch.float32)
 
+    @property
+    def _skip(self):
+        """What every launch takes as its ``skip``: the buffers' skip slot under the guard, else None."""
+        return self.b.skip_slot if self.guard else None
+
     def set_step(self, step):
         """Resume from a checkpointed step count."""
         self.step_count = int(step)
@@ -192,13 +208,9 @@ class FlatAdam:
 
     def prepare(self, grad_scale=1.0):
         self.step_count += 1
-        prev_skip = self.b.skip_slot if self.guard else None
-        if self.schedule is None:
-            N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale, prev_skip=prev_skip)
-        else:
-            N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale, prev_skip=prev_skip,
-                           warmup_steps=self.schedule.warmup_steps, total_steps=self.schedule.total_steps,
-                           lr_min=self.schedule.lr_min)
+        s = self.schedule                                     # none: the unscheduled entry point
+        sched = {} if s is None else dict(warmup_steps=s.warmup_steps, total_steps=s.total_steps, lr_min=s.lr_min)
+        N.adam_advance(self.scalars, self.lr, self.betas[0], self.betas[1], grad_scale, prev_skip=self._skip, **sched)
 
     def clip(self, lo, hi):
         """Global-norm clipping over grad[lo:hi) -- after the step's all-reduce, before ``apply``: two launches that scale
@@ -207,8 +219,7 @@ class FlatAdam:
             return
         if self._clip_ws is None:
             self._clip_ws = N.grad_clip_workspace(self.b.grad.device)
-        N.grad_clip(self.b.grad[lo:hi], self.scalars, self.max_grad_norm, skip=self.b.skip_slot if self.guard else None,
-                    workspace=self._clip_ws)
+        N.grad_clip(self.b.grad[lo:hi], self.scalars, self.max_grad_norm, skip=self._skip, workspace=self._clip_ws)
 
     def grad_norm(self):
         """(norm, coef) of the last step's ``clip`` as floats (one host sync): the 2-norm of the mean gradient before
@@ -253,7 +264,6 @@ class FlatAdam:
         round 2 re-read every weight in a separate packing launch at the start of the next step), everything else --
         biases, the codebook -- by one segmented launch.  Same arithmetic, bit for bit."""
         groups = pack_pool.adam_groups() if (pack_pool is not None and os.environ.get("ALVQ_ADAM_PACK", "1") != "0") else None
-        skip_ptr = self.b.skip_slot if self.guard else None
         if groups:
             skipped = [(int(a), int(b)) for a, b in skip]
             by_planes, segments, fused = {}, [], set()
@@ -271,9 +281,9 @@ class FlatAdam:
                 else:
                     segments.append((off, off + n))
             for planes, entries in by_planes.items():       # one launch per weight format (per-role modes: two)
-                N.adam_pack_batch(entries, planes, self.scalars, self.betas[0], self.betas[1], self.eps, skip=skip_ptr)
+                N.adam_pack_batch(entries, planes, self.scalars, self.betas[0], self.betas[1], self.eps, skip=self._skip)
             N.adam_segments(self.b.flat, self.b.grad, self.exp_avg, self.exp_avg_sq, segments, self.scalars, self.betas[0],
-                            self.betas[1], self.eps, skip=skip_ptr)
+                            self.betas[1], self.eps, skip=self._skip)
             pack_pool.mark_adam_packed(fused)
             _ops.bump_weight_epoch()
             return
@@ -281,7 +291,7 @@ class FlatAdam:
         for s_lo, s_hi in sorted(skip) + [(self.b.flat.numel(), self.b.flat.numel())]:
             if s_lo > lo:
                 N.adam_step_dev(self.b.flat[lo:s_lo], self.b.grad[lo:s_lo], self.exp_avg[lo:s_lo],
-                                self.exp_avg_sq[lo:s_lo], self.scalars, self.betas[0], self.betas[1], self.eps, skip=skip_ptr)
+                                self.exp_avg_sq[lo:s_lo], self.scalars, self.betas[0], self.betas[1], self.eps, skip=self._skip)
             lo = max(lo, s_hi)
         if pack_pool is not None:
             pack_pool.forget_adam_marks()   # the images were NOT written by this update: every one is stale (round-3 advisor)
@@ -310,8 +320,7 @@ class LocationTrainer:
             _ops.register_grad_sinks(self.buffers.params)
         self.buffers.broadcast_params(group=group)
         self.opt = FlatAdam(self.buffers, lr=lr, max_grad_norm=max_grad_norm, schedule=lr_schedule)
-        world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-        self.grad_scale = 1.0 / world
+        self.grad_scale = 1.0 / _world_rank(group)[0]
 
     def grad_norm(self):
         """``FlatAdam.grad_norm``: (norm, coef) of the last step.  One host sync."""
@@ -387,20 +396,23 @@ class Trainer:
         # The caller's sub-models are left as they are (no requires_grad mutation).
         self._echoed_train_encoder = bool(getattr(model, "flag_train_encoder", False)) if kind == "echoed" else None
         params = model._decoder.parameters() if (kind == "echoed" and not self._echoed_train_encoder) else model.parameters()
-        # EMA quantisers (decay > 0): their forward writes the per-code statistics into a span at the end of the flat gradient
-        # buffer, which the step's all-reduce sums over the ranks; _finish applies the update.  The echoed loop's quantisers
-        # are frozen by the model (set_train_vq(False)) and are not updated.
+        # 1. the flat buffers, and at the end of the gradient buffer the EMA quantisers' (decay > 0) span: their forward writes
+        # the per-code statistics there and, with dead-code restarts on, R candidate rows (rank r fills the slots
+        # s % world == r, the other ranks add zeros); the step's all-reduce sums both over the ranks and _finish applies them.
+        # The echoed loop's quantisers are frozen by the model (set_train_vq(False)) and are not updated.
         from .vq_vae.vector_quantizer import VectorQuantizerEMA
         self._ema = [m for m in model.modules() if isinstance(m, VectorQuantizerEMA)] if kind != "echoed" else []
-        ema_lens = [(m._num_embeddings + _ALIGN - 1) // _ALIGN * _ALIGN + m._num_embeddings * m._embedding_dim
-                    for m in self._ema]
-        # dead-code restarts: R candidate rows more per quantiser that has them on (rank r fills the slots s % world == r in
-        # its forward, the all-reduce adds the other ranks' zeros: every rank ends with the same R rows)
         self._restart = [m for m in self._ema if m.restarts_enabled()]
-        ema_lens = [(n + _ALIGN - 1) // _ALIGN * _ALIGN + m._restart_candidates * m._embedding_dim if m.restarts_enabled() else n
-                    for m, n in zip(self._ema, ema_lens)]
-        self.buffers = FlatBuffers(params, extra=sum(ema_lens))
+        self.buffers = FlatBuffers(params, extra=sum(_ops.EMASink.span_len(m) for m in self._ema))
         self._trainable = [p.requires_grad for p in self.buffers.params]
+        world, rank = _world_rank(group)
+        self._ema_sinks, off = {}, self.buffers.extra_span[0] if self._ema else 0
+        for m in self._ema:
+            self._ema_sinks[id(m)] = _ops.EMASink(m, self.buffers.grad, off, rank, world)
+            off += _ops.EMASink.span_len(m)
+        if world > 1:                                         # the ranks draw different restart positions
+            for m in self._restart:
+                m._restart_gen.manual_seed(m._restart_seed + rank)
         if self.buffers.flat.is_cuda:
             _ops.register_grad_sinks(self.buffers.params)     # weight-grad launches accumulate straight into the flat buffer
         # every conv weight of the model (frozen sub-models of the echoed config included) keeps persistent packed
@@ -408,32 +420,17 @@ class Trainer:
         use_pool = self.buffers.flat.is_cuda and os.environ.get("ALVQ_PACK_POOL", "1") != "0"
         self.pack_pool = _ops.PackPool(list(model.parameters()), dynamic=self.buffers.params) if use_pool else None
         self.buffers.broadcast_params(group=group)
+        self._broadcast_ema()
+        # 2. the optimiser
         self.opt = FlatAdam(self.buffers, lr=lr, guard=os.environ.get("ALVQ_SKIP_SATURATED", "1") != "0",
                             max_grad_norm=max_grad_norm, schedule=lr_schedule)
-        world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
-        rank = dist.get_rank(group) if world > 1 else 0
         self.grad_scale = 1.0 / world
-        self._ema_sinks = {}
-        off = self.buffers.extra_span[0] if self._ema else 0
-        for m, n in zip(self._ema, ema_lens):
-            K, D = m._num_embeddings, m._embedding_dim
-            kp = (K + _ALIGN - 1) // _ALIGN * _ALIGN
-            self._ema_sinks[id(m)] = _ops.EMASink(self.buffers.grad[off:off + K], self.buffers.grad[off + kp:off + kp + K * D].view(K, D),
-                                                  world)
-            if m.restarts_enabled():
-                co = off + kp + (K * D + _ALIGN - 1) // _ALIGN * _ALIGN
-                sink = self._ema_sinks[id(m)]
-                sink.rank, sink.cand = rank, self.buffers.grad[co:co + m._restart_candidates * D].view(m._restart_candidates, D)
-                if world > 1:                                  # the ranks draw different positions
-                    m._restart_gen.manual_seed(m._restart_seed + rank)
-            off += n
-        self._broadcast_ema()
-        self._graph = None
-        # Two gradient buckets for the VQ-VAE loops: "late" = encoder + pre-VQ conv (a prefix of the flat buffer, its
+        self._one = None                                      # the backward's root gradient, made by the first step
+        # 3. two gradient buckets for the VQ-VAE loops: "late" = encoder + pre-VQ conv (a prefix of the flat buffer, its
         # gradients are produced last), "early" = quantiser + decoder.  The backward runs in two parts so the early
         # bucket's all-reduce overlaps the late part's kernels (see ``step``).  The echoed loop trains the decoder
         # only: one part, one bucket.
-        self._buckets = None
+        self._buckets = self._cut = self._graph = None
         want_buckets = int(os.environ.get("ALVQ_GRAD_BUCKETS", "1")) if grad_buckets is None else grad_buckets
         if want_buckets >= 2 and kind != "echoed" and hasattr(model, "_encoder") and hasattr(model, "_pre_vq_conv"):
             late = unique_trainable(list(model._encoder.parameters()) + list(model._pre_vq_conv.parameters()))
@@ -445,7 +442,6 @@ class Trainer:
                 xs = self.buffers.extra_span
                 if xs is not None and not any(lo <= xs[0] and xs[1] <= hi for lo, hi in self._buckets):
                     raise RuntimeError("the EMA statistics span (restart candidates included) is not inside one gradient bucket")
-        self._cut = None
 
     def preprocess(self, raw, wiener=None):
         if self.kind == "speech":
@@ -506,7 +502,7 @@ class Trainer:
             # partials behind and ONE launch sums them all once the backward has been queued
             x, target = self.preprocess(raw, wiener)
             self.buffers.zero_grad()
-            if getattr(self, "_one", None) is None or self._one.device != x.device:
+            if self._one is None or self._one.device != x.device:
                 self._one = torch.ones((), device=x.device)   # the backward's root gradient, made once (autograd would fill a
                 #                                               fresh ones_like(loss) every step: an ATen launch on the step path)
             if self._buckets is None:
@@ -526,7 +522,7 @@ class Trainer:
     def _post_verdict(self):
         """Last launch of the step's backward: did this step saturate an fp16-range format?  -> the skip slot, which the
         step's all-reduce then sums over the ranks (it is element 0 of the flat gradient buffer)."""
-        if getattr(self.opt, "guard", False) and _ops.has_fp16_range():
+        if self.opt.guard and _ops.has_fp16_range():
             N.range_flag_to_slot(self.buffers.skip_slot)
 
     def _body_late(self):
@@ -552,22 +548,17 @@ class Trainer:
             for w in (early_work, late_work):
                 if w is not None:
                     w.wait()                                   # stream-level wait: the Adam launch queues behind both
-        if getattr(self.opt, "max_grad_norm", None) is not None:
+        if self.opt.max_grad_norm is not None:
             xs = self.buffers.extra_span                       # the parameters' gradients only: not the header (skip slot),
             self.opt.clip(_ALIGN, xs[0] if xs is not None else self.buffers.grad.numel())   # not the EMA statistics span
         if self.pack_pool is not None:                         # Adam + the re-pack of the conv weights' images in one launch
             self.opt.apply(self._adam_skip(), pack_pool=self.pack_pool)
         else:
             self.opt.apply(self._adam_skip())                  # one Adam launch over the flat buffer
-        skip = self.buffers.skip_slot if getattr(self.opt, "guard", False) else None
-        for m in self._ema:                                    # the EMA codebooks, from the statistics summed over the ranks
-            sink = self._ema_sinks[id(m)]
+        for m in self._ema:                                    # the EMA codebooks and their dead-code restarts, from the
+            sink = self._ema_sinks[id(m)]                      # statistics and candidates every rank now holds
             if sink.written:                                   # (a replay repeats what its capture wrote)
-                N.vq_ema_update(sink.counts, sink.sums, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data, m._decay,
-                                m._epsilon, skip=skip)
-                if sink.cand is not None:                      # dead-code restarts, from the candidates every rank now holds
-                    N.vq_restart_dead(sink.cand, m._ema_cluster_size, m._ema_w.data, m._embedding.weight.data,
-                                      m._restart_counters, m._dead_code_threshold, skip=skip)
+                m.apply_update(sink, skip=self.opt._skip)
 
     def grad_norm(self):
         """(norm, coef) of the last step (``max_grad_norm`` set): the global 2-norm of the gradient Adam was about to see --
@@ -585,7 +576,7 @@ class Trainer:
 
     def _broadcast_ema(self):
         """Rank 0's EMA state (cluster sizes, moving-average sums, codebook) to every rank of the group."""
-        if not self._ema or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.group) == 1:
+        if not self._ema or _world_rank(self.group)[0] == 1:
             return
         src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
         for m in self._ema:
@@ -673,12 +664,7 @@ class Trainer:
                 # np.random stream one draw behind the reference's from here on (round-3 advisor finding)
                 for j in self._graph_jitters:
                     j.refresh()
-            self.opt.prepare(self.grad_scale)
-            out = self._body(raw, wiener)                       # (an eager forward draws its own restart positions)
-            early = self._sync_early()
-            self._body_late()
-            self._finish(early)
-            return out
+            return self._eager_step(raw, wiener)
         # replay: refresh the graphs' static inputs (batch, jitter columns, Adam scalars), then two launches
         self._static_raw.copy_(raw, non_blocking=True)
         if wiener is not None:
@@ -695,6 +681,15 @@ class Trainer:
             self._graph_late.replay()
         self._finish(early)
         return self._static_out
+
+    def _eager_step(self, raw, wiener):
+        """One whole step as eager launches (its forward draws its own restart positions)."""
+        self.opt.prepare(self.grad_scale)
+        out = self._body(raw, wiener)
+        early = self._sync_early()
+        self._body_late()
+        self._finish(early)
+        return out
 
     def init_codebook(self, raw_batches, wiener_batches=None, **kmeans_kwargs):
         """Initialise the model's codebook by k-means (``ConvolutionalVQVAE.init_codebook``) on raw batches preprocessed
@@ -717,9 +712,7 @@ class Trainer:
             wieners = [wiener_batches] if isinstance(wiener_batches, torch.Tensor) else list(wiener_batches)
         if self.kind == "rir" and (len(wieners) != len(raws) or any(w is None for w in wieners)):
             raise ValueError("init_codebook: kind='rir' needs one Wiener batch per raw batch")
-        world, rank = 1, 0
-        if dist.is_available() and dist.is_initialized():
-            world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        world, rank = _world_rank(self.group)
         weight = self.model._vq._embedding.weight
         km = None
         if rank == 0:
@@ -769,11 +762,7 @@ class Trainer:
             for _ in range(warmup):
                 for j in self._graph_jitters:
                     j.refresh()
-                self.opt.prepare(self.grad_scale)
-                self._body(self._static_raw, self._static_wiener)
-                early = self._sync_early()
-                self._body_late()
-                self._finish(early)
+                self._eager_step(self._static_raw, self._static_wiener)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         # capture_error_mode="thread_local": with a process group alive, ProcessGroupNCCL's watchdog THREAD polls the events
@@ -791,6 +780,5 @@ class Trainer:
                 self._body_late()
         self._graph, self._graph_late = graph, graph_late
         # restart positions: (rows of the captured forward, positions this rank supplies) per quantiser
-        self._graph_restart = [(m._restart_nrows, len(range(self._ema_sinks[id(m)].rank, m._restart_candidates,
-                                                            self._ema_sinks[id(m)].world))) for m in self._restart]
+        self._graph_restart = [(m._restart_nrows, self._ema_sinks[id(m)].slots) for m in self._restart]
         return self

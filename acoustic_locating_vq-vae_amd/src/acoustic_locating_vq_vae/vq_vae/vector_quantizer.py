@@ -148,19 +148,15 @@ class VectorQuantizerEMA(nn.Module):
             raise RuntimeError("VectorQuantizerEMA: a restart position lay outside the step's rows (status %d)" % status)
         return int(total), int(dead)
 
-    def _restart_candidates_from(self, inputs, rows, sink):
-        """Draw (unless a capture is recording) and gather this step's candidates: into the sink's span under a Trainer,
-        else into the module's own buffer."""
-        D = self._embedding_dim
-        rank, world = (sink.rank, sink.world) if sink is not None else (0, 1)
-        n = len(range(rank, self._restart_candidates, world))
-        self._restart_nrows = rows
-        if not torch.cuda.is_current_stream_capturing():
-            self.draw_restart_rows(rows, n)
-        flat = _ops.dense(inputs.detach()).view(-1, D)
-        cand = sink.cand if sink is not None else self._restart_cand
-        _native.vq_restart_gather(flat, self._restart_rows, cand, self._restart_status, first=rank, stride=world)
-        return cand
+    def apply_update(self, sink, skip=None):
+        """Apply a step's statistics: the EMA update from ``sink.counts`` / ``sink.sums``, then -- restarts on -- the dead
+        codes' restart from ``sink.cand``.  ``skip``: a Trainer's skip slot (non-zero: nothing is written)."""
+        weight = self._embedding.weight.data
+        _native.vq_ema_update(sink.counts, sink.sums, self._ema_cluster_size, self._ema_w.data, weight, self._decay,
+                              self._epsilon, skip=skip)
+        if sink.cand is not None:
+            _native.vq_restart_dead(sink.cand, self._ema_cluster_size, self._ema_w.data, weight, self._restart_counters,
+                                    self._dead_code_threshold, skip=skip)
 
     def quantize(self, inputs):
         """(loss, quantized_st, perplexity, indices[N] int64) without the dense one-hot; updates the state when training."""
@@ -175,30 +171,27 @@ class VectorQuantizerEMA(nn.Module):
         beta = float(self._commitment_cost)
         if not (self.training and self._train_vq):
             return _ops.VQEMAFn.apply(inputs, weight, beta, None)
+        # a Trainer's sink: statistics and candidates only, it applies the update after the all-reduce; else a sink of our own
         sink = _ops.ema_sink(self)
-        world = sink.world if sink is not None else 1
-        if rows * world >= 1 << 24:
+        local = sink is None
+        if local:
+            sink = _ops.EMASink.local(self, inputs.device)
+        if rows * sink.world >= 1 << 24:
             raise ValueError("VectorQuantizerEMA: %d rows per step (over %d rank(s)) >= 2^24: the counts travel as fp32"
-                             % (rows * world, world))
-        restart = self.restarts_enabled()
-        if restart and rows < len(range(sink.rank if sink is not None else 0, self._restart_candidates, world)):
+                             % (rows * sink.world, sink.world))
+        if rows < sink.slots:
             raise ValueError("VectorQuantizerEMA: %d rows on this rank, fewer than the restart candidates it must supply" % rows)
-        if sink is not None:                     # Trainer: statistics only; it applies the update after the all-reduce
-            out = _ops.VQEMAFn.apply(inputs, weight, beta, (sink.counts, sink.sums))
-            if restart:
-                self._restart_candidates_from(inputs, rows, sink)
-            sink.written = True
-            return out
-        counts = torch.empty((K,), device=inputs.device, dtype=torch.float32)
-        sums = torch.empty((K, D), device=inputs.device, dtype=torch.float32)
-        # the backward needs the codebook this forward quantised with: quantise with a copy, then update in place
-        out = _ops.VQEMAFn.apply(inputs, weight.detach().clone(), beta, (counts, sums))
-        _native.vq_ema_update(counts, sums, self._ema_cluster_size, self._ema_w.data, weight.data, self._decay,
-                              self._epsilon)
-        if restart:
-            cand = self._restart_candidates_from(inputs, rows, None)
-            _native.vq_restart_dead(cand, self._ema_cluster_size, self._ema_w.data, weight.data, self._restart_counters,
-                                    self._dead_code_threshold)
+        # the backward needs the codebook this forward quantised with: updating at once, quantise with a copy
+        out = _ops.VQEMAFn.apply(inputs, weight.detach().clone() if local else weight, beta, (sink.counts, sink.sums))
+        if sink.cand is not None:                # restarts: draw (unless a capture is recording) and gather this rank's slots
+            self._restart_nrows = rows
+            if not torch.cuda.is_current_stream_capturing():
+                self.draw_restart_rows(rows, sink.slots)
+            _native.vq_restart_gather(_ops.dense(inputs.detach()).view(-1, D), self._restart_rows, sink.cand,
+                                      self._restart_status, first=sink.rank, stride=sink.world)
+        sink.written = True
+        if local:
+            self.apply_update(sink)
         return out
 
     def forward(self, inputs):

@@ -187,6 +187,8 @@ def _trainer_worker(rank, world, port, ret, buckets):
             return err + vq_loss, err, perp
 
     class SGD:                                            # stands in for the one-launch flat Adam
+        guard, max_grad_norm = False, None                # (its fp16-range guard and its clipping: off)
+
         def __init__(self, b):
             self.b, self.step_count = b, 0
 
