@@ -71,5 +71,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the same, read back from lane 0 (the form the float64 kernels of kmeans.hip and tsne.hip were written with)
+__device__ __forceinline__ double wave_sum_lane0(double v) { return __shfl(wave_sum(v), 0, 64); }
 
 }  // namespace alvq

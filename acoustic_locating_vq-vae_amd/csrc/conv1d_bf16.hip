@@ -24,6 +24,7 @@
 #include "alvq_common.h"
 #include "bf16_common.h"
 #include "conv1d_bf16_tile256.h"
+#include "nlc_host.h"
 
 namespace alvq {
 
@@ -217,8 +218,6 @@ __global__ __launch_bounds__(256) void relu_mask_bf16_kernel(const u16* dy, cons
 
 using namespace alvq;
 
-static inline int pad_to(int x, int q) { return (x + q - 1) / q * q; }
-
 extern "C" int64_t alvq_nlc_rows(int B, int L) { return (B <= 0 || L <= 0) ? -1 : (int64_t)pad_to(1 + B * (L + 1), NLC_ROW_PAD); }
 extern "C" int alvq_nlc_channels(int C) { return C <= 0 ? -1 : pad_to(C, TB_K); }
 extern "C" int alvq_nlc_guard_rows(void) { return GUARD_ROWS; }
@@ -233,22 +232,29 @@ extern "C" int alvq_pack_weight_bf16(const float* w, void* wp, int M, int C, int
   return alvq_pack_weights_bf16_batch(&d, 1, 1, stream);
 }
 
+// the layout conversions of the one-plane formats: F16 0 bf16, 1 fp16 (scale: device scalar or null)
+template <int F16>
+static int ncl_to_nlc_16bit(const char* who, const float* x, void* y, int B, int C, int L, const float* scale, void* stream) {
+  if (int rc = check_nlc_dims(who, x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(ncl_to_nlc_kernel<F16>, d.grid32(), dim3(256), 0, (hipStream_t)stream, x, (u16*)y, B, C, L, d.Cp, d.rows, scale);
+  return check_launch(who);
+}
+template <int F16>
+static int nlc_to_ncl_16bit(const char* who, const void* x, float* y, int B, int C, int L, const float* scale, void* stream) {
+  if (int rc = check_nlc_dims(who, x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(nlc_to_ncl_kernel<F16>, d.grid32(), dim3(256), 0, (hipStream_t)stream, (const u16*)x, y, B, C, L, d.Cp, d.rows,
+                     scale);
+  return check_launch(who);
+}
+
 extern "C" int alvq_ncl_to_nlc_bf16(const float* x, void* y, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_ncl_to_nlc_bf16: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_ncl_to_nlc_bf16: bad dims");
-  const int Cp = pad_to(C, TB_K), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(ncl_to_nlc_kernel<0>, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y, B, C,
-                     L, Cp, rows, (const float*)nullptr);
-  return check_launch("alvq_ncl_to_nlc_bf16");
+  return ncl_to_nlc_16bit<0>("alvq_ncl_to_nlc_bf16", x, y, B, C, L, nullptr, stream);
 }
 
 extern "C" int alvq_nlc_to_ncl_f32(const void* x, float* y, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_nlc_to_ncl_f32: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_nlc_to_ncl_f32: bad dims");
-  const int Cp = pad_to(C, TB_K), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(nlc_to_ncl_kernel<0>, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, (const u16*)x, y, B,
-                     C, L, Cp, rows, (const float*)nullptr);
-  return check_launch("alvq_nlc_to_ncl_f32");
+  return nlc_to_ncl_16bit<0>("alvq_nlc_to_ncl_f32", x, y, B, C, L, nullptr, stream);
 }
 
 extern "C" int alvq_relu_mask_bf16(const void* dy, const void* t, void* out, int64_t n, void* stream) {
@@ -261,25 +267,28 @@ extern "C" int alvq_relu_mask_bf16(const void* dy, const void* t, void* out, int
   return check_launch("alvq_relu_mask_bf16");
 }
 
+// conv1d_bf16_kernel<KW, OUT, F16> sits at b16_slot(KW, OUT, F16)
+static constexpr int b16_slot(int KW, int OUT, int F16) { return ((KW == 3) * 2 + OUT) * 2 + F16; }
+typedef KernelTable<void (*)(ConvBArgs), 8> B16Table;
+static B16Table b16_table() {
+  B16Table t;
+  for_values<1, 3>([&](auto kw) { for_values<0, 1>([&](auto out) { for_values<0, 1>([&](auto f16) {
+    t.put(b16_slot(kw, out, f16), conv1d_bf16_kernel<kw, out, f16>, LDS_BYTES);
+  }); }); });
+  return t;
+}
+
 // the 16-bit convolution behind alvq_conv1d_bf16 (elem 0) and alvq_conv1d_f16 (elem 1)
 static int conv1d_16bit(int elem, const float* out_scale, const void* x, const void* wp, const float* bias, const void* skip1,
                         const void* skip2, const void* mask, const void* post, void* y, void* y2, float* y_ncl, int B, int C, int M,
                         int L, int KW, int relu, const void* mask_bits, void* relu_bits_out, void* stream) {
   const char* const who = elem ? "alvq_conv1d_f16" : "alvq_conv1d_bf16";
-  ALVQ_REQUIRE(x && wp && (y || y_ncl), ALVQ_EINVAL, "%s: null x/wp/y", who);
-  ALVQ_REQUIRE(!(y && y_ncl), ALVQ_EINVAL, "%s: choose one of y (NLC) and y_ncl (NCL fp32)", who);
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "%s: bad dims", who);
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "%s: KW=%d (only 1 and 3)", who, KW);
-  ALVQ_REQUIRE((y2 == nullptr) == (post == nullptr), ALVQ_EINVAL, "%s: y2 and post go together", who);
-  ALVQ_REQUIRE(!y_ncl || (!skip1 && !skip2 && !mask && !post && !relu), ALVQ_EUNSUPPORTED,
-               "%s: the NCL fp32 epilogue fuses bias only", who);
-  ALVQ_REQUIRE((long)B * (L + 1) < (1L << 30), ALVQ_EUNSUPPORTED, "%s: problem too large", who);
+  if (int rc = check_conv_args(who, x, wp, skip1, skip2, mask, post, y, y2, y_ncl, B, C, M, L, KW, relu, mask_bits, relu_bits_out))
+    return rc;
   ConvBArgs a{(const u16*)x, (const u16*)wp, bias, (const u16*)skip1, (const u16*)skip2, (const u16*)mask, (const u16*)post,
               (u16*)y, (u16*)y2, y_ncl, B, L, pad_to(C, TB_K), M, pad_to(M, TB_K), pad_to(M, WP_ROWS), relu,
               (int)(alvq_nlc_rows(B, L) / TB_R), pad_to(M, TB_M) / TB_M, (const unsigned char*)mask_bits,
               (unsigned char*)relu_bits_out};
-  ALVQ_REQUIRE(!(mask && mask_bits), ALVQ_EINVAL, "%s: pass the mask as a tensor or as bits, not both", who);
-  ALVQ_REQUIRE(!y_ncl || (!mask_bits && !relu_bits_out), ALVQ_EUNSUPPORTED, "%s: sign bits go with the NLC output", who);
   hipStream_t s = (hipStream_t)stream;
   a.relu = relu ? 1 : 0;
   a.elem = elem;
@@ -297,34 +306,10 @@ static int conv1d_16bit(int elem, const float* out_scale, const void* x, const v
   const long min_tiles = option(OPT_WIDE_MIN_TILES);
   if (use_v2 && pad_to(M, 256) - M <= 32 && tiles256 >= min_tiles)
     return (KW == 3 && use_k3) ? conv1d_bf16_k3_launch(a, s) : conv1d_bf16_v2_launch(a, KW, s);
+  static const B16Table table = b16_table();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<3, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<3, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<3, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_kernel<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  }
-  const dim3 grid(a.rtiles * a.mtiles), block(256);
-  if (elem) {
-    if (KW == 3) {
-      if (y) hipLaunchKernelGGL((conv1d_bf16_kernel<3, 0, 1>), grid, block, LDS_BYTES, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16_kernel<3, 1, 1>), grid, block, LDS_BYTES, s, a);
-    } else {
-      if (y) hipLaunchKernelGGL((conv1d_bf16_kernel<1, 0, 1>), grid, block, LDS_BYTES, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16_kernel<1, 1, 1>), grid, block, LDS_BYTES, s, a);
-    }
-  } else if (KW == 3) {
-    if (y) hipLaunchKernelGGL((conv1d_bf16_kernel<3, 0>), grid, block, LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((conv1d_bf16_kernel<3, 1>), grid, block, LDS_BYTES, s, a);
-  } else {
-    if (y) hipLaunchKernelGGL((conv1d_bf16_kernel<1, 0>), grid, block, LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((conv1d_bf16_kernel<1, 1>), grid, block, LDS_BYTES, s, a);
-  }
-  return check_launch("alvq_conv1d_bf16");
+  if (attr.need()) table.raise_lds_limit();
+  return table.launch(b16_slot(KW, y ? 0 : 1, elem ? 1 : 0), dim3(a.rtiles * a.mtiles), dim3(256), s, who, a);
 }
 
 extern "C" int alvq_conv1d_bf16(const void* x, const void* wp, const float* bias, const void* skip1, const void* skip2,
@@ -343,85 +328,64 @@ extern "C" int alvq_conv1d_f16(const void* x, const void* wp, const float* bias,
 }
 
 extern "C" int alvq_ncl_to_nlc_f16(const float* x, void* y, int B, int C, int L, const float* scale, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_ncl_to_nlc_f16: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_ncl_to_nlc_f16: bad dims");
-  const int Cp = pad_to(C, TB_K), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(ncl_to_nlc_kernel<1>, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y, B, C, L, Cp,
-                     rows, scale);
-  return check_launch("alvq_ncl_to_nlc_f16");
+  return ncl_to_nlc_16bit<1>("alvq_ncl_to_nlc_f16", x, y, B, C, L, scale, stream);
 }
 
 extern "C" int alvq_nlc_to_ncl_f16(const void* x, float* y, int B, int C, int L, const float* scale, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_nlc_to_ncl_f16: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_nlc_to_ncl_f16: bad dims");
-  const int Cp = pad_to(C, TB_K), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(nlc_to_ncl_kernel<1>, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, (const u16*)x, y, B, C, L,
-                     Cp, rows, scale);
-  return check_launch("alvq_nlc_to_ncl_f16");
+  return nlc_to_ncl_16bit<1>("alvq_nlc_to_ncl_f16", x, y, B, C, L, scale, stream);
 }
 
 // workspace = the split partials of the weight gradient, then 64 * pad64(M) floats of bias-gradient partials
 static int64_t wgrad_bias_offset(int rows, int C, int M, int KW) { return conv1d_wgrad_bf16_v2_workspace_bytes(rows, C, M, KW); }
 
 extern "C" int64_t alvq_conv1d_wgrad_bf16_workspace_bytes(int B, int C, int M, int L, int KW) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3)) return -1;
+  if (!wgrad_shape_ok(B, C, M, L, KW)) return -1;
   return wgrad_bias_offset((int)alvq_nlc_rows(B, L), C, M, KW) + (int64_t)64 * pad_to(M, TB_K) * 4;
 }
 
 extern "C" int64_t alvq_conv1d_wgrad_bf16_bias_offset(int B, int C, int M, int L, int KW) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3)) return -1;
+  if (!wgrad_shape_ok(B, C, M, L, KW)) return -1;
   return wgrad_bias_offset((int)alvq_nlc_rows(B, L), C, M, KW);
 }
 
 extern "C" int alvq_conv1d_wgrad_bf16_splits(int B, int C, int M, int L, int KW, int nseg, int with_bias) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3) || nseg < 1 || nseg > 4) return -1;
+  if (!wgrad_shape_ok(B, C, M, L, KW) || nseg < 1 || nseg > WGRAD_MAXSEG) return -1;
   return conv1d_wgrad_bf16_v2_splits((int)alvq_nlc_rows(B, L), C, M, KW, nseg, with_bias != 0);
+}
+
+// the weight gradient behind the four bf16 / fp16 exports (elem 0 / 1); the single forms carry the bias gradient, which
+// rides in the same launch (column sums of dY by an all-ones MFMA operand).  These families can defer their reduction.
+static int wgrad_16bit(const char* who, int elem, const void* const* dy, const void* const* x, int nseg, bool multi, float* dw,
+                       float* dbias, void* workspace, int B, int C, int M, int L, int KW, int w_layout, int accumulate,
+                       const float* inv_scale, void* stream) {
+  if (int rc = check_wgrad_args(who, dy, x, nseg, multi, dw, workspace, B, C, M, L, KW, w_layout, accumulate, true)) return rc;
+  const int rows = (int)alvq_nlc_rows(B, L);
+  float* const bias_partial = multi ? nullptr : (float*)((char*)workspace + wgrad_bias_offset(rows, C, M, KW));
+  return conv1d_wgrad_bf16_v2_launch(dy, x, nseg, dw, workspace, rows, C, M, KW, w_layout, accumulate, (hipStream_t)stream, dbias,
+                                     bias_partial, elem, inv_scale);
 }
 
 extern "C" int alvq_conv1d_wgrad_bf16(const void* dy, const void* x, float* dw, float* dbias, void* workspace, int B, int C,
                                       int M, int L, int KW, int w_layout, int accumulate, void* stream) {
-  ALVQ_REQUIRE(dy && x && (dw || accumulate == ALVQ_WGRAD_DEFER) && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16: w_layout");
-  const int rows = (int)alvq_nlc_rows(B, L);
-  // the bias gradient rides in the same launch (column sums of dY by an all-ones MFMA operand)
-  return conv1d_wgrad_bf16_v2_launch(&dy, &x, 1, dw, workspace, rows, C, M, KW, w_layout, accumulate, (hipStream_t)stream,
-                                     dbias, (float*)((char*)workspace + wgrad_bias_offset(rows, C, M, KW)));
+  return wgrad_16bit("alvq_conv1d_wgrad_bf16", 0, &dy, &x, 1, false, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate,
+                     nullptr, stream);
 }
 
 extern "C" int alvq_conv1d_wgrad_f16(const void* dy, const void* x, float* dw, float* dbias, void* workspace, int B, int C, int M,
                                      int L, int KW, int w_layout, int accumulate, const float* inv_scale, void* stream) {
-  ALVQ_REQUIRE(dy && x && (dw || accumulate == ALVQ_WGRAD_DEFER) && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16: w_layout");
-  const int rows = (int)alvq_nlc_rows(B, L);
-  return conv1d_wgrad_bf16_v2_launch(&dy, &x, 1, dw, workspace, rows, C, M, KW, w_layout, accumulate, (hipStream_t)stream, dbias,
-                                     (float*)((char*)workspace + wgrad_bias_offset(rows, C, M, KW)), 1, inv_scale);
+  return wgrad_16bit("alvq_conv1d_wgrad_f16", 1, &dy, &x, 1, false, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate,
+                     inv_scale, stream);
 }
 
 extern "C" int alvq_conv1d_wgrad_f16_multi(const void* const* dy, const void* const* x, int nseg, float* dw, void* workspace, int B,
                                            int C, int M, int L, int KW, int w_layout, int accumulate, const float* inv_scale,
                                            void* stream) {
-  ALVQ_REQUIRE(dy && x && (dw || accumulate == ALVQ_WGRAD_DEFER) && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16_multi: null pointer");
-  ALVQ_REQUIRE(nseg >= 1 && nseg <= 4, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16_multi: nseg=%d (1..4)", nseg);
-  for (int i = 0; i < nseg; ++i) ALVQ_REQUIRE(dy[i] && x[i], ALVQ_EINVAL, "alvq_conv1d_wgrad_f16_multi: null segment %d", i);
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16_multi: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16_multi: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16_multi: w_layout");
-  return conv1d_wgrad_bf16_v2_launch(dy, x, nseg, dw, workspace, (int)alvq_nlc_rows(B, L), C, M, KW, w_layout, accumulate,
-                                     (hipStream_t)stream, nullptr, nullptr, 1, inv_scale);
+  return wgrad_16bit("alvq_conv1d_wgrad_f16_multi", 1, dy, x, nseg, true, dw, nullptr, workspace, B, C, M, L, KW, w_layout,
+                     accumulate, inv_scale, stream);
 }
 
 extern "C" int alvq_conv1d_wgrad_bf16_multi(const void* const* dy, const void* const* x, int nseg, float* dw, void* workspace,
                                             int B, int C, int M, int L, int KW, int w_layout, int accumulate, void* stream) {
-  ALVQ_REQUIRE(dy && x && (dw || accumulate == ALVQ_WGRAD_DEFER) && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16_multi: null pointer");
-  ALVQ_REQUIRE(nseg >= 1 && nseg <= 4, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16_multi: nseg=%d (1..4)", nseg);
-  for (int i = 0; i < nseg; ++i) ALVQ_REQUIRE(dy[i] && x[i], ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16_multi: null segment %d", i);
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16_multi: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16_multi: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16_multi: w_layout");
-  return conv1d_wgrad_bf16_v2_launch(dy, x, nseg, dw, workspace, (int)alvq_nlc_rows(B, L), C, M, KW, w_layout, accumulate,
-                                     (hipStream_t)stream);
+  return wgrad_16bit("alvq_conv1d_wgrad_bf16_multi", 0, dy, x, nseg, true, dw, nullptr, workspace, B, C, M, L, KW, w_layout,
+                     accumulate, nullptr, stream);
 }

@@ -20,6 +20,7 @@
 #include "alvq_common.h"
 #include "bf16_common.h"
 #include "conv1d_bf16_tile256.h"
+#include "nlc_host.h"
 
 namespace alvq {
 
@@ -187,25 +188,22 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16_k3_kernel(ConvBArgs a) {
   tile256_epilogue<OUT, F16>(a, acc, lds, m0, r0, wave, tid, li, kq, wm0);
 }
 
+static constexpr int wide_slot(int OUT, int F16) { return OUT * 2 + F16; }
 int conv1d_bf16_k3_launch(const ConvBArgs& a_in, hipStream_t stream) {
   ConvBArgs a = a_in;
   const long rows = (long)a.rtiles * TB_R;     // caller computed rtiles in 128-row units; rows % 256 == 0
   a.rtiles = (int)(rows / V2_R);
   a.mtiles = (a.M + V2_M - 1) / V2_M;
+  static const auto table = [] {   // conv1d_bf16_k3_kernel<OUT, F16> sits at wide_slot(OUT, F16)
+    KernelTable<void (*)(ConvBArgs), 4> t;
+    for_values<0, 1>([&](auto out) { for_values<0, 1>([&](auto f16) {
+      t.put(wide_slot(out, f16), conv1d_bf16_k3_kernel<out, f16>, K3_LDS);
+    }); });
+    return t;
+  }();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_k3_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_k3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_k3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16_k3_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, K3_LDS);
-  }
-  const dim3 grid(a.rtiles * a.mtiles), block(512);
-  if (a.elem) {
-    if (a.y) hipLaunchKernelGGL((conv1d_bf16_k3_kernel<0, 1>), grid, block, K3_LDS, stream, a);
-    else hipLaunchKernelGGL((conv1d_bf16_k3_kernel<1, 1>), grid, block, K3_LDS, stream, a);
-  } else if (a.y) hipLaunchKernelGGL((conv1d_bf16_k3_kernel<0>), grid, block, K3_LDS, stream, a);
-  else hipLaunchKernelGGL((conv1d_bf16_k3_kernel<1>), grid, block, K3_LDS, stream, a);
-  return check_launch("alvq_conv1d_bf16(k3)");
+  if (attr.need()) table.raise_lds_limit();
+  return table.launch(wide_slot(a.y ? 0 : 1, a.elem ? 1 : 0), dim3(a.rtiles * a.mtiles), dim3(512), stream, "alvq_conv1d_bf16(k3)", a);
 }
 
 }  // namespace alvq

@@ -17,6 +17,7 @@
 
 #include "alvq_common.h"
 #include "bf16_common.h"
+#include "nlc_host.h"
 #include "wgrad_reduce.h"
 
 namespace alvq {
@@ -690,18 +691,14 @@ static constexpr int wgrad_x3_lds() {
   return 2 * (2 * 32 * 256 + 2 * (KW == 1 ? 32 : 36) * (4 * NCF * 16 * 2));
 }
 
-static int wgrad_x3_tiles(int C, int M, int KW) { return ((M + 127) / 128) * ((C + (KW == 3 ? 128 : 256) - 1) / (KW == 3 ? 128 : 256)); }
+// tile of a launch: 128 m x {128 c x 3 taps | 256 c}
+static WgradTile wgrad_x3_tile(int KW) { return {128, KW == 3 ? 128 : 256}; }
 
 constexpr int X3_BIAS_SPLITS = 64;     // upper bound of the split count (wgrad_split_plan)
 
 }  // namespace alvq
 
 using namespace alvq;
-
-static inline int pad_to(int x, int q) { return (x + q - 1) / q * q; }
-static inline long nlc_plane_elems(int B, int L, int C) {
-  return ((long)alvq_nlc_rows(B, L) + 2L * alvq_nlc_guard_rows()) * pad_to(C, 64);
-}
 
 extern "C" int64_t alvq_nlc_plane_bytes(int B, int L, int C) {
   return (B <= 0 || L <= 0 || C <= 0) ? -1 : nlc_plane_elems(B, L, C) * 2;
@@ -713,68 +710,56 @@ extern "C" int alvq_pack_weight_bf16x3(const float* w, void* wp, int M, int C, i
 }
 
 extern "C" int alvq_ncl_to_nlc_bf16x3(const float* x, void* y, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_ncl_to_nlc_bf16x3: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_ncl_to_nlc_bf16x3: bad dims");
-  const int Cp = pad_to(C, 64), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(ncl_to_nlc_x3_kernel, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y,
-                     nlc_plane_elems(B, L, C), B, C, L, Cp, rows);
+  if (int rc = check_nlc_dims("alvq_ncl_to_nlc_bf16x3", x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(ncl_to_nlc_x3_kernel, d.grid32(), dim3(256), 0, (hipStream_t)stream, x, (u16*)y, d.plane, B, C, L, d.Cp, d.rows);
   return check_launch("alvq_ncl_to_nlc_bf16x3");
 }
 
 extern "C" int alvq_nlc_to_ncl_bf16x3(const void* x, float* y, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_nlc_to_ncl_bf16x3: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_nlc_to_ncl_bf16x3: bad dims");
-  const int Cp = pad_to(C, 64), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(nlc_to_ncl_x3_kernel, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, (const u16*)x,
-                     nlc_plane_elems(B, L, C), y, B, C, L, Cp, rows);
+  if (int rc = check_nlc_dims("alvq_nlc_to_ncl_bf16x3", x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(nlc_to_ncl_x3_kernel, d.grid32(), dim3(256), 0, (hipStream_t)stream, (const u16*)x, d.plane, y, B, C, L, d.Cp,
+                     d.rows);
   return check_launch("alvq_nlc_to_ncl_bf16x3");
 }
 
 extern "C" int alvq_relu_mask_bf16x3(const void* dy, const void* t, void* out, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(dy && t && out, ALVQ_EINVAL, "alvq_relu_mask_bf16x3: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_relu_mask_bf16x3: bad dims");
-  const long n = (long)alvq_nlc_rows(B, L) * pad_to(C, 64);
+  if (int rc = check_nlc_dims("alvq_relu_mask_bf16x3", dy && t && out, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  const long n = (long)d.rows * d.Cp;
   long g = (n / 8 + 1023) / 1024;
   if (g > 2048) g = 2048;
   hipLaunchKernelGGL(relu_mask_x3_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const u16*)dy, (const u16*)t,
-                     (u16*)out, nlc_plane_elems(B, L, C) / 8, n / 8);
+                     (u16*)out, d.plane / 8, n / 8);
   return check_launch("alvq_relu_mask_bf16x3");
+}
+
+// conv1d_bf16x3_kernel<OUT, KW, NNI> sits at x3_slot(OUT, KW, NNI); NNI 1, 2, 4 (128 x 128, 256 x 128, 256 x 256 tiles) -> 0, 1, 2
+static constexpr int x3_slot(int OUT, int KW, int NNI) { return ((NNI >> 1) * 2 + OUT) * 2 + (KW == 3); }
+typedef KernelTable<void (*)(ConvX3Args), 12> X3Table;
+static X3Table x3_table() {
+  X3Table t;
+  for_values<1, 2, 4>([&](auto nni) { for_values<0, 1>([&](auto out) { for_values<1, 3>([&](auto kw) {
+    t.put(x3_slot(out, kw, nni), conv1d_bf16x3_kernel<out, kw, nni>, X3_LDS2);
+  }); }); });
+  return t;
 }
 
 extern "C" int alvq_conv1d_bf16x3(const void* x, const void* wp, const float* bias, const void* skip1, const void* skip2,
                                   const void* mask, const void* post, void* y, void* y2, float* y_ncl, int B, int C, int M,
                                   int L, int KW, int relu, void* stream) {
-  ALVQ_REQUIRE(x && wp && (y || y_ncl), ALVQ_EINVAL, "alvq_conv1d_bf16x3: null x/wp/y");
-  ALVQ_REQUIRE(!(y && y_ncl), ALVQ_EINVAL, "alvq_conv1d_bf16x3: choose one of y (NLC) and y_ncl (NCL fp32)");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_bf16x3: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_bf16x3: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE((y2 == nullptr) == (post == nullptr), ALVQ_EINVAL, "alvq_conv1d_bf16x3: y2 and post go together");
-  ALVQ_REQUIRE(!y_ncl || (!skip1 && !skip2 && !mask && !post && !relu), ALVQ_EUNSUPPORTED,
-               "alvq_conv1d_bf16x3: the NCL fp32 epilogue fuses bias only");
-  ALVQ_REQUIRE((long)B * (L + 1) < (1L << 30), ALVQ_EUNSUPPORTED, "alvq_conv1d_bf16x3: problem too large");
+  if (int rc = check_conv_args("alvq_conv1d_bf16x3", x, wp, skip1, skip2, mask, post, y, y2, y_ncl, B, C, M, L, KW, relu, nullptr,
+                               nullptr))
+    return rc;
   const long rows = alvq_nlc_rows(B, L);
   ConvX3Args a{{(const u16*)x, (const u16*)wp, bias, (const u16*)skip1, (const u16*)skip2, (const u16*)mask, (const u16*)post,
                 (u16*)y, (u16*)y2, y_ncl, B, L, pad_to(C, 64), M, pad_to(M, 64), pad_to(M, WP_ROWS), relu ? 1 : 0,
                 (int)(rows / X3_R), pad_to(M, X3_M) / X3_M},
                nlc_plane_elems(B, L, C), (long)alvq_packed_weight_elems(M, C, KW), nlc_plane_elems(B, L, M)};
-  hipStream_t s = (hipStream_t)stream;
+  static const X3Table table = x3_table();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-    (void)hipFuncSetAttribute((const void*)conv1d_bf16x3_kernel<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS2);
-  }
-  // fp32-NCL output of at most 128 channels (the pre-VQ convolution): 128-channel m-tile, no MFMA spent on padding channels
-  // (option "fx_narrow" = 0 switches it off here as in the f16mx kernel); results are bit-identical to the 256-wide tile's
+  if (attr.need()) table.raise_lds_limit();
   // 128-channel m-tile: outputs of at most 128 channels (no MFMA spent on padding channels), and problems whose 256 x 256
   // tiles would leave CUs idle (option "fx_narrow" = 0 switches it off here as in the f16mx kernel; "fx_rows" = 256 forces
   // the wide tile for the second case); results are bit-identical to the 256-wide tile's
@@ -784,71 +769,38 @@ extern "C" int alvq_conv1d_bf16x3(const void* x, const void* wp, const float* bi
   // still fewer than ~3/4 of the CUs covered: 128-row tiles as well
   const bool small = narrow && forced != 256 && (a.b.rtiles * a.b.mtiles < 192 || forced == 128);
   if (small) a.b.rtiles = (int)(rows / 128);
-  const dim3 grid(a.b.rtiles * a.b.mtiles), block(512);
-  if (small) {
-    if (y) {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 3, 1>), grid, block, X3_LDS2, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 1, 1>), grid, block, X3_LDS2, s, a);
-    } else {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 3, 1>), grid, block, X3_LDS2, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 1, 1>), grid, block, X3_LDS2, s, a);
-    }
-  } else if (narrow) {
-    if (y) {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 3, 2>), grid, block, X3_LDS2, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 1, 2>), grid, block, X3_LDS2, s, a);
-    } else {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 3, 2>), grid, block, X3_LDS2, s, a);
-      else hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 1, 2>), grid, block, X3_LDS2, s, a);
-    }
-  } else if (y) {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 3>), grid, block, X3_LDS2, s, a);
-    else hipLaunchKernelGGL((conv1d_bf16x3_kernel<0, 1>), grid, block, X3_LDS2, s, a);
-  } else {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 3>), grid, block, X3_LDS2, s, a);
-    else hipLaunchKernelGGL((conv1d_bf16x3_kernel<1, 1>), grid, block, X3_LDS2, s, a);
-  }
-  return check_launch("alvq_conv1d_bf16x3");
+  return table.launch(x3_slot(y ? 0 : 1, KW, small ? 1 : narrow ? 2 : 4), dim3(a.b.rtiles * a.b.mtiles), dim3(512),
+                      (hipStream_t)stream, "alvq_conv1d_bf16x3", a);
 }
 
 extern "C" int64_t alvq_conv1d_wgrad_bf16x3_workspace_bytes(int B, int C, int M, int L, int KW) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3)) return -1;
-  const int splits = wgrad_split_bound((int)alvq_nlc_rows(B, L), wgrad_x3_tiles(C, M, KW), WX_MAXSEG);
-  return (int64_t)splits * KW * M * C * 4 + (int64_t)X3_BIAS_SPLITS * pad_to(M, 64) * 4;
+  return wgrad_workspace_bytes(B, C, M, L, KW, wgrad_x3_tile(KW), X3_BIAS_SPLITS);
 }
 
-static int wgrad_x3_launch(const void* const* dy, const void* const* x, int nseg, float* dw, float* dbias, void* workspace, int B,
-                           int C, int M, int L, int KW, int w_layout, int accumulate, hipStream_t s) {
-  const int rows = (int)alvq_nlc_rows(B, L);
-  const int ct = KW == 3 ? 128 : 256;
+extern "C" int alvq_conv1d_wgrad_bf16x3_splits(int B, int C, int M, int L, int KW, int nseg) {
+  return wgrad_splits(B, C, M, L, KW, nseg, wgrad_x3_tile(KW));
+}
+
+// the weight gradient behind alvq_conv1d_wgrad_bf16x3 and its _multi form (no bias gradient there: dbias null)
+static int wgrad_x3(const char* who, const void* const* dy, const void* const* x, int nseg, bool multi, float* dw, float* dbias,
+                    void* workspace, int B, int C, int M, int L, int KW, int w_layout, int accumulate, hipStream_t s) {
+  if (int rc = check_wgrad_args(who, dy, x, nseg, multi, dw, workspace, B, C, M, L, KW, w_layout, accumulate, false)) return rc;
   WgradX3Args a{};
-  for (int i = 0; i < WX_MAXSEG; ++i) {
-    a.dy[i] = (const u16*)dy[i < nseg ? i : 0];
-    a.x[i] = (const u16*)x[i < nseg ? i : 0];
-  }
-  a.nseg = nseg;
-  a.partial = (float*)workspace;
-  a.bias_partial = nullptr;
-  a.dy_plane = nlc_plane_elems(B, L, M);
-  a.x_plane = nlc_plane_elems(B, L, C);
-  a.Mp = pad_to(M, 64); a.Cp = pad_to(C, 64); a.M = M; a.C = C;
-  a.mtiles = (M + 127) / 128; a.ctiles = (C + ct - 1) / ct;
-  a.total_rows = rows;
-  a.splits = wgrad_split_plan(nseg * rows, a.mtiles * a.ctiles, &a.chunks_per_split);
-  ALVQ_REQUIRE(a.mtiles * a.ctiles == wgrad_x3_tiles(C, M, KW) && a.splits <= wgrad_split_bound(rows, wgrad_x3_tiles(C, M, KW), WX_MAXSEG),
-               ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3: %d splits exceed what alvq_conv1d_wgrad_bf16x3_workspace_bytes sizes", a.splits);
-  float* bpart = (float*)((char*)workspace + (int64_t)a.splits * KW * M * C * 4);
+  float* bpart;
+  if (int rc = wgrad_plan("alvq_conv1d_wgrad_bf16x3", a, dy, x, nseg, workspace, B, C, M, L, KW, wgrad_x3_tile(KW), &bpart)) return rc;
   if (dbias) a.bias_partial = bpart;
+  // conv1d_wgrad_bf16x3_kernel<KW, NCF> sits at [KW == 3]
+  static const auto table = [] {
+    KernelTable<void (*)(WgradX3Args), 2> t;
+    for_values<1, 3>([&](auto kw) {
+      constexpr int NCF = kw == 3 ? 2 : 4;
+      t.put(kw == 3, conv1d_wgrad_bf16x3_kernel<kw, NCF>, wgrad_x3_lds<kw, NCF>());
+    });
+    return t;
+  }();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16x3_kernel<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_x3_lds<3, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16x3_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_x3_lds<1, 4>());
-  }
-  const int grid = a.mtiles * a.ctiles * a.splits;
-  if (KW == 3) hipLaunchKernelGGL((conv1d_wgrad_bf16x3_kernel<3, 2>), dim3(grid), dim3(512), (wgrad_x3_lds<3, 2>()), s, a);
-  else hipLaunchKernelGGL((conv1d_wgrad_bf16x3_kernel<1, 4>), dim3(grid), dim3(512), (wgrad_x3_lds<1, 4>()), s, a);
-  int rc = check_launch("alvq_conv1d_wgrad_bf16x3");
-  if (rc) return rc;
+  if (attr.need()) table.raise_lds_limit();
+  if (int rc = table.launch(KW == 3, dim3(a.mtiles * a.ctiles * a.splits), dim3(512), s, "alvq_conv1d_wgrad_bf16x3", a)) return rc;
   wgrad_reduce_launch((const float*)workspace, dw, a.splits, KW, M, C, w_layout, accumulate, s);
   if (dbias)     // single segment only (the shared residual weights have no bias)
     hipLaunchKernelGGL(wgrad_x3_bias_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const float*)bpart, dbias, a.splits,
@@ -856,28 +808,14 @@ static int wgrad_x3_launch(const void* const* dy, const void* const* x, int nseg
   return check_launch("alvq_conv1d_wgrad_bf16x3/reduce");
 }
 
-extern "C" int alvq_conv1d_wgrad_bf16x3_splits(int B, int C, int M, int L, int KW, int nseg) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3) || nseg < 1 || nseg > WX_MAXSEG) return -1;
-  int cps;
-  return wgrad_split_plan(nseg * (int)alvq_nlc_rows(B, L), wgrad_x3_tiles(C, M, KW), &cps);
-}
-
 extern "C" int alvq_conv1d_wgrad_bf16x3(const void* dy, const void* x, float* dw, float* dbias, void* workspace, int B, int C,
                                         int M, int L, int KW, int w_layout, int accumulate, void* stream) {
-  ALVQ_REQUIRE(dy && x && dw && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16x3: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3: w_layout");
-  return wgrad_x3_launch(&dy, &x, 1, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate, (hipStream_t)stream);
+  return wgrad_x3("alvq_conv1d_wgrad_bf16x3", &dy, &x, 1, false, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate,
+                  (hipStream_t)stream);
 }
 
 extern "C" int alvq_conv1d_wgrad_bf16x3_multi(const void* const* dy, const void* const* x, int nseg, float* dw, void* workspace,
                                               int B, int C, int M, int L, int KW, int w_layout, int accumulate, void* stream) {
-  ALVQ_REQUIRE(dy && x && dw && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3_multi: null pointer");
-  ALVQ_REQUIRE(nseg >= 1 && nseg <= WX_MAXSEG, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16x3_multi: nseg=%d (1..4)", nseg);
-  for (int i = 0; i < nseg; ++i) ALVQ_REQUIRE(dy[i] && x[i], ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3_multi: null segment %d", i);
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3_multi: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_bf16x3_multi: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16x3_multi: w_layout");
-  return wgrad_x3_launch(dy, x, nseg, dw, nullptr, workspace, B, C, M, L, KW, w_layout, accumulate, (hipStream_t)stream);
+  return wgrad_x3("alvq_conv1d_wgrad_bf16x3_multi", dy, x, nseg, true, dw, nullptr, workspace, B, C, M, L, KW, w_layout, accumulate,
+                  (hipStream_t)stream);
 }

@@ -14,6 +14,7 @@
 
 #include "alvq_common.h"
 #include "f16mx_common.h"
+#include "nlc_host.h"
 
 namespace alvq {
 
@@ -690,26 +691,19 @@ __global__ void grad_scale_kernel(float* state) {
 
 using namespace alvq;
 
-static inline int pad_to(int x, int q) { return (x + q - 1) / q * q; }
-static inline long nlc_plane_elems(int B, int L, int C) {
-  return ((long)alvq_nlc_rows(B, L) + 2L * alvq_nlc_guard_rows()) * pad_to(C, 64);
-}
-
 extern "C" int alvq_ncl_to_nlc_f16mx(const float* x, void* y, int B, int C, int L, const float* scale, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_ncl_to_nlc_f16mx: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_ncl_to_nlc_f16mx: bad dims");
-  const int Cp = pad_to(C, 64), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(ncl_to_nlc_fx_kernel, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, x, (u16*)y,
-                     nlc_plane_elems(B, L, C), B, C, L, Cp, rows, FX_E_ACT, scale);
+  if (int rc = check_nlc_dims("alvq_ncl_to_nlc_f16mx", x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(ncl_to_nlc_fx_kernel, d.grid32(), dim3(256), 0, (hipStream_t)stream, x, (u16*)y, d.plane, B, C, L, d.Cp, d.rows,
+                     FX_E_ACT, scale);
   return check_launch("alvq_ncl_to_nlc_f16mx");
 }
 
 extern "C" int alvq_nlc_to_ncl_f16mx(const void* x, float* y, int B, int C, int L, const float* scale, void* stream) {
-  ALVQ_REQUIRE(x && y, ALVQ_EINVAL, "alvq_nlc_to_ncl_f16mx: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_nlc_to_ncl_f16mx: bad dims");
-  const int Cp = pad_to(C, 64), rows = (int)alvq_nlc_rows(B, L);
-  hipLaunchKernelGGL(nlc_to_ncl_fx_kernel, dim3((rows / 32) * (Cp / 32)), dim3(256), 0, (hipStream_t)stream, (const u16*)x,
-                     nlc_plane_elems(B, L, C), y, B, C, L, Cp, rows, FX_E_ACT, scale);
+  if (int rc = check_nlc_dims("alvq_nlc_to_ncl_f16mx", x && y, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  hipLaunchKernelGGL(nlc_to_ncl_fx_kernel, d.grid32(), dim3(256), 0, (hipStream_t)stream, (const u16*)x, d.plane, y, B, C, L, d.Cp,
+                     d.rows, FX_E_ACT, scale);
   return check_launch("alvq_nlc_to_ncl_f16mx");
 }
 
@@ -720,13 +714,12 @@ extern "C" int alvq_f16mx_range_flag(int* out, int reset, void* stream) {
 }
 
 extern "C" int alvq_relu_mask_f16mx(const void* dy, const void* t, void* out, int B, int C, int L, void* stream) {
-  ALVQ_REQUIRE(dy && t && out, ALVQ_EINVAL, "alvq_relu_mask_f16mx: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && L > 0, ALVQ_EINVAL, "alvq_relu_mask_f16mx: bad dims");
-  const int Cp = pad_to(C, 64), rows = (int)alvq_nlc_rows(B, L);
-  long gq = ((long)rows * Cp / 16 + 255) / 256;
+  if (int rc = check_nlc_dims("alvq_relu_mask_f16mx", dy && t && out, B, C, L)) return rc;
+  const NlcDims d(B, C, L);
+  long gq = ((long)d.rows * d.Cp / 16 + 255) / 256;
   if (gq > 2048) gq = 2048;
   hipLaunchKernelGGL(relu_mask_fx_kernel, dim3((int)gq), dim3(256), 0, (hipStream_t)stream, (const u16*)dy, (const u16*)t, (u16*)out,
-                     nlc_plane_elems(B, L, C), rows, Cp);
+                     d.plane, d.rows, d.Cp);
   return check_launch("alvq_relu_mask_f16mx");
 }
 
@@ -742,19 +735,27 @@ extern "C" int alvq_grad_scale_f32(const float* x, int64_t n, float* state, void
   return check_launch("alvq_grad_scale_f32");
 }
 
+// conv1d_f16mx_kernel<OUT, KW, 0, NIN, MIN> sits at fx_slot(OUT, KW, NIN, MIN); (NIN, MIN) = (2, 4), (1, 4), (1, 2) -- the
+// 256-row tile, the 128-row tile, the 128-row x 128-channel tile -> 0, 1, 2.  The last exists for the fp32-NCL output only.
+static constexpr int fx_slot(int OUT, int KW, int NIN, int MIN) { return (((NIN == 1) + (MIN == 2)) * 2 + OUT) * 2 + (KW == 3); }
+typedef KernelTable<void (*)(ConvFxArgs), 12> FxTable;
+static FxTable fx_table() {
+  FxTable t;
+  for_values<1, 3>([&](auto kw) {
+    for_values<0, 1>([&](auto out) { for_values<2, 1>([&](auto nin) {
+      t.put(fx_slot(out, kw, nin, 4), conv1d_f16mx_kernel<out, kw, 0, nin, 4>, FX_LDS);
+    }); });
+    t.put(fx_slot(1, kw, 1, 2), conv1d_f16mx_kernel<1, kw, 0, 1, 2>, FX_LDS);
+  });
+  return t;
+}
+
 extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bias, const void* skip1, const void* skip2,
                                  const void* mask, const void* post, void* y, void* y2, float* y_ncl, int B, int C, int M, int L,
                                  int KW, int relu, const void* mask_bits, void* relu_bits_out, const float* out_scale, void* stream) {
-  ALVQ_REQUIRE(x && wp && (y || y_ncl), ALVQ_EINVAL, "alvq_conv1d_f16mx: null x/wp/y");
-  ALVQ_REQUIRE(!(y && y_ncl), ALVQ_EINVAL, "alvq_conv1d_f16mx: choose one of y (NLC) and y_ncl (NCL fp32)");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_f16mx: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_f16mx: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE((y2 == nullptr) == (post == nullptr), ALVQ_EINVAL, "alvq_conv1d_f16mx: y2 and post go together");
-  ALVQ_REQUIRE(!y_ncl || (!skip1 && !skip2 && !mask && !post && !relu), ALVQ_EUNSUPPORTED,
-               "alvq_conv1d_f16mx: the NCL fp32 epilogue fuses bias (and the output scale) only");
-  ALVQ_REQUIRE((long)B * (L + 1) < (1L << 30), ALVQ_EUNSUPPORTED, "alvq_conv1d_f16mx: problem too large");
-  ALVQ_REQUIRE(!(mask && mask_bits), ALVQ_EINVAL, "alvq_conv1d_f16mx: pass the mask as a tensor or as bits, not both");
-  ALVQ_REQUIRE(!y_ncl || (!mask_bits && !relu_bits_out), ALVQ_EUNSUPPORTED, "alvq_conv1d_f16mx: sign bits go with the NLC output");
+  if (int rc = check_conv_args("alvq_conv1d_f16mx", x, wp, skip1, skip2, mask, post, y, y2, y_ncl, B, C, M, L, KW, relu, mask_bits,
+                               relu_bits_out, " (and the output scale)"))
+    return rc;
   const long rows = alvq_nlc_rows(B, L);
   ConvFxArgs a{{(const u16*)x, (const u16*)wp, bias, (const u16*)skip1, (const u16*)skip2, (const u16*)mask, (const u16*)post,
                 (u16*)y, (u16*)y2, y_ncl, B, L, pad_to(C, 64), M, pad_to(M, 64), pad_to(M, WP_ROWS), relu ? 1 : 0,
@@ -769,18 +770,10 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
 #endif
   a.dbg = dbg_env;
   hipStream_t s = (hipStream_t)stream;
+  static const FxTable table = fx_table();
   static DeviceOnce attr;
   if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 3, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 3, 0, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<1, 1, 0, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
+    table.raise_lds_limit();
 #ifdef ALVQ_DEBUG_KERNELS
     (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
     (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
@@ -828,23 +821,5 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
     return check_launch("alvq_conv1d_f16mx(dbg)");
   }
 #endif
-  if (narrow) {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 3, 0, 1, 2>), grid, block, FX_LDS, s, a);
-    else hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 1, 0, 1, 2>), grid, block, FX_LDS, s, a);
-  } else if (half) {
-    if (y) {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 0, 1>), grid, block, FX_LDS, s, a);
-      else hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 1, 0, 1>), grid, block, FX_LDS, s, a);
-    } else {
-      if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 3, 0, 1>), grid, block, FX_LDS, s, a);
-      else hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 1, 0, 1>), grid, block, FX_LDS, s, a);
-    }
-  } else if (y) {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3>), grid, block, FX_LDS, s, a);
-    else hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 1>), grid, block, FX_LDS, s, a);
-  } else {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 3>), grid, block, FX_LDS, s, a);
-    else hipLaunchKernelGGL((conv1d_f16mx_kernel<1, 1>), grid, block, FX_LDS, s, a);
-  }
-  return check_launch("alvq_conv1d_f16mx");
+  return table.launch(fx_slot(y ? 0 : 1, KW, half ? 1 : 2, narrow ? 2 : 4), grid, block, s, "alvq_conv1d_f16mx", a);
 }

@@ -19,6 +19,7 @@
 
 #include "alvq_common.h"
 #include "bf16_common.h"
+#include "nlc_host.h"
 #include "wgrad_reduce.h"
 
 namespace alvq {
@@ -533,8 +534,21 @@ static bool wgrad_uses_v3(int KW, bool with_bias) {
 }
 // tiles of a launch: 128 m x {128 c x 3 taps | 256 c}; the v3 width-1 kernel owns 256 m x 256 c
 static int wgrad_v2_tiles(int C, int M, int KW, bool v3) {
-  const int ct = KW == 3 ? 128 : 256, mt = (v3 && KW == 1) ? 256 : 128;
-  return ((M + mt - 1) / mt) * ((C + ct - 1) / ct);
+  return WgradTile{(v3 && KW == 1) ? 256 : 128, KW == 3 ? 128 : 256}.count(C, M);
+}
+
+// conv1d_wgrad_bf16_v2_kernel<KW, NCF, F16> sits at wg_slot(0, KW, F16), conv1d_wgrad_bf16_v3_kernel<KW, NC, MF, F16> at
+// wg_slot(1, KW, F16); the fragment counts follow from the width
+static constexpr int wg_slot(int v3, int KW, int F16) { return (v3 * 2 + (KW == 3)) * 2 + F16; }
+typedef KernelTable<void (*)(WgradV2Args), 8> WgTable;
+static WgTable wg_table() {
+  WgTable t;
+  for_values<1, 3>([&](auto kw) { for_values<0, 1>([&](auto f16) {
+    constexpr int NCF = kw == 3 ? 2 : 4, NC = kw == 3 ? 1 : 2, MF = kw == 3 ? 2 : 4;
+    t.put(wg_slot(0, kw, f16), conv1d_wgrad_bf16_v2_kernel<kw, NCF, f16>, wgrad_v2_lds<kw, NCF>());
+    t.put(wg_slot(1, kw, f16), conv1d_wgrad_bf16_v3_kernel<kw, NC, MF, f16>, wgrad_v3_lds<kw, NC, MF>());
+  }); });
+  return t;
 }
 
 int conv1d_wgrad_bf16_v2_splits(int total_rows, int C, int M, int KW, int nseg, bool with_bias) {
@@ -553,7 +567,7 @@ int conv1d_wgrad_bf16_v2_launch(const void* const* dy, const void* const* x, int
                                 int total_rows, int C, int M, int KW, int w_layout, int accumulate, hipStream_t s,
                                 float* dbias, float* bias_partial, int elem, const float* out_scale) {
   const int ct = KW == 3 ? 128 : 256;
-  const int Mp = (M + 63) / 64 * 64, Cp = (C + 63) / 64 * 64;
+  const int Mp = pad_to(M, 64), Cp = pad_to(C, 64);
   WgradV2Args a{};
   for (int i = 0; i < WG_MAXSEG; ++i) {
     a.dy[i] = (const u16*)dy[i < nseg ? i : 0];
@@ -570,30 +584,11 @@ int conv1d_wgrad_bf16_v2_launch(const void* const* dy, const void* const* x, int
   ALVQ_REQUIRE(a.mtiles * a.ctiles == wgrad_v2_tiles(C, M, KW, v3) &&
                    (int64_t)a.splits * KW * M * C * 4 <= conv1d_wgrad_bf16_v2_workspace_bytes(total_rows, C, M, KW),
                ALVQ_EINVAL, "alvq_conv1d_wgrad_bf16: %d splits exceed what alvq_conv1d_wgrad_bf16_workspace_bytes sizes", a.splits);
+  static const WgTable table = wg_table();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v3_kernel<1, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v3_lds<1, 2, 4>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v3_kernel<3, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v3_lds<3, 1, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v2_kernel<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds<3, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v2_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds<1, 4>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v3_kernel<1, 2, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v3_lds<1, 2, 4>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v3_kernel<3, 1, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v3_lds<3, 1, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v2_kernel<3, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds<3, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_bf16_v2_kernel<1, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_v2_lds<1, 4>());
-  }
-  const int grid = a.mtiles * a.ctiles * a.splits;
-  if (elem) {
-    if (v3 && KW == 1) hipLaunchKernelGGL((conv1d_wgrad_bf16_v3_kernel<1, 2, 4, 1>), dim3(grid), dim3(512), (wgrad_v3_lds<1, 2, 4>()), s, a);
-    else if (v3) hipLaunchKernelGGL((conv1d_wgrad_bf16_v3_kernel<3, 1, 2, 1>), dim3(grid), dim3(512), (wgrad_v3_lds<3, 1, 2>()), s, a);
-    else if (KW == 3) hipLaunchKernelGGL((conv1d_wgrad_bf16_v2_kernel<3, 2, 1>), dim3(grid), dim3(512), (wgrad_v2_lds<3, 2>()), s, a);
-    else hipLaunchKernelGGL((conv1d_wgrad_bf16_v2_kernel<1, 4, 1>), dim3(grid), dim3(512), (wgrad_v2_lds<1, 4>()), s, a);
-  } else
-  if (v3 && KW == 1) hipLaunchKernelGGL((conv1d_wgrad_bf16_v3_kernel<1, 2, 4>), dim3(grid), dim3(512), (wgrad_v3_lds<1, 2, 4>()), s, a);
-  else if (v3) hipLaunchKernelGGL((conv1d_wgrad_bf16_v3_kernel<3, 1, 2>), dim3(grid), dim3(512), (wgrad_v3_lds<3, 1, 2>()), s, a);
-  else if (KW == 3) hipLaunchKernelGGL((conv1d_wgrad_bf16_v2_kernel<3, 2>), dim3(grid), dim3(512), (wgrad_v2_lds<3, 2>()), s, a);
-  else hipLaunchKernelGGL((conv1d_wgrad_bf16_v2_kernel<1, 4>), dim3(grid), dim3(512), (wgrad_v2_lds<1, 4>()), s, a);
-  int rc = check_launch("alvq_conv1d_wgrad_bf16(v2)");
-  if (rc) return rc;
+  if (attr.need()) table.raise_lds_limit();
+  if (int rc = table.launch(wg_slot(v3, KW, elem ? 1 : 0), dim3(a.mtiles * a.ctiles * a.splits), dim3(512), s, "alvq_conv1d_wgrad_bf16(v2)", a))
+    return rc;
   if (accumulate == ALVQ_WGRAD_DEFER) return ALVQ_OK;   // the caller sums the partials later (alvq_wgrad_reduce_batch)
   wgrad_reduce_launch((const float*)workspace, dw, a.splits, KW, M, C, w_layout, accumulate, s, out_scale);
   if (dbias)

@@ -16,6 +16,7 @@
 
 #include "alvq_common.h"
 #include "f16mx_common.h"
+#include "nlc_host.h"
 #include "wgrad_reduce.h"
 
 namespace alvq {
@@ -337,77 +338,56 @@ static constexpr int wgrad_fx_lds() {
   return 2 * (2 * 32 * (2 * MF * 32 * 2) + 2 * (KW == 1 ? 32 : 36) * (4 * NC * 32 * 2));
 }
 
-// tiles of a launch: 128 x 128 x 3 taps for width 3, 256 x 256 for width 1
-static int wgrad_fx_tiles(int C, int M, int KW) {
-  const int ct = KW == 3 ? 128 : 256, mt = KW == 3 ? 128 : 256;
-  return ((M + mt - 1) / mt) * ((C + ct - 1) / ct);
-}
+// tile of a launch: 128 x 128 x 3 taps for width 3, 256 x 256 for width 1
+static WgradTile wgrad_fx_tile(int KW) { return KW == 3 ? WgradTile{128, 128} : WgradTile{256, 256}; }
 
 }  // namespace alvq
 
 using namespace alvq;
 
-static inline int pad_to(int x, int q) { return (x + q - 1) / q * q; }
-static inline long nlc_plane_elems(int B, int L, int C) {
-  return ((long)alvq_nlc_rows(B, L) + 2L * alvq_nlc_guard_rows()) * pad_to(C, 64);
-}
-
 extern "C" int64_t alvq_conv1d_wgrad_f16mx_workspace_bytes(int B, int C, int M, int L, int KW) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3)) return -1;
-  const int splits = wgrad_split_bound((int)alvq_nlc_rows(B, L), wgrad_fx_tiles(C, M, KW), WF_MAXSEG);
-  return (int64_t)splits * KW * M * C * 4 + (int64_t)FX_BIAS_SPLITS * pad_to(M, 64) * 4;
+  return wgrad_workspace_bytes(B, C, M, L, KW, wgrad_fx_tile(KW), FX_BIAS_SPLITS);
 }
 
-static int wgrad_fx_launch(const void* const* dy, const void* const* x, int nseg, float* dw, float* dbias, void* workspace, int B,
-                           int C, int M, int L, int KW, int w_layout, int accumulate, const float* inv_scale, hipStream_t s) {
-  const int rows = (int)alvq_nlc_rows(B, L);
-  const int ct = KW == 3 ? 128 : 256, mt = KW == 3 ? 128 : 256;
+extern "C" int alvq_conv1d_wgrad_f16mx_splits(int B, int C, int M, int L, int KW, int nseg) {
+  return wgrad_splits(B, C, M, L, KW, nseg, wgrad_fx_tile(KW));
+}
+
+// the weight gradient behind alvq_conv1d_wgrad_f16mx and its _multi form (no bias gradient there: dbias null)
+static int wgrad_fx(const char* who, const void* const* dy, const void* const* x, int nseg, bool multi, float* dw, float* dbias,
+                    void* workspace, int B, int C, int M, int L, int KW, int w_layout, int accumulate, const float* inv_scale,
+                    hipStream_t s) {
+  if (int rc = check_wgrad_args(who, dy, x, nseg, multi, dw, workspace, B, C, M, L, KW, w_layout, accumulate, false)) return rc;
   WgradFxArgs a{};
-  for (int i = 0; i < WF_MAXSEG; ++i) {
-    a.dy[i] = (const u16*)dy[i < nseg ? i : 0];
-    a.x[i] = (const u16*)x[i < nseg ? i : 0];
-  }
-  a.nseg = nseg;
-  a.partial = (float*)workspace;
+  float* bpart;
+  if (int rc = wgrad_plan("alvq_conv1d_wgrad_f16mx", a, dy, x, nseg, workspace, B, C, M, L, KW, wgrad_fx_tile(KW), &bpart)) return rc;
   a.inv_scale = inv_scale;
-  a.dy_plane = nlc_plane_elems(B, L, M);
-  a.x_plane = nlc_plane_elems(B, L, C);
-  a.Mp = pad_to(M, 64); a.Cp = pad_to(C, 64); a.M = M; a.C = C;
-  a.mtiles = (M + mt - 1) / mt; a.ctiles = (C + ct - 1) / ct;
-  a.total_rows = rows; a.e = FX_E_ACT;
+  a.e = FX_E_ACT;
 #ifdef ALVQ_DEBUG_KERNELS   // ablation instantiations: debug library only (build.py --debug-kernels)
   static const int dbg_env = getenv("ALVQ_FX_DBG") ? atoi(getenv("ALVQ_FX_DBG")) : 0;   // timing ablations (results are garbage)
 #else
   constexpr int dbg_env = 0;
 #endif
   a.dbg = dbg_env;
-  a.splits = wgrad_split_plan(nseg * rows, a.mtiles * a.ctiles, &a.chunks_per_split);
-  ALVQ_REQUIRE(a.mtiles * a.ctiles == wgrad_fx_tiles(C, M, KW) && a.splits <= wgrad_split_bound(rows, wgrad_fx_tiles(C, M, KW), WF_MAXSEG),
-               ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx: %d splits exceed what alvq_conv1d_wgrad_f16mx_workspace_bytes sizes", a.splits);
-  float* bpart = (float*)((char*)workspace + (int64_t)a.splits * KW * M * C * 4);
+  // conv1d_wgrad_f16mx_kernel<KW, NC, MF, DBG> sits at [DBG][KW == 3]
+  static const auto table = [] {
+    KernelTable<void (*)(WgradFxArgs), 4> t;
+    for_values<1, 3>([&](auto kw) {
+      constexpr int NC = kw == 3 ? 1 : 2, MF = kw == 3 ? 2 : 4;
+      t.put(kw == 3, conv1d_wgrad_f16mx_kernel<kw, NC, MF>, wgrad_fx_lds<kw, NC, MF>());
+#ifdef ALVQ_DEBUG_KERNELS
+      t.put(2 + (kw == 3), conv1d_wgrad_f16mx_kernel<kw, NC, MF, true>, wgrad_fx_lds<kw, NC, MF>());
+#endif
+    });
+    return t;
+  }();
   static DeviceOnce attr;
-  if (attr.need()) {
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_f16mx_kernel<3, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_fx_lds<3, 1, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_f16mx_kernel<1, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_fx_lds<1, 2, 4>());
-#ifdef ALVQ_DEBUG_KERNELS
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_f16mx_kernel<3, 1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_fx_lds<3, 1, 2>());
-    (void)hipFuncSetAttribute((const void*)conv1d_wgrad_f16mx_kernel<1, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wgrad_fx_lds<1, 2, 4>());
-#endif
-  }
-  const int grid = a.mtiles * a.ctiles * a.splits;
-#ifdef ALVQ_DEBUG_KERNELS
-  if (dbg_env) {
-    if (KW == 3) hipLaunchKernelGGL((conv1d_wgrad_f16mx_kernel<3, 1, 2, true>), dim3(grid), dim3(512), (wgrad_fx_lds<3, 1, 2>()), s, a);
-    else hipLaunchKernelGGL((conv1d_wgrad_f16mx_kernel<1, 2, 4, true>), dim3(grid), dim3(512), (wgrad_fx_lds<1, 2, 4>()), s, a);
-  } else
-#endif
-  if (KW == 3) hipLaunchKernelGGL((conv1d_wgrad_f16mx_kernel<3, 1, 2>), dim3(grid), dim3(512), (wgrad_fx_lds<3, 1, 2>()), s, a);
-  else hipLaunchKernelGGL((conv1d_wgrad_f16mx_kernel<1, 2, 4>), dim3(grid), dim3(512), (wgrad_fx_lds<1, 2, 4>()), s, a);
-  int rc = check_launch("alvq_conv1d_wgrad_f16mx");
-  if (rc) return rc;
+  if (attr.need()) table.raise_lds_limit();
+  if (int rc = table.launch((dbg_env ? 2 : 0) + (KW == 3), dim3(a.mtiles * a.ctiles * a.splits), dim3(512), s, "alvq_conv1d_wgrad_f16mx", a))
+    return rc;
   wgrad_reduce_launch((const float*)workspace, dw, a.splits, KW, M, C, w_layout, accumulate, s);
   if (dbias) {     // single segment only (the shared residual weights have no bias)
-    const int rps = (rows + FX_BIAS_SPLITS - 1) / FX_BIAS_SPLITS;
+    const int rows = a.total_rows, rps = (rows + FX_BIAS_SPLITS - 1) / FX_BIAS_SPLITS;
     hipLaunchKernelGGL(bias_grad_fx_partial_kernel, dim3(a.Mp / 64, FX_BIAS_SPLITS), dim3(256), 0, s, (const u16*)dy[0], a.dy_plane, bpart,
                        rows, a.Mp, rps, a.e);
     hipLaunchKernelGGL(wgrad_fx_bias_reduce_kernel, dim3((M + 31) / 32), dim3(256), 0, s, (const float*)bpart, dbias, a.Mp, M,
@@ -416,29 +396,15 @@ static int wgrad_fx_launch(const void* const* dy, const void* const* x, int nseg
   return check_launch("alvq_conv1d_wgrad_f16mx/reduce");
 }
 
-extern "C" int alvq_conv1d_wgrad_f16mx_splits(int B, int C, int M, int L, int KW, int nseg) {
-  if (B <= 0 || C <= 0 || M <= 0 || L <= 0 || (KW != 1 && KW != 3) || nseg < 1 || nseg > WF_MAXSEG) return -1;
-  int cps;
-  return wgrad_split_plan(nseg * (int)alvq_nlc_rows(B, L), wgrad_fx_tiles(C, M, KW), &cps);
-}
-
 extern "C" int alvq_conv1d_wgrad_f16mx(const void* dy, const void* x, float* dw, float* dbias, void* workspace, int B, int C, int M,
                                        int L, int KW, int w_layout, int accumulate, const float* inv_scale, void* stream) {
-  ALVQ_REQUIRE(dy && x && dw && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx: null pointer");
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16mx: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx: w_layout");
-  return wgrad_fx_launch(&dy, &x, 1, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate, inv_scale, (hipStream_t)stream);
+  return wgrad_fx("alvq_conv1d_wgrad_f16mx", &dy, &x, 1, false, dw, dbias, workspace, B, C, M, L, KW, w_layout, accumulate, inv_scale,
+                  (hipStream_t)stream);
 }
 
 extern "C" int alvq_conv1d_wgrad_f16mx_multi(const void* const* dy, const void* const* x, int nseg, float* dw, void* workspace,
                                              int B, int C, int M, int L, int KW, int w_layout, int accumulate,
                                              const float* inv_scale, void* stream) {
-  ALVQ_REQUIRE(dy && x && dw && workspace, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx_multi: null pointer");
-  ALVQ_REQUIRE(nseg >= 1 && nseg <= WF_MAXSEG, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16mx_multi: nseg=%d (1..4)", nseg);
-  for (int i = 0; i < nseg; ++i) ALVQ_REQUIRE(dy[i] && x[i], ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx_multi: null segment %d", i);
-  ALVQ_REQUIRE(B > 0 && C > 0 && M > 0 && L > 0, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx_multi: bad dims");
-  ALVQ_REQUIRE(KW == 1 || KW == 3, ALVQ_EUNSUPPORTED, "alvq_conv1d_wgrad_f16mx_multi: KW=%d (only 1 and 3)", KW);
-  ALVQ_REQUIRE(w_layout == ALVQ_W_OIK || w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_conv1d_wgrad_f16mx_multi: w_layout");
-  return wgrad_fx_launch(dy, x, nseg, dw, nullptr, workspace, B, C, M, L, KW, w_layout, accumulate, inv_scale, (hipStream_t)stream);
+  return wgrad_fx("alvq_conv1d_wgrad_f16mx_multi", dy, x, nseg, true, dw, nullptr, workspace, B, C, M, L, KW, w_layout, accumulate,
+                  inv_scale, (hipStream_t)stream);
 }

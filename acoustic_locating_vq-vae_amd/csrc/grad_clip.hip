@@ -28,12 +28,6 @@ constexpr int GC_THREADS = 512;
 constexpr int GC_BATCH = 16;      // partials thread 0 of the second pass holds in registers while the next batch is in flight
 constexpr int GC_UNROLL = 4;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // components of quad q that lie in [0, n), the others as +0; vec: the buffer is 16-byte aligned and q is a full quad
 __device__ __forceinline__ f32x4 load_quad(const float* __restrict__ g, long q, long nq, long n, bool vec) {
   if (vec && q < nq) return ((const f32x4*)g)[q];
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(GC_THREADS) void grad_sumsq_kernel(const float* __r
     a2 += z * z;
     a3 += w * w;
   }
-  double s = wave_sum_f64((a0 + a1) + (a2 + a3));
+  double s = wave_sum((a0 + a1) + (a2 + a3));
   if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

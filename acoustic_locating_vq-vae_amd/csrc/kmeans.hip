@@ -35,12 +35,6 @@ constexpr int PP_ROWS = 64;     // rows per k-means++ block
 constexpr int PP_DC = 128;      // dims per staged chunk
 constexpr int PP_MAX_T = 16;    // candidates per round (one wave each in pick_kernel)
 
-__device__ __forceinline__ double km_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return __shfl(v, 0, 64);
-}
-
 // exclusive scan over the workgroup (threads in order); `total` = the sum of all.  sh: >= 16 ints of LDS.
 __device__ int block_scan_excl(int v, int* sh, int& total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -239,7 +233,7 @@ __global__ __launch_bounds__(256) void rowdist_kernel(const float* __restrict__ 
         const double v = (double)x[r * D + d] - (double)c[l * D + d];
         s += v * v;
       }
-    s = km_wave_sum(s);
+    s = wave_sum_lane0(s);
     if (lane == 0) dist[r] = s;
   }
 }
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(128) void finalize_kernel(const double* __restrict_
     const double df = (double)v - (double)c_old[(long)k * D + d];
     acc += df * df;
   }
-  acc = km_wave_sum(acc);
+  acc = wave_sum_lane0(acc);
   if ((tid & 63) == 0) sh[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0) {
@@ -364,7 +358,7 @@ __global__ __launch_bounds__(256) void verdict_kernel(const double* __restrict__
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int k = tid; k < K; k += 256) s += shift[k] * shift[k];
-  s = km_wave_sum(s);
+  s = wave_sum_lane0(s);
   if ((tid & 63) == 0) sh[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
@@ -385,7 +379,7 @@ __global__ __launch_bounds__(1024) void sum_kernel(const double* __restrict__ v,
   const long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
   double s = 0.0;
   for (long i = lo; i < hi; ++i) s += v[i];
-  s = km_wave_sum(s);
+  s = wave_sum_lane0(s);
   if ((tid & 63) == 0) sh[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
@@ -407,7 +401,7 @@ __global__ __launch_bounds__(1024) void ema_size_kernel(const float* __restrict_
   const double omd = 1.0 - decay;
   double s = 0.0;
   for (int k = tid; k < K; k += 1024) s += decay * (double)cs[k] + omd * (double)counts[k];
-  s = km_wave_sum(s);
+  s = wave_sum_lane0(s);
   if ((tid & 63) == 0) sh[tid >> 6] = s;
   __syncthreads();
   double n = 0.0;
@@ -600,7 +594,7 @@ __global__ __launch_bounds__(256) void ppdist_kernel(const float* __restrict__ x
     a += __shfl_xor(a, 2, 64);
     const double m = closest ? fmin(cl, a) : a;
     if (q == 0 && r < N) dist[(long)t * N + r] = m;
-    const double bs = km_wave_sum((q == 0 && r < N) ? m : 0.0);
+    const double bs = wave_sum_lane0((q == 0 && r < N) ? m : 0.0);
     if (lane == 0) sh[wave][t] = bs;
   }
   __syncthreads();
@@ -617,7 +611,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ 
   for (int t = 0; t < T; ++t) {
     double s = 0.0;
     for (int b = tid; b < NBK; b += 1024) s += part[(long)t * NBK + b];
-    s = km_wave_sum(s);
+    s = wave_sum_lane0(s);
     if (lane == 0) sh[t][wave] = s;
   }
   __syncthreads();

@@ -6,6 +6,7 @@
 #include "alvq_common.h"
 #include "bf16_common.h"
 #include "f16mx_common.h"
+#include "nlc_host.h"
 
 namespace alvq {
 
@@ -233,8 +234,6 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(float* p, const floa
 }  // namespace alvq
 
 using namespace alvq;
-
-static inline int pad_to(int x, int q) { return (x + q - 1) / q * q; }
 
 extern "C" int alvq_pack_weights_bf16_batch(const alvq_pack_desc* descs, int n, int planes, void* stream) {
   ALVQ_REQUIRE(descs && n > 0, ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: no descriptors");

@@ -28,13 +28,6 @@ constexpr int TS_MAX_N = 65536;
 constexpr int TS_MAX_L = 4096;
 constexpr double TS_EPS = 2.220446049250313e-16;  // float64 machine epsilon (sklearn's MACHINE_EPSILON)
 
-// butterfly sum over the 64 lanes; x + y == y + x bitwise, so every lane ends with the same value (lane 0's is broadcast)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return __shfl(v, 0, 64);
-}
-
 __global__ __launch_bounds__(256) void sqdist_kernel(const int* __restrict__ codes, float* __restrict__ d2, int N, int L) {
   __shared__ int ci[TS_TILE][TS_LC + 1];
   __shared__ int cj[TS_TILE][TS_LC + 1];
@@ -117,8 +110,8 @@ __global__ __launch_bounds__(TS_SEARCH_THREADS) void search_kernel(float* __rest
     }
     for (int j = TS_REG_N + tid; j < N; j += TS_SEARCH_THREADS)
       if (j != i) search_term((double)hi[j - TS_REG_N], beta, s, sd);
-    s = wave_sum_f64(s);
-    sd = wave_sum_f64(sd);
+    s = wave_sum_lane0(s);
+    sd = wave_sum_lane0(sd);
     double* pp = &part[step & 1][0][0];  // alternate buffers: one barrier per step
     if (lane == 0) {
       pp[wave] = s;
@@ -185,7 +178,7 @@ __global__ __launch_bounds__(256) void rowsum_kernel(const float* __restrict__ P
   double s = 0.0;
   for (int j = lane; j < N; j += 64)
     if (j != i) s += (double)row[j];
-  s = wave_sum_f64(s);
+  s = wave_sum_lane0(s);
   if (lane == 0) rowsum[i] = s;
 }
 
@@ -223,7 +216,7 @@ __global__ __launch_bounds__(256) void numsum_kernel(const double* __restrict__ 
     const double dx = yx - Y[2 * j], dy = yy - Y[2 * j + 1];
     s += 1.0 / (1.0 + (dx * dx + dy * dy));
   }
-  s = wave_sum_f64(s);
+  s = wave_sum_lane0(s);
   if (lane == 0) rowZ[i] = s;
 }
 
@@ -253,9 +246,9 @@ __global__ __launch_bounds__(256) void grad_kernel(const float* __restrict__ P, 
     gy += coef * dy;
     if (WANT_KL) kl += ep * log(fmax(ep, TS_EPS) / q);
   }
-  gx = wave_sum_f64(gx);
-  gy = wave_sum_f64(gy);
-  if (WANT_KL) kl = wave_sum_f64(kl);
+  gx = wave_sum_lane0(gx);
+  gy = wave_sum_lane0(gy);
+  if (WANT_KL) kl = wave_sum_lane0(kl);
   if (lane != 0) return;
   const double g0[2] = {4.0 * gx, 4.0 * gy};
   const double y0[2] = {yx, yy};

@@ -1,4 +1,4 @@
-"""Bitwise fingerprint of the f16mx / bf16 / bf16x3 kernels' outputs on a fixed set of deterministic cases: run once per
+"""Bitwise fingerprint of the f16mx / bf16 / bf16x3 / f16 kernels' outputs on a fixed set of deterministic cases: run once per
 library build (ALVQ_LIB=...), diff the JSON lines.  A kernel rewrite that claims "bit-identical" must leave every hash
 unchanged.     ALVQ_LIB=$PWD/acoustic_locating_vq-vae_amd/lib/libalvq_base.so python3 tools/ab_bits.py > a.json
                python3 tools/ab_bits.py > b.json && diff a.json b.json"""
@@ -13,6 +13,9 @@ for p in (ROOT, PKG, os.path.join(PKG, "src")):
     sys.path.insert(0, p)
 import torch  # noqa: E402
 from acoustic_locating_vq_vae import _native as N  # noqa: E402
+
+
+MODES = {"f16mx": (2, 3, "f16mx"), "bf16": (1, 1, None), "bf16x3": (2, 2, None), "f16": (1, 3, "f16")}   # planes, weight code, fmt
 
 
 def digest(*tensors):
@@ -30,13 +33,13 @@ def digest(*tensors):
 
 
 def main():
-    modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3"]
+    modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3", "f16"]
     out = {}
     shapes = [(2, 7, 16, 13, 3), (3, 72, 136, 95, 1), (2, 201, 1024, 500, 3), (2, 1024, 128, 500, 3), (2, 1024, 1024, 201, 1),
               (5, 130, 130, 129, 3), (4, 1024, 1024, 500, 1), (4, 1024, 1024, 500, 3), (3, 1024, 201, 500, 3), (2, 500, 1024, 201, 3)]
     for mode in modes:
-        planes, wpl = {"f16mx": (2, 3), "bf16": (1, 1), "bf16x3": (2, 2)}[mode]
-        fmt = "f16mx" if mode == "f16mx" else None
+        # f16: one fp16 plane reading the H plane of f16mx-packed weights, gradients under a loss scale (the _hb backward)
+        planes, wpl, fmt = MODES[mode]
         for (B, C, M, L, KW) in shapes:
             g = torch.Generator(device="cuda").manual_seed(B * 1000 + C + M + L + KW)
             x = torch.randn(B, C, L, device="cuda", generator=g)
@@ -77,7 +80,7 @@ def xn_relu(xn, N, mode, B, C, L, g, enter):
     """A ReLU'd tensor of the input's shape that carries sign bits (the mask operand of a data-gradient launch)."""
     t = enter(torch.randn(B, C, L, device="cuda", generator=g))
     out = N.relu_mask_bf16(t, t)        # relu via mask; no sign bits here
-    pk1 = N.pack_weight(torch.eye(C, device="cuda").view(C, C, 1).contiguous(), N.W_OIK, {"f16mx": 3, "bf16": 1, "bf16x3": 2}[mode])
+    pk1 = N.pack_weight(torch.eye(C, device="cuda").view(C, C, 1).contiguous(), N.W_OIK, MODES[mode][1])
     return N.conv1d_bf16(out, pk1, relu=True)   # identity conv with ReLU: leaves the sign bits behind
 
 

@@ -1,0 +1,107 @@
+"""Are the device kernels of two builds the same?  For a host-only change: compares, kernel by kernel, the gfx950 code of every
+object file of two build directories (acoustic_locating_vq-vae_amd/build or build_dbg of two checkouts).
+
+    python tools/compare_kernels.py OLD_BUILD_DIR NEW_BUILD_DIR [more OLD NEW pairs]
+
+Per object: the .hip_fatbin section is dumped, its gfx950 code object unbundled, and three things are compared keyed by kernel
+symbol -- the set of kernels, each kernel's disassembly (addresses and address comments stripped) and each kernel's metadata
+entry (registers, LDS, scratch, kernarg layout).  Whole files or whole .text sections are NOT compared: they differ between
+two builds of the same source (the per-build unit id) and whenever the host code names the kernels in another order.
+Prints one line per object and a total; exit status 1 if anything differs."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def _run(*cmd):
+    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+
+
+def code_object(obj, tmp):
+    fat, co = os.path.join(tmp, "fatbin"), os.path.join(tmp, "co")
+    for f in (fat, co):
+        if os.path.exists(f):
+            os.remove(f)
+    try:
+        _run(os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj)
+    except subprocess.CalledProcessError:
+        return None                                           # an object without device code (no such section)
+    _run(os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co)
+    return co
+
+
+def kernels(co):
+    """{kernel symbol: (disassembly, metadata entry)} of one code object."""
+    notes = _run(os.path.join(LLVM, "llvm-readelf"), "--notes", co)
+    by_name, entry = {}, None
+    for line in notes.split("amdhsa.kernels:", 1)[-1].splitlines()[1:] + ["end"]:
+        if not line.startswith("    ") and entry:        # "  - " opens the next entry, anything less indented ends the list
+            name = [ln.split()[-1] for ln in entry if ln.startswith("    .name:") or ln.startswith("  - .name:")]
+            by_name[name[0]] = "\n".join(entry)
+            entry = None
+        if line and not line.startswith(" "):                 # amdhsa.target: -- the kernel list is over
+            break
+        if line.startswith("  - "):
+            entry = []
+        if entry is not None and line.strip():
+            entry.append(line.rstrip())
+    dis = _run(os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", co)
+    code, sym = {}, None
+    for line in dis.splitlines():
+        m = re.match(r"^(?:[0-9a-f]+ )?<(\S+)>:$", line)
+        if m:
+            sym = m.group(1)
+            code[sym] = []
+        elif sym is not None and line.strip() and line.strip() != "...":   # "...": zero padding after the section's last kernel
+            code[sym].append(re.sub(r"\s*//.*$", "", line).strip())
+    return {k: ("\n".join(code.get(k, ["<no code>"])), by_name[k]) for k in by_name}
+
+
+def compare(old_dir, new_dir, tmp):
+    objs_old = {f for f in os.listdir(old_dir) if f.endswith(".o")}
+    objs_new = {f for f in os.listdir(new_dir) if f.endswith(".o")}
+    nobj = nker = ndiff = 0
+    for f in sorted(objs_old ^ objs_new):
+        print("DIFF object only on one side: %s" % f)
+        ndiff += 1
+    for f in sorted(objs_old & objs_new):
+        sides = []
+        for d in (old_dir, new_dir):
+            co = code_object(os.path.join(d, f), tmp)
+            sides.append(kernels(co) if co else {})
+        a, b = sides
+        bad = sorted(set(a) ^ set(b))
+        for k in bad:
+            print("DIFF %s: kernel on one side only: %s" % (f, k))
+        for k in sorted(set(a) & set(b)):
+            if a[k][0] != b[k][0]:
+                bad.append(k)
+                print("DIFF %s: code of %s" % (f, k))
+            elif a[k][1] != b[k][1]:
+                bad.append(k)
+                print("DIFF %s: metadata of %s" % (f, k))
+        print("%-28s %3d kernels, %d differences" % (f, len(set(a) | set(b)), len(bad)))
+        nobj, nker, ndiff = nobj + 1, nker + len(set(a) | set(b)), ndiff + len(bad)
+    return nobj, nker, ndiff
+
+
+def main(argv):
+    if len(argv) < 2 or len(argv) % 2:
+        sys.exit(__doc__)
+    tot = [0, 0, 0]
+    with tempfile.TemporaryDirectory() as tmp:
+        for i in range(0, len(argv), 2):
+            print("== %s  vs  %s" % (argv[i], argv[i + 1]))
+            for j, v in enumerate(compare(argv[i], argv[i + 1], tmp)):
+                tot[j] += v
+    print("objects compared: %d, kernels compared: %d, differences: %d" % tuple(tot))
+    return 1 if tot[2] else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
