@@ -121,6 +121,10 @@ _SIGNATURES = {
     "alvq_rir_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p] + [ctypes.c_double] * 2
                      + [_i32] * 2 + [_c_void_p]),
     "alvq_rir_rooms_f64": (_i32, [_c_void_p] * 6 + [_i32] * 2 + [ctypes.c_double] * 2 + [_i32] * 2 + [_c_void_p]),
+    "alvq_edc_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
+    "alvq_edc_f64": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
+    "alvq_room_acoustics_f32": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
+    "alvq_room_acoustics_f64": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -878,6 +882,35 @@ def rir_rooms(src, rcv, room, beta, c, fs, nsample, order=-1, hp_filter=True):
                                     _ptr(status, torch.int32, "status"), B, int(nsample), float(c), float(fs), int(order),
                                     int(bool(hp_filter)), _stream()), "alvq_rir_rooms_f64")
     return h, status
+
+
+def _responses(h, who):
+    if h.dim() != 2 or h.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("%s: h must be a float32 or float64 (B, n) tensor (got %s %s)" % (who, h.dtype, tuple(h.shape)))
+    return h.shape[0], h.shape[1], "f64" if h.dtype == torch.float64 else "f32"
+
+
+def edc(h):
+    """Energy decay curves (alvq_edc_f32 / _f64): h (B, n) float32 or float64 on the GPU -> (B, n) float64 dB."""
+    B, n, sfx = _responses(h, "edc")
+    out = torch.empty((B, n), device=h.device, dtype=torch.float64)
+    name = "alvq_edc_" + sfx
+    _check(getattr(lib(), name)(_ptr(h, h.dtype, "h"), _ptr(out, torch.float64), B, n, _stream()), name)
+    return out
+
+
+def room_acoustics(h, fs, k50, k80, kdirect):
+    """Room-acoustic parameters (alvq_room_acoustics_f32 / _f64): h (B, n) float32 or float64 on the GPU -> (out (B, 7)
+    float64 with columns t30 t20 edt c50 c80 d50 drr, onset (B,) int32, status (B,) int32).  status is the kernel's per-row
+    flag (include/alvq.h) and is not read here."""
+    B, n, sfx = _responses(h, "room_acoustics")
+    out = torch.empty((B, 7), device=h.device, dtype=torch.float64)
+    onset = torch.empty((B,), device=h.device, dtype=torch.int32)
+    status = torch.empty((B,), device=h.device, dtype=torch.int32)
+    name = "alvq_room_acoustics_" + sfx
+    _check(getattr(lib(), name)(_ptr(h, h.dtype, "h"), _ptr(out, torch.float64), _ptr(onset, torch.int32), _ptr(status, torch.int32),
+                                B, n, float(fs), int(k50), int(k80), int(kdirect), _stream()), name)
+    return out, onset, status
 
 
 # ----------------------------------------------------------------------------------------------- t-SNE

@@ -310,6 +310,38 @@ int alvq_rir_rooms_f64(const double* src, const double* rcv, const double* room,
                        int nsample, double c, double fs, int order, int hp_filter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * What reverberation an impulse response has (csrc/room_acoustics.hip): Schroeder's backward integration and least-squares
+ * line fits to the decay curve (ISO 3382).  h: device (B, n) responses, float32 ("_f32") or float64 ("_f64"); all arithmetic
+ * is float64 (a float32 sample is widened first, so the _f32 result is bitwise the _f64 result on the widened rows).
+ * B >= 1, 2 <= n <= 2^24.  One workgroup per response and one launch; no atomics, no workspace, no host sync.  Each response is
+ * summed in one fixed order that depends on n alone: a row has the same bits in any batch and on any run.
+ *
+ * Energy decay curve: with T(t) = sum_{s >= t} h[s]^2,  edc_db[t] = 10 log10(T(t) / T(0)), evaluated as
+ * 10 (log10 T(t) - log10 T(0)) and never above 0; -inf where T(t) = 0; the whole row NaN when T(0) is 0 or not finite.
+ * edc_db: device (B, n) float64. */
+int alvq_edc_f32(const float* h, double* edc_db, int B, int n, void* stream);
+int alvq_edc_f64(const double* h, double* edc_db, int B, int n, void* stream);
+
+/* Room-acoustic parameters.  out: device (B, 7) float64, columns t30, t20, edt (s), c50, c80 (dB), d50, drr (dB); onset and
+ * status: device (B,) int32.  fs: sample rate (> 0); k50, k80, kdirect (>= 0): 50 ms, 80 ms and 2.5 ms in samples -- the
+ * caller rounds them (floor(ms * 1e-3 * fs + 0.5)), the kernel has no rounding rule of its own.
+ *   E(a, b) = sum_{a <= t < b} h[t]^2, a and b clipped to [0, n], taken as the difference T(a) - T(b) of tail energies.
+ *   n0      = the first index of max |h[t]| (a NaN counts as the largest value), written to onset.  Everything is measured
+ *             from n0.
+ *   L(t)    = 10 log10(E(t, n) / E(n0, n)) for t >= n0, the decay level (evaluated as for edc_db; L(n0) = 0 exactly).
+ *   A decay time over (hi, lo) dB is -60 / slope, the slope (dB/s) of the least-squares line of L(t) against (t - n0) / fs over
+ *   all t >= n0 with lo <= L(t) <= hi:  t30 over (-5, -35), t20 over (-5, -25), edt over (0, -10).
+ *   c50 = 10 log10(E(n0, n0 + k50) / E(n0 + k50, n)), c80 likewise with k80;  d50 = E(n0, n0 + k50) / E(n0, n);
+ *   drr = 10 log10(E(n0 - kdirect, n0 + kdirect + 1) / E(n0 + kdirect + 1, n)).
+ * status bits: 1 = T(0) is 0 or not finite (all seven outputs NaN, no other bit); 2 = a decay range held fewer than two
+ * samples (that output NaN); 4 = a late or reverberant energy was 0 (that ratio +inf).  The caller reads status when it can
+ * sync. */
+int alvq_room_acoustics_f32(const float* h, double* out, int* onset, int* status, int B, int n, double fs, int k50, int k80,
+                            int kdirect, void* stream);
+int alvq_room_acoustics_f64(const double* h, double* out, int* onset, int* status, int B, int n, double fs, int k50, int k80,
+                            int kdirect, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
