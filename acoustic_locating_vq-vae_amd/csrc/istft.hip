@@ -7,33 +7,17 @@
 //                        frame workspace (B, T, n_fft).
 //   ola_gather_kernel    one thread per output sample: sums the <= ceil(n_fft/hop) windowed frames that cover it, in
 //                        ascending frame order, and divides by the overlap-added w^2 envelope (computed in place).
-//   stft_project_kernel  Griffin-Lim's forward STFT (as csrc/stft.hip: reflect pad, frames + table in LDS, thread k = bin k of
-//                        8 frames) with the projection in its epilogue: it reads tprev, writes rebuilt over it, and writes the
-//                        next mag * angles for the inverse.  No separate elementwise pass over the spectra.
+//   stft_project_kernel  Griffin-Lim's forward STFT (the framing and transform of csrc/stft.hip, both from dft_frames.h) with
+//                        the projection as its tail: it reads tprev, writes rebuilt over it, and writes the next mag * angles
+//                        for the inverse.  No separate elementwise pass over the spectra.
 // Griffin-Lim enqueues 3 launches per iteration + 2 on one stream: a linear chain, capturable in a single-stream graph.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "alvq_common.h"
+#include "dft_frames.h"
 
 namespace alvq {
-
-constexpr int IS_FT = 8;  // frames per workgroup (both DFT kernels)
-
-template <typename R>
-__device__ __forceinline__ void fill_twiddles(R* cs, R* sn, int N, int tid) {
-  for (int j = tid; j < N; j += 256) {
-    const double ang = 2.0 * (double)j / (double)N;
-    cs[j] = (R)cospi(ang);
-    sn[j] = (R)sinpi(ang);
-  }
-}
-
-template <typename R>
-__device__ __forceinline__ R hann(int n, int N) {
-  return (R)(0.5 - 0.5 * cospi(2.0 * (double)n / (double)N));  // periodic Hann
-}
 
 // frames[b][t][n] = scale * w[n] * (X0.re + (-1)^n X_{N/2}.re + 2 sum_{k=1}^{N/2-1} (Xk.re cos - Xk.im sin)(2 pi k n / N)),
 // X = spec[b][:, t] (interleaved), or mag[b][:, t] * spec[b][:, t] when mag is given (Griffin-Lim's first inverse).
@@ -45,12 +29,12 @@ __global__ __launch_bounds__(256) void irfft_frames_kernel(const R* spec, const 
   const int F = N / 2 + 1;
   R* cs = sm;               // [N]
   R* sn = sm + N;           // [N]
-  R* xs = sm + 2 * N;       // [IS_FT][F][2]
+  R* xs = sm + 2 * N;       // [DFT_FT][F][2]
   const int tid = threadIdx.x;
-  const int ttiles = (T + IS_FT - 1) / IS_FT;
-  const int b = blockIdx.x / ttiles, t0 = (blockIdx.x % ttiles) * IS_FT;
+  const FrameTile tile = frame_tile(T);
+  const int b = tile.b, t0 = tile.t0;
   fill_twiddles(cs, sn, N, tid);
-  for (int e = tid; e < IS_FT * F; e += 256) {
+  for (int e = tid; e < DFT_FT * F; e += 256) {
     const int f = e / F, k = e - f * F;
     const int t = t0 + f;
     R re = 0, im = 0;
@@ -69,15 +53,15 @@ __global__ __launch_bounds__(256) void irfft_frames_kernel(const R* spec, const 
   }
   __syncthreads();
   for (int n = tid; n < N; n += 256) {
-    R acc[IS_FT];
+    R acc[DFT_FT];
     const R sgn = (n & 1) ? (R)-1 : (R)1;
 #pragma unroll
-    for (int f = 0; f < IS_FT; ++f) acc[f] = 0;
+    for (int f = 0; f < DFT_FT; ++f) acc[f] = 0;
     int idx = n;
     for (int k = 1; k < F - 1; ++k) {
       const R c = cs[idx], s = sn[idx];
 #pragma unroll
-      for (int f = 0; f < IS_FT; ++f) {
+      for (int f = 0; f < DFT_FT; ++f) {
         const R* x = xs + 2 * (f * F + k);
         acc[f] += x[0] * c - x[1] * s;
       }
@@ -86,7 +70,7 @@ __global__ __launch_bounds__(256) void irfft_frames_kernel(const R* spec, const 
     }
     const R w = hann<R>(n, N) * scale;
 #pragma unroll
-    for (int f = 0; f < IS_FT; ++f)
+    for (int f = 0; f < DFT_FT; ++f)
       if (t0 + f < T) {
         const R v = xs[2 * f * F] + sgn * xs[2 * (f * F + F - 1)] + (R)2 * acc[f];
         frames[((long)b * T + t0 + f) * N + n] = v * w;
@@ -128,61 +112,29 @@ __global__ __launch_bounds__(256) void stft_project_kernel(const R* wave, const 
   R* sm = (R*)sm_raw;
   R* cs = sm;               // [N]
   R* sn = sm + N;           // [N]
-  R* fr = sm + 2 * N;       // [IS_FT][N]
+  R* fr = sm + 2 * N;       // [DFT_FT][N]
   const int tid = threadIdx.x;
-  const int ttiles = (T + IS_FT - 1) / IS_FT;
-  const int b = blockIdx.x / ttiles, t0 = (blockIdx.x % ttiles) * IS_FT;
-  const R* wv = wave + (long)b * S;
+  const FrameTile tile = frame_tile(T);
+  const int b = tile.b, t0 = tile.t0;
   const int F = N / 2 + 1;
   fill_twiddles(cs, sn, N, tid);
   __syncthreads();
-  for (int e = tid; e < IS_FT * N; e += 256) {
-    const int f = e / N, n = e - f * N;
-    const int t = t0 + f;
-    R v = 0;
-    if (t < T) {
-      int i = t * hop + n - N / 2;  // reflect padding; S > N/2 so one reflection suffices
-      if (i < 0) i = -i;
-      if (i >= S) i = 2 * (S - 1) - i;
-      const R w = (R)0.5 - (R)0.5 * cs[n];
-      v = wv[i] * w;
-    }
-    fr[e] = v;
-  }
+  load_frames(fr, cs, wave + (long)b * S, S, N, hop, T, t0, tid);
   __syncthreads();
-  for (int k = tid; k < F; k += 256) {
-    R re[IS_FT], im[IS_FT];
-#pragma unroll
-    for (int f = 0; f < IS_FT; ++f) re[f] = im[f] = 0;
-    int idx = 0;
-    for (int n = 0; n < N; ++n) {
-      const R c = cs[idx], s = sn[idx];
-#pragma unroll
-      for (int f = 0; f < IS_FT; ++f) {
-        const R x = fr[f * N + n];
-        re[f] += x * c;
-        im[f] -= x * s;
-      }
-      idx += k;
-      if (idx >= N) idx -= N;
+  forward_dft(cs, sn, fr, N, T, t0, tid, [=](int k, int t, R re, R im) {
+    const long o = ((long)b * F + k) * T + t;
+    R ar = re, ai = im;
+    if (!first) {
+      ar -= coef * tprev[2 * o];
+      ai -= coef * tprev[2 * o + 1];
     }
-#pragma unroll
-    for (int f = 0; f < IS_FT; ++f)
-      if (t0 + f < T) {
-        const long o = ((long)b * F + k) * T + t0 + f;
-        R ar = re[f], ai = im[f];
-        if (!first) {
-          ar -= coef * tprev[2 * o];
-          ai -= coef * tprev[2 * o + 1];
-        }
-        tprev[2 * o] = re[f];
-        tprev[2 * o + 1] = im[f];
-        const R inv = (R)1 / (sqrt(ar * ar + ai * ai) + (R)1e-16);
-        const R m = mag[o];
-        next[2 * o] = m * (ar * inv);
-        next[2 * o + 1] = m * (ai * inv);
-      }
-  }
+    tprev[2 * o] = re;
+    tprev[2 * o + 1] = im;
+    const R inv = (R)1 / (sqrt(ar * ar + ai * ai) + (R)1e-16);
+    const R m = mag[o];
+    next[2 * o] = m * (ar * inv);
+    next[2 * o + 1] = m * (ai * inv);
+  });
 }
 
 }  // namespace alvq
@@ -204,7 +156,7 @@ template <typename R>
 static int istft_check(int B, int T, int n_fft, int hop, int length, const char* who) {
   ALVQ_REQUIRE(B > 0 && T > 0 && hop > 0 && n_fft >= 4 && n_fft % 2 == 0 && length > 0, ALVQ_EINVAL,
                "%s: bad dims (B=%d T=%d n_fft=%d hop=%d length=%d; even n_fft >= 4)", who, B, T, n_fft, hop, length);
-  ALVQ_REQUIRE(n_fft <= 2048 * (int)sizeof(float) / (int)sizeof(R), ALVQ_EINVAL, "%s: n_fft=%d too large", who, n_fft);
+  ALVQ_REQUIRE(n_fft <= dft_max_n_fft<R>(), ALVQ_EINVAL, "%s: n_fft=%d too large", who, n_fft);
   ALVQ_REQUIRE((long)n_fft + (long)hop * (T - 1) < (1L << 30), ALVQ_EINVAL, "%s: signal too long", who);
   const int total = n_fft + hop * (T - 1), p0 = n_fft / 2, p1 = std::min(p0 + length, total);
   std::vector<double> env(total, 0.0);
@@ -220,15 +172,10 @@ static int istft_check(int B, int T, int n_fft, int hop, int length, const char*
 }
 
 template <typename R>
-static size_t dft_lds(int n_fft) {
-  return (size_t)(2 * n_fft + IS_FT * 2 * (n_fft / 2 + 1)) * sizeof(R);  // >= (2 + IS_FT) * n_fft: serves both kernels
-}
-
-template <typename R>
 static void enqueue_inverse(const R* spec, const R* mag, R* wave, R* frames, int B, int T, int n_fft, int hop, int length, R scale,
                             hipStream_t s) {
-  hipLaunchKernelGGL(irfft_frames_kernel<R>, dim3(B * ((T + IS_FT - 1) / IS_FT)), dim3(256), dft_lds<R>(n_fft), s, spec, mag,
-                     frames, n_fft, T, scale);
+  hipLaunchKernelGGL(irfft_frames_kernel<R>, dft_grid(B, T), dim3(256), dft_inverse_lds<R>(n_fft), s, spec, mag, frames, n_fft, T,
+                     scale);
   hipLaunchKernelGGL(ola_gather_kernel<R>, dim3((length + 255) / 256, B), dim3(256), 0, s, (const R*)frames, wave, n_fft, hop, T,
                      length);
 }
@@ -238,8 +185,8 @@ template <typename R>
 static void set_lds_limits() {
   static DeviceOnce attr;
   if (!attr.need()) return;
-  (void)hipFuncSetAttribute((const void*)irfft_frames_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  (void)hipFuncSetAttribute((const void*)stft_project_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  (void)hipFuncSetAttribute((const void*)irfft_frames_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, DFT_LDS_LIMIT);
+  (void)hipFuncSetAttribute((const void*)stft_project_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, DFT_LDS_LIMIT);
 }
 
 template <typename R>
@@ -281,11 +228,13 @@ static int griffin_lim_launch(const R* mag, const R* angles, R* wave, void* work
   // 1e-16 of the phase normalisation does not see: rebuilt is the unnormalised STFT of the same waveform either way
   const R scale = (R)(sqrt(wsum_of(n_fft)) / (double)n_fft);
   const R coef = (R)(momentum / (1.0 + momentum));
-  const dim3 dft_grid(B * ((T + IS_FT - 1) / IS_FT));
+  // the projection is launched with the inverse's byte count, 2 * DFT_FT elements above what its frames need: one number for
+  // the whole chain (the smaller one could move an occupancy boundary of the projection that has not been measured)
+  const size_t lds = dft_inverse_lds<R>(n_fft);
   enqueue_inverse<R>(angles, mag, wave, frames, B, T, n_fft, hop, length, scale, s);
   for (int it = 0; it < n_iter; ++it) {
-    hipLaunchKernelGGL(stft_project_kernel<R>, dft_grid, dim3(256), dft_lds<R>(n_fft), s, (const R*)wave, mag, tprev, next, length,
-                       n_fft, hop, T, coef, (int)(it == 0));
+    hipLaunchKernelGGL(stft_project_kernel<R>, dft_grid(B, T), dim3(256), lds, s, (const R*)wave, mag, tprev, next, length, n_fft,
+                       hop, T, coef, (int)(it == 0));
     enqueue_inverse<R>(next, (const R*)nullptr, wave, frames, B, T, n_fft, hop, length, scale, s);
   }
   return check_launch(who);

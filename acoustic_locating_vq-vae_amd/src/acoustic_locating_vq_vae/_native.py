@@ -747,15 +747,21 @@ def range_flag_to_slot(slot):
     _check(lib().alvq_range_flag_to_slot(_ptr(slot, name="slot"), _stream()), "alvq_range_flag_to_slot")
 
 
+def _call_real(stem, real, *args):
+    """The checked call of ``alvq_<stem>_f32`` or ``alvq_<stem>_f64``, chosen by the real dtype of the call's tensors, on the
+    current stream (the entry points' last argument)."""
+    sfx = {torch.float32: "f32", torch.float64: "f64"}.get(real)
+    if sfx is None:
+        raise RuntimeError("alvq_%s: float32 or float64 only (got %s)" % (stem, real))
+    name = "alvq_%s_%s" % (stem, sfx)
+    _check(getattr(lib(), name)(*args, _stream()), name)
+
+
 def stft_power(wave, n_fft=400, hop=160):
     """Power spectrogram of (B,S) waveforms, fp32 or fp64 (the reference's echoed signal is float64)."""
     B, S = wave.shape
     power = torch.empty((B, n_fft // 2 + 1, 1 + S // hop), device=wave.device, dtype=wave.dtype)
-    if wave.dtype == torch.float64:
-        _check(lib().alvq_stft_power_f64(_ptr(wave, torch.float64, "wave"), _ptr(power, torch.float64), B, S, n_fft, hop,
-                                         _stream()), "alvq_stft_power_f64")
-    else:
-        _check(lib().alvq_stft_power_f32(_ptr(wave, name="wave"), _ptr(power), B, S, n_fft, hop, _stream()), "alvq_stft_power_f32")
+    _call_real("stft_power", wave.dtype, _ptr(wave, wave.dtype, "wave"), _ptr(power, wave.dtype), B, S, n_fft, hop)
     return power
 
 
@@ -764,11 +770,7 @@ def stft_complex(wave, n_fft=400, hop=160):
     B, S = wave.shape
     F, T = n_fft // 2 + 1, 1 + S // hop
     out = torch.empty((B, F, T, 2), device=wave.device, dtype=wave.dtype)
-    if wave.dtype == torch.float64:
-        _check(lib().alvq_stft_complex_f64(_ptr(wave, torch.float64, "wave"), _ptr(out, torch.float64), B, S, n_fft, hop,
-                                           _stream()), "alvq_stft_complex_f64")
-    else:
-        _check(lib().alvq_stft_complex_f32(_ptr(wave, name="wave"), _ptr(out), B, S, n_fft, hop, _stream()), "alvq_stft_complex_f32")
+    _call_real("stft_complex", wave.dtype, _ptr(wave, wave.dtype, "wave"), _ptr(out, wave.dtype), B, S, n_fft, hop)
     return torch.view_as_complex(out)
 
 
@@ -824,9 +826,7 @@ def istft(spec, n_fft=400, hop=160, length=None):
     sr = torch.view_as_real(spec.resolve_conj().contiguous())
     wave = torch.empty((B, length), device=spec.device, dtype=real)
     ws = torch.empty((B, T, n_fft), device=spec.device, dtype=real)
-    name = "alvq_istft_f64" if real == torch.float64 else "alvq_istft_f32"
-    _check(getattr(lib(), name)(_ptr(sr, real, "spec"), _ptr(wave, real), _ptr(ws, real), B, T, n_fft, hop, length, _stream()),
-           name)
+    _call_real("istft", real, _ptr(sr, real, "spec"), _ptr(wave, real), _ptr(ws, real), B, T, n_fft, hop, length)
     return wave
 
 
@@ -843,9 +843,8 @@ def griffin_lim(mag, angles, n_iter, momentum, n_fft, hop, length):
     if nbytes < 0:
         raise RuntimeError("griffin_lim: bad dims (B=%d T=%d n_fft=%d)" % (B, T, n_fft))
     ws = torch.empty((nbytes,), device=mag.device, dtype=torch.uint8)
-    name = "alvq_griffin_lim_f64" if real == torch.float64 else "alvq_griffin_lim_f32"
-    _check(getattr(lib(), name)(_ptr(mag, real, "mag"), _ptr(ar, real, "angles"), _ptr(wave, real), _ptr(ws, torch.uint8), B, T,
-                                n_fft, hop, int(length), int(n_iter), float(momentum), _stream()), name)
+    _call_real("griffin_lim", real, _ptr(mag, real, "mag"), _ptr(ar, real, "angles"), _ptr(wave, real), _ptr(ws, torch.uint8), B, T,
+               n_fft, hop, int(length), int(n_iter), float(momentum))
     return wave
 
 
@@ -887,15 +886,14 @@ def rir_rooms(src, rcv, room, beta, c, fs, nsample, order=-1, hp_filter=True):
 def _responses(h, who):
     if h.dim() != 2 or h.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("%s: h must be a float32 or float64 (B, n) tensor (got %s %s)" % (who, h.dtype, tuple(h.shape)))
-    return h.shape[0], h.shape[1], "f64" if h.dtype == torch.float64 else "f32"
+    return h.shape[0], h.shape[1]
 
 
 def edc(h):
     """Energy decay curves (alvq_edc_f32 / _f64): h (B, n) float32 or float64 on the GPU -> (B, n) float64 dB."""
-    B, n, sfx = _responses(h, "edc")
+    B, n = _responses(h, "edc")
     out = torch.empty((B, n), device=h.device, dtype=torch.float64)
-    name = "alvq_edc_" + sfx
-    _check(getattr(lib(), name)(_ptr(h, h.dtype, "h"), _ptr(out, torch.float64), B, n, _stream()), name)
+    _call_real("edc", h.dtype, _ptr(h, h.dtype, "h"), _ptr(out, torch.float64), B, n)
     return out
 
 
@@ -903,13 +901,12 @@ def room_acoustics(h, fs, k50, k80, kdirect):
     """Room-acoustic parameters (alvq_room_acoustics_f32 / _f64): h (B, n) float32 or float64 on the GPU -> (out (B, 7)
     float64 with columns t30 t20 edt c50 c80 d50 drr, onset (B,) int32, status (B,) int32).  status is the kernel's per-row
     flag (include/alvq.h) and is not read here."""
-    B, n, sfx = _responses(h, "room_acoustics")
+    B, n = _responses(h, "room_acoustics")
     out = torch.empty((B, 7), device=h.device, dtype=torch.float64)
     onset = torch.empty((B,), device=h.device, dtype=torch.int32)
     status = torch.empty((B,), device=h.device, dtype=torch.int32)
-    name = "alvq_room_acoustics_" + sfx
-    _check(getattr(lib(), name)(_ptr(h, h.dtype, "h"), _ptr(out, torch.float64), _ptr(onset, torch.int32), _ptr(status, torch.int32),
-                                B, n, float(fs), int(k50), int(k80), int(kdirect), _stream()), name)
+    _call_real("room_acoustics", h.dtype, _ptr(h, h.dtype, "h"), _ptr(out, torch.float64), _ptr(onset, torch.int32),
+               _ptr(status, torch.int32), B, n, float(fs), int(k50), int(k80), int(kdirect))
     return out, onset, status
 
 

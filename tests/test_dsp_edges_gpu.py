@@ -78,14 +78,24 @@ def host(t):
 
 
 # ------------------------------------------------------------------------------------------------------------------ STFT
-def run_stft(x, n_fft, hop, prec, cplx):
-    """x (B, S) numpy -> (B, F, T) complex (cplx) or real, from the kernel, outputs pre-filled with NaN."""
+def run_stft(x, n_fft, hop, prec, cplx, captured=False):
+    """x (B, S) numpy -> (B, F, T) complex (cplx) or real, from the kernel, outputs pre-filled with NaN.  captured: the call is
+    not run but captured on the current stream in a graph (one stream, one launch), which is then replayed."""
     B, S = x.shape
     F, T = n_fft // 2 + 1, 1 + S // hop
     xd = dev(x, TDT[prec])
     out = nan((B, F, T, 2) if cplx else (B, F, T), TDT[prec])
     name = "alvq_stft_%s_%s" % ("complex" if cplx else "power", prec)
-    ok(getattr(lib(), name)(xd.data_ptr(), out.data_ptr(), B, S, n_fft, hop, stream()), name)
+    if captured:
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rc = getattr(lib(), name)(xd.data_ptr(), out.data_ptr(), B, S, n_fft, hop, stream())
+        ok(rc, name)
+        assert torch.isnan(out).all(), "%s ran during its capture" % name
+        graph.replay()
+    else:
+        ok(getattr(lib(), name)(xd.data_ptr(), out.data_ptr(), B, S, n_fft, hop, stream()), name)
     o = host(out).astype(np.float64)
     return o[..., 0] + 1j * o[..., 1] if cplx else o
 
@@ -142,6 +152,7 @@ def test_stft_batch_independent_and_deterministic(n_fft, hop, S):
         for cplx in (False, True):
             a = run_stft(x, n_fft, hop, prec, cplx)
             assert np.array_equal(a, run_stft(x, n_fft, hop, prec, cplx)), (prec, cplx)
+            assert np.array_equal(a, run_stft(x, n_fft, hop, prec, cplx, captured=True)), (prec, cplx, "graph replay")
             for b in range(5):
                 assert np.array_equal(a[b], run_stft(x[b:b + 1], n_fft, hop, prec, cplx)[0]), (prec, cplx, b)
 

@@ -1,7 +1,9 @@
 """Bitwise fingerprint of the f16mx / bf16 / bf16x3 / f16 kernels' outputs on a fixed set of deterministic cases: run once per
 library build (ALVQ_LIB=...), diff the JSON lines.  A kernel rewrite that claims "bit-identical" must leave every hash
 unchanged.     ALVQ_LIB=$PWD/acoustic_locating_vq-vae_amd/lib/libalvq_base.so python3 tools/ab_bits.py > a.json
-               python3 tools/ab_bits.py > b.json && diff a.json b.json"""
+               python3 tools/ab_bits.py > b.json && diff a.json b.json
+The modes above are the default; ``python3 tools/ab_bits.py dsp`` fingerprints the waveform front end instead (STFT power and
+complex, the inverse STFT of each complex result, Griffin-Lim), in fp32 and fp64."""
 import hashlib
 import json
 import os
@@ -32,9 +34,36 @@ def digest(*tensors):
     return h.hexdigest()[:16]
 
 
+# (B, S, n_fft, hop) per precision: the front end's own framing, and the largest n_fft of each precision at a hop of 3
+DSP_CASES = {torch.float32: [(3, 1601, 400, 160), (2, 1031, 2048, 3)],
+             torch.float64: [(3, 1601, 400, 160), (2, 1031, 1024, 3)]}
+
+
+def dsp():
+    out = {}
+    for real, cases in DSP_CASES.items():
+        prec = "f64" if real == torch.float64 else "f32"
+        for (B, S, n_fft, hop) in cases:
+            g = torch.Generator(device="cuda").manual_seed(B * 1000 + S + n_fft + hop)
+            x = torch.randn(B, S, device="cuda", dtype=real, generator=g)
+            spec = N.stft_complex(x, n_fft, hop)
+            out["dsp:stft:%s:%s" % (prec, (B, S, n_fft, hop))] = {
+                "power": digest(N.stft_power(x, n_fft, hop)), "complex": digest(torch.view_as_real(spec)),
+                "istft": digest(N.istft(spec, n_fft, hop))}
+        B, S, n_fft, hop = cases[0]                          # T = 11
+        g = torch.Generator(device="cuda").manual_seed(B + S + n_fft + hop)
+        shape = (B, n_fft // 2 + 1, 1 + S // hop)
+        mag = torch.rand(shape, device="cuda", dtype=real, generator=g)
+        angles = torch.view_as_complex(torch.rand(shape + (2,), device="cuda", dtype=real, generator=g))
+        wave = N.griffin_lim(mag, angles, 4, 0.99, n_fft, hop, S)
+        out["dsp:griffin_lim:%s:%s" % (prec, (B, S, n_fft, hop))] = {"wave": digest(wave)}
+    return out
+
+
 def main():
     modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3", "f16"]
-    out = {}
+    out = dsp() if "dsp" in modes else {}
+    modes = [m for m in modes if m != "dsp"]
     shapes = [(2, 7, 16, 13, 3), (3, 72, 136, 95, 1), (2, 201, 1024, 500, 3), (2, 1024, 128, 500, 3), (2, 1024, 1024, 201, 1),
               (5, 130, 130, 129, 3), (4, 1024, 1024, 500, 1), (4, 1024, 1024, 500, 3), (3, 1024, 201, 500, 3), (2, 500, 1024, 201, 3)]
     for mode in modes:
