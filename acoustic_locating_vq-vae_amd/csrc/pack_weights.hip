@@ -235,12 +235,16 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(float* p, const floa
 
 using namespace alvq;
 
+// pack_store8 writes 16-byte runs into the images, adam_pack_batch_kernel reads and writes w, g, m, v with 16-byte vectors
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 extern "C" int alvq_pack_weights_bf16_batch(const alvq_pack_desc* descs, int n, int planes, void* stream) {
   ALVQ_REQUIRE(descs && n > 0, ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: no descriptors");
   ALVQ_REQUIRE(planes >= 1 && planes <= 3, ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: planes=%d (1, 2 or 3)", planes);
   for (int i = 0; i < n; ++i) {
     const alvq_pack_desc& s = descs[i];
     ALVQ_REQUIRE(s.w && s.wp, ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: null pointer in descriptor %d", i);
+    ALVQ_REQUIRE(aligned16(s.wp), ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: misaligned image in descriptor %d (16 bytes)", i);
     ALVQ_REQUIRE(s.M > 0 && s.C > 0 && (s.KW == 1 || s.KW == 3), ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: bad dims in descriptor %d", i);
     ALVQ_REQUIRE(s.w_layout == ALVQ_W_OIK || s.w_layout == ALVQ_W_IOK, ALVQ_EINVAL, "alvq_pack_weights_bf16_batch: w_layout in descriptor %d", i);
   }
@@ -273,6 +277,10 @@ extern "C" int alvq_adam_pack_batch(const alvq_adam_pack_desc* descs, int n, int
   for (int i = 0; i < n; ++i) {
     const alvq_adam_pack_desc& s = descs[i];
     ALVQ_REQUIRE(s.w && s.g && s.m && s.v, ALVQ_EINVAL, "alvq_adam_pack_batch: null pointer in descriptor %d", i);
+    ALVQ_REQUIRE(aligned16(s.w) && aligned16(s.g) && aligned16(s.m) && aligned16(s.v), ALVQ_EINVAL,
+                 "alvq_adam_pack_batch: misaligned w / g / m / v in descriptor %d (16 bytes)", i);
+    ALVQ_REQUIRE(aligned16(s.wp_oik) && aligned16(s.wp_iok), ALVQ_EINVAL,
+                 "alvq_adam_pack_batch: misaligned image in descriptor %d (16 bytes)", i);
     ALVQ_REQUIRE(s.dim0 > 0 && s.dim1 > 0 && (s.KW == 1 || s.KW == 3), ALVQ_EINVAL, "alvq_adam_pack_batch: bad dims in descriptor %d", i);
   }
   for (int i0 = 0; i0 < n; i0 += AP_MAX) {
@@ -304,12 +312,13 @@ extern "C" int alvq_adam_segments_f32(float* param, const float* grad, float* ex
                                       const float* skip, void* stream) {
   ALVQ_REQUIRE(param && grad && exp_avg && exp_avg_sq && scalars && lo && hi, ALVQ_EINVAL, "alvq_adam_segments_f32: null pointer");
   ALVQ_REQUIRE(nseg > 0, ALVQ_EINVAL, "alvq_adam_segments_f32: no segments");
+  for (int i = 0; i < nseg; ++i)          // every segment before the first launch: a refusal leaves nothing half updated
+    ALVQ_REQUIRE(lo[i] >= 0 && hi[i] > lo[i], ALVQ_EINVAL, "alvq_adam_segments_f32: bad segment %d", i);
   for (int i0 = 0; i0 < nseg; i0 += AS_MAX) {
     AdamSegs s{};
     s.n = nseg - i0 < AS_MAX ? nseg - i0 : AS_MAX;
     int blocks = 0;
     for (int i = 0; i < s.n; ++i) {
-      ALVQ_REQUIRE(lo[i0 + i] >= 0 && hi[i0 + i] > lo[i0 + i], ALVQ_EINVAL, "alvq_adam_segments_f32: bad segment %d", i0 + i);
       s.lo[i] = lo[i0 + i]; s.hi[i] = hi[i0 + i];
       s.blk0[i] = blocks;
       blocks += (int)((hi[i0 + i] - lo[i0 + i] + 1023) / 1024);

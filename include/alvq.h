@@ -468,7 +468,9 @@ int alvq_pack_weight_bf16(const float* w, void* wp, int M, int C, int KW, int w_
  * data-gradient layout, after each optimiser update: one launch instead of ~20).  `descs` is a HOST array; it is
  * copied into the kernel argument, so the call can be captured into a hipGraph.  planes = 1: bf16 images;
  * planes = 2: the hi + lo images of the split-bf16 path (as alvq_pack_weight_bf16x3); planes = 3: the H + Q images of
- * the f16mx path (two images of alvq_packed_weight_elems 2-byte units each, weight-class scale). */
+ * the f16mx path (two images of alvq_packed_weight_elems 2-byte units each, weight-class scale).
+ * Every wp must be 16-byte aligned (the images are written in 16-byte runs): a descriptor whose image is not is refused
+ * with ALVQ_EINVAL, naming the descriptor, before anything is launched. */
 typedef struct alvq_pack_desc {
   const float* w;   /* fp32 weight, (M,C,KW) for ALVQ_W_OIK or (C,M,KW) for ALVQ_W_IOK */
   void* wp;         /* packed image(s): planes * alvq_packed_weight_elems(M,C,KW) bf16 values */
@@ -481,7 +483,10 @@ int alvq_pack_weights_bf16_batch(const alvq_pack_desc* descs, int n, int planes,
  * alvq_adam_dev_f32, bit for bit, scalars = {lr/bias_correction1, sqrt(bias_correction2), grad_scale} on the device -- and
  * write the updated weight's packed image read as OIK (wp_oik: M = dim0, C = dim1) and / or as IOK (wp_iok: C = dim0,
  * M = dim1, taps flipped) while the new values are in registers.  Images must have been packed in full once before
- * (their padding is not rewritten).  planes as in alvq_pack_weights_bf16_batch.  descs: HOST array. */
+ * (their padding is not rewritten).  planes as in alvq_pack_weights_bf16_batch.  descs: HOST array.
+ * w, g, m, v and every non-NULL image must be 16-byte aligned (full tiles are read and written with 16-byte vectors, the
+ * images in 16-byte runs): a descriptor with a pointer that is not is refused with ALVQ_EINVAL, naming the descriptor,
+ * before anything is launched. */
 typedef struct alvq_adam_pack_desc {
   float* w; const float* g; float* m; float* v;
   void* wp_oik; void* wp_iok;      /* either may be NULL */

@@ -24,7 +24,7 @@ def _planes_equal(a, b):
 
 
 @pytest.mark.parametrize("planes,fmt", FORMATS)
-@pytest.mark.parametrize("B,L,C", [(3, 201, 500), (1, 7, 5), (2, 64, 64), (5, 33, 130), (32, 201, 500)])
+@pytest.mark.parametrize("B,L,C", [(3, 201, 500), (1, 7, 5), (2, 64, 64), (5, 33, 130), (32, 201, 500), (1, 1, 1), (2, 3, 65)])
 def test_rows_to_nlc_equals_transpose_then_convert(B, L, C, planes, fmt):
     from acoustic_locating_vq_vae import _native as N
     x = torch.randn(B, L, C, generator=torch.Generator().manual_seed(B * 1000 + L)).cuda() * 3.0
@@ -44,6 +44,22 @@ def test_fused_standardise_is_bit_identical_to_the_three_pass_route(B, F, T, tak
     fused = N.rows_to_nlc(raw, planes, fmt, standardise=True, take_abs=take_abs)
     ref = N.ncl_to_nlc(N.transpose12(N.standardise(raw, take_abs=take_abs)), planes, fmt)
     assert _planes_equal(fused, ref)
+
+
+@pytest.mark.parametrize("planes,fmt", FORMATS)
+@pytest.mark.parametrize("take_abs", [False, True])
+def test_fused_standardise_at_the_edges_of_both_axes(take_abs, planes, fmt):
+    """The same identity where the launch geometry changes: F (the reduced axis) from 2 and around its channel groups of 4 to
+    the 240 of the RIR loop, T around the 64-column tile and at 1 (the Wiener target).  The reference route's standardise is
+    itself pinned to float64 at these sizes by tests/test_elementwise_edges_gpu.py."""
+    from acoustic_locating_vq_vae import _native as N
+    for B in (1, 3):
+        for F in (2, 3, 4, 5, 239, 240):
+            for T in (1, 63, 64, 65, 129):
+                raw = (torch.randn(B, F, T, generator=torch.Generator().manual_seed(F + T)) * 2.0 + 0.5).cuda()
+                fused = N.rows_to_nlc(raw, planes, fmt, standardise=True, take_abs=take_abs)
+                ref = N.ncl_to_nlc(N.transpose12(N.standardise(raw, take_abs=take_abs)), planes, fmt)
+                assert _planes_equal(fused, ref), (B, F, T)
 
 
 def test_fused_standardise_refuses_what_it_cannot_hold():
