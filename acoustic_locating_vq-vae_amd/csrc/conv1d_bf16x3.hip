@@ -18,7 +18,9 @@
 #include "alvq_common.h"
 #include "bf16_common.h"
 #include "nlc_host.h"
+#include "wgrad_bias_reduce.h"
 #include "wgrad_reduce.h"
+#include "wgrad_tile.h"
 
 namespace alvq {
 
@@ -358,12 +360,11 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
 }
 
 // ------------------------------------------------------------------------------------------- weight-gradient
-constexpr int WX_MAXSEG = 4;
 struct WgradX3Args {
-  // Up to WX_MAXSEG (dy, x) pairs of identical shape whose products are summed into ONE dW (the R uses of a shared
+  // Up to WGRAD_MAXSEG (dy, x) pairs of identical shape whose products are summed into ONE dW (the R uses of a shared
   // residual weight): virtual row v = seg * total_rows + r, as in the bf16 and f16mx weight gradients.
-  const u16* dy[WX_MAXSEG];
-  const u16* x[WX_MAXSEG];
+  const u16* dy[WGRAD_MAXSEG];
+  const u16* x[WGRAD_MAXSEG];
   int nseg;
   float* partial;
   float* bias_partial;   // [splits][Mp] column sums of dY (the bias gradient), or null
@@ -372,101 +373,22 @@ struct WgradX3Args {
   int mtiles, ctiles, splits, chunks_per_split, total_rows;
 };
 
-typedef unsigned long long u64x;
-template <int ROW_BYTES>
-__device__ __forceinline__ void tr_issue(unsigned lds_addr, u64x& lo, u64x& hi) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(lds_addr));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(lds_addr), "n"(16 * ROW_BYTES));
-}
-__device__ __forceinline__ bf16x8_t tr_join(u64x lo, u64x hi) {
-  typedef u64x u64x2 __attribute__((ext_vector_type(2)));
-  const u64x2 v = {lo, hi};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 template <int KW, int NCF>
 __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args a) {
-  constexpr int PAD = (KW - 1) / 2;
   constexpr int MT = 128, CT = 4 * NCF * 16;
-  constexpr int YRB = MT * 2, XRB = CT * 2;
-  constexpr int XROWS = KW == 1 ? 32 : 36;
-  constexpr int YBYTES = 32 * YRB, XBYTES = XROWS * XRB;
-  constexpr int STAGE = 2 * YBYTES + 2 * XBYTES;      // dY_hi, dY_lo, X_hi, X_lo
-  constexpr int XPIECES = XBYTES / 1024, XROWS_PER_PIECE = 1024 / XRB;
+  typedef WgradSlabs<KW, MT, CT, 2> Slabs;                 // a stage: dY_hi, dY_lo, X_hi, X_lo
+  constexpr int YRB = Slabs::YRB, XRB = Slabs::XRB, YBYTES = Slabs::YBYTES, XBYTES = Slabs::XBYTES;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 2) * 64, wc0 = (wave & 3) * NCF * 16;
-  const int ntile = a.mtiles * a.ctiles;
-  const int id = xcd_remap(blockIdx.x, ntile * a.splits);
-  const int split = id / ntile, t_id = id % ntile;
-  const int m0 = (t_id / a.ctiles) * MT, c0 = (t_id % a.ctiles) * CT;
-  const int vrows = a.nseg * a.total_rows;
-  const int rbeg = split * a.chunks_per_split * 64;
-  const int rend = min(vrows, rbeg + a.chunks_per_split * 64);
-  const int n = (rend - rbeg) / 32;
+  const WgradWork w = wgrad_work<MT, CT>(a);
+  const int n = w.n;
+  WgradStager<WgradX3Args, KW, MT, CT, 2, WgradDmaAsm> st(a, wave, lane, w);
 
-  const int y_r = lane >> 4, y_s = lane & 15;
-  const int x_r = (lane * 16) / XRB, x_s = ((lane * 16) % XRB) >> 4;
-  auto src_slot = [](int slot, int row) { return (slot & 16) | (((((slot >> 1) & 7) ^ (row & 7)) << 1) | (slot & 1)); };
-  const int last_row = a.total_rows - 1;
-  const unsigned lds0 = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)lds;
-  // LDS-DMA as inline asm (scalar base + 32-bit lane offset): invisible to the compiler, which would otherwise drain
-  // the whole ring (s_waitcnt vmcnt(0)) in front of every fragment read
-  auto dma = [&](const char* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-  };
-  int is_seg = rbeg / a.total_rows;          // segment and first row (inside it) of the K-tile the next issue() stages
-  int is_row = rbeg - is_seg * a.total_rows;
-  auto issue = [&](int stage) {
-    const unsigned dst = lds0 + stage * STAGE;
-    const char* const dy_hi = (const char*)a.dy[is_seg];
-    const char* const dy_lo = (const char*)(a.dy[is_seg] + a.dy_plane);
-    const char* const x_hi = (const char*)a.x[is_seg];
-    const char* const x_lo = (const char*)(a.x[is_seg] + a.x_plane);
-    {
-      const int lr = 4 * wave + y_r;
-      const int mcol = min(m0 + src_slot(y_s, lr) * 8, a.Mp - 8);
-      const unsigned off = (unsigned)(((long)(is_row + lr) * a.Mp + mcol) * 2);
-      dma(dy_hi, off, dst + wave * 1024);
-      dma(dy_lo, off, dst + YBYTES + wave * 1024);
-    }
-#pragma unroll
-    for (int q = 0; q < (XPIECES + 7) / 8; ++q) {
-      const int p = wave + 8 * q;
-      if (p < XPIECES) {
-        const int lr = p * XROWS_PER_PIECE + x_r;
-        int gr = is_row - PAD + lr;
-        gr = gr < 0 ? 0 : (gr > last_row ? last_row : gr);
-        const int ccol = min(c0 + src_slot(x_s, lr) * 8, a.Cp - 8);
-        const unsigned off = (unsigned)(((long)gr * a.Cp + ccol) * 2);
-        dma(x_hi, off, dst + 2 * YBYTES + p * 1024);
-        dma(x_lo, off, dst + 2 * YBYTES + XBYTES + p * 1024);
-      }
-    }
-    is_row += 32;
-    if (is_row == a.total_rows) {
-      is_row = 0;
-      ++is_seg;
-    }
-  };
-
-  const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-  const int krow = 4 * g + q4;
-  int ybase, xbase[KW];
-  ybase = krow * YRB + ((krow & 7) << 5) + p4 * 8;
-#pragma unroll
-  for (int t = 0; t < KW; ++t) xbase[t] = (krow + t) * XRB + (((krow + t) & 7) << 5) + p4 * 8;
-  int yseg[4], xseg[NCF], xline[NCF];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) yseg[mi] = ((wm0 >> 4) + mi) << 5;
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf) {
-    const int cb = (wc0 >> 4) + cf;
-    xseg[cf] = (cb & 7) << 5;
-    xline[cf] = (cb >> 3) * 256;
-  }
+  int ybase, xbase[KW], yseg[4], xseg[NCF], xline[NCF];
+  wgrad_frag16_bases<KW, NCF, YRB, XRB>(lane, wm0, wc0, ybase, xbase, yseg, xseg, xline);
 
   f32x4 acc[KW][4][NCF];
 #pragma unroll
@@ -477,7 +399,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
       for (int j = 0; j < NCF; ++j) acc[t][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // bias gradient = column sums of dY (hi + lo): the workgroups of c-tile 0 multiply their dY fragments by an all-ones
   // operand as well (one wave per 64 m), instead of a separate pass re-reading dY
-  const bool do_bias = a.bias_partial != nullptr && c0 == 0 && (wave & 3) == 0;
+  const bool do_bias = a.bias_partial != nullptr && w.c0 == 0 && (wave & 3) == 0;
   f32x4 accb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -494,19 +416,11 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
   // the lo fragments are read during phase 1, the next K-tile's hi fragments during phase 3 (A hi and the X set that
   // phase 2 has finished with are dead by then), and the two X fragment sets swap roles from one K-tile to the next.
   bf16x8_t ah[4], al[4], b0[KW][NCF], b1[KW][NCF];
-  typedef short s16x4_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) s16x4_t* lds_tr_ptr;
-  // two transposing reads (k rows r..r+3 and r+16..r+19 of one 16-column block) -> one 8-element k fragment; through
-  // the builtin the two halves land directly in the halves of the fragment's register tuple (no copies)
-#define WX_TR(DST, BYTE_OFF, ROW_BYTES)                                                                              \
-  {                                                                                                                  \
-    const s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(lds + (BYTE_OFF)));                    \
-    const s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(lds + (BYTE_OFF) + 16 * (ROW_BYTES))); \
-    DST = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));                  \
-  }
-#define WX_RDA(DST, STAGE, PLANE, MI) WX_TR(DST[MI], (STAGE) * STAGE_B + (PLANE) * YBYTES + (ybase ^ yseg[MI]), YRB)
-#define WX_RDB(DST, STAGE, PLANE, TP, CF) \
-  WX_TR(DST[TP][CF], (STAGE) * STAGE_B + 2 * YBYTES + (PLANE) * XBYTES + ((xbase[TP] ^ xseg[CF]) + xline[CF]), XRB)
+#define WX_RDA(DST, STAGE, PLANE, MI) \
+  DST[MI] = wgrad_tr16_pair<bf16x8_t>(lds + ((STAGE) * STAGE_B + (PLANE) * YBYTES + (ybase ^ yseg[MI])), YRB);
+#define WX_RDB(DST, STAGE, PLANE, TP, CF)                                                                                      \
+  DST[TP][CF] = wgrad_tr16_pair<bf16x8_t>(                                                                                     \
+      lds + ((STAGE) * STAGE_B + 2 * YBYTES + (PLANE) * XBYTES + ((xbase[TP] ^ xseg[CF]) + xline[CF])), XRB);
   // MFMAs of one m-fragment against every (tap, c-fragment) of an X set (tied asm: see the convolution kernel)
 #define WX_MM(A, B, MI)                                                                                    \
   _Pragma("unroll") for (int tp = 0; tp < KW; ++tp)                                                        \
@@ -517,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
 #define WX_BIAS_ON(A, MI) asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(accb[MI]) : "v"(A[MI]), "v"(ones));
 #define WX_BIAS_OFF(A, MI)
 #define WX_SB __builtin_amdgcn_sched_barrier(0);
-  constexpr int STAGE_B = STAGE;
+  constexpr int STAGE_B = Slabs::STAGE;
 
   // one K-tile in stage S; BX = X hi fragments (already in registers), BY receives X lo, then the next tile's X hi
 #define WX_TILE(S, BX, BY, MORE, WX_BIAS)                                                                         \
@@ -532,23 +446,17 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                              \
   __builtin_amdgcn_s_barrier();                                                                            \
   /* phase 3: lo*hi; meanwhile the DMA of K-tile t+2 into this stage and the next tile's hi fragments */   \
-  if (MORE) issue(S);                                                                                      \
+  if (MORE) st.issue(lds, S);                                                                              \
   WX_MM(al, BX, 0) WX_BIAS(al, 0) WX_SB                                                                    \
   WX_RDA(ah, (S) ^ 1, 0, 0) WX_RDA(ah, (S) ^ 1, 0, 1) WX_RDA(ah, (S) ^ 1, 0, 2) WX_RDA(ah, (S) ^ 1, 0, 3)  \
   WX_SB WX_MM(al, BX, 1) WX_BIAS(al, 1) WX_SB                                                              \
   _Pragma("unroll") for (int tp = 0; tp < KW; ++tp) _Pragma("unroll") for (int cf = 0; cf < NCF; ++cf) WX_RDB(BY, (S) ^ 1, 0, tp, cf) \
   WX_SB WX_MM(al, BX, 2) WX_BIAS(al, 2) WX_MM(al, BX, 3) WX_BIAS(al, 3) WX_SB
 
-  const bool extra = (XPIECES % 8 != 0) && (wave < XPIECES % 8);   // this wave stages one more X piece per K-tile
   if (n > 0) {
-    issue(0);
-    if (n > 1) issue(1);
-    if (n > 1) {
-      if (extra) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * ((XPIECES + 7) / 8) + 2) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (XPIECES / 8) + 2) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    st.issue(lds, 0);
+    if (n > 1) st.issue(lds, 1);
+    st.wait_keep(n > 1 ? 1 : 0);   // K-tile 0 landed; K-tile 1's pieces (this wave's count) may stay in flight
     __builtin_amdgcn_s_barrier();
     WX_RDA(ah, 0, 0, 0) WX_RDA(ah, 0, 0, 1) WX_RDA(ah, 0, 0, 2) WX_RDA(ah, 0, 0, 3)
 #pragma unroll
@@ -575,51 +483,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
 #undef WX_BIAS_ON
 #undef WX_BIAS_OFF
 #undef WX_MM
-#undef WX_TR
 #undef WX_RDB
 #undef WX_RDA
 
-  const int li = lane & 15, kq = lane >> 4;
-  float* out = a.partial + (long)split * KW * a.M * a.C;
-#pragma unroll
-  for (int t = 0; t < KW; ++t)
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int cf = 0; cf < NCF; ++cf)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + wm0 + mi * 16 + kq * 4 + r;
-          const int c = c0 + wc0 + cf * 16 + li;
-          if (m < a.M && c < a.C) out[((long)t * a.M + m) * a.C + c] = acc[t][mi][cf][r];
-        }
-  if (do_bias && li == 0) {      // every column j of D holds the same sum; lane li = 0 writes it
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm0 + mi * 16 + kq * 4 + r;
-        if (m < a.Mp) a.bias_partial[(long)split * a.Mp + m] = accb[mi][r];
-      }
-  }
-}
-
-// dbias[m] (+)= sum_s bias_partial[s][m], fixed order
-static __global__ __launch_bounds__(256) void wgrad_x3_bias_reduce_kernel(const float* bp, float* dbias, int splits, int Mp, int M,
-                                                                          int accumulate) {
-  const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m >= M) return;
-  float s = 0.f;
-  int k = 0;
-  for (; k + 8 <= splits; k += 8) {      // eight loads in flight (one at a time is a round trip to L2 per split)
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = bp[(long)(k + j) * Mp + m];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += v[j];
-  }
-  for (; k < splits; ++k) s += bp[(long)k * Mp + m];
-  dbias[m] = accumulate ? dbias[m] + s : s;
+  wgrad_store16<KW, NCF>(a, w, lane, wm0, wc0, acc, do_bias, accb);
 }
 
 __global__ __launch_bounds__(256) void ncl_to_nlc_x3_kernel(const float* x, u16* y, long plane, int B, int C, int L, int Cp,
@@ -688,7 +555,7 @@ __global__ __launch_bounds__(256) void relu_mask_x3_kernel(const u16* dy, const 
 
 template <int KW, int NCF>
 static constexpr int wgrad_x3_lds() {
-  return 2 * (2 * 32 * 256 + 2 * (KW == 1 ? 32 : 36) * (4 * NCF * 16 * 2));
+  return 2 * WgradSlabs<KW, 128, 4 * NCF * 16, 2>::STAGE;
 }
 
 // tile of a launch: 128 m x {128 c x 3 taps | 256 c}
@@ -803,8 +670,8 @@ static int wgrad_x3(const char* who, const void* const* dy, const void* const* x
   if (int rc = table.launch(KW == 3, dim3(a.mtiles * a.ctiles * a.splits), dim3(512), s, "alvq_conv1d_wgrad_bf16x3", a)) return rc;
   wgrad_reduce_launch((const float*)workspace, dw, a.splits, KW, M, C, w_layout, accumulate, s);
   if (dbias)     // single segment only (the shared residual weights have no bias)
-    hipLaunchKernelGGL(wgrad_x3_bias_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const float*)bpart, dbias, a.splits,
-                       a.Mp, M, accumulate);
+    hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const float*)bpart, dbias, a.splits,
+                       a.Mp, M, accumulate, (const float*)nullptr);
   return check_launch("alvq_conv1d_wgrad_bf16x3/reduce");
 }
 

@@ -18,17 +18,17 @@
 #include "f16mx_common.h"
 #include "nlc_host.h"
 #include "wgrad_reduce.h"
+#include "wgrad_tile.h"
 
 namespace alvq {
 
-constexpr int WF_MAXSEG = 4;
 struct WgradFxArgs {
-  // Up to WF_MAXSEG (dy, x) pairs of identical shape whose products are summed into ONE dW: the R uses of a shared
+  // Up to WGRAD_MAXSEG (dy, x) pairs of identical shape whose products are summed into ONE dW: the R uses of a shared
   // residual weight (residual_stack.py:40-41) become a single longer contraction -- one split reduction instead of R.
   // Rows are numbered through all segments: virtual row v = seg * total_rows + r (total_rows % 64 == 0, so neither a
   // 64-row chunk nor a 32-row K-tile straddles two segments).
-  const u16* dy[WF_MAXSEG];
-  const u16* x[WF_MAXSEG];
+  const u16* dy[WGRAD_MAXSEG];
+  const u16* x[WGRAD_MAXSEG];
   int nseg;
   float* partial;        // [splits][KW][M][C]
   const float* inv_scale;   // device scalar multiplied into every partial (1 / loss scale), or null
@@ -45,73 +45,18 @@ struct WgradFxArgs {
 template <int KW, int NC, int MF, bool DBG = false>
 __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs a) {
   const int dbg = DBG ? a.dbg : 0;
-  constexpr int PAD = (KW - 1) / 2;
   constexpr int MT = 2 * MF * 32, CT = 4 * NC * 32;
-  constexpr int YRB = MT * 2, XRB = CT * 2;
-  constexpr int XROWS = KW == 1 ? 32 : 36;
-  constexpr int YBYTES = 32 * YRB, XBYTES = XROWS * XRB;
-  constexpr int STAGE = 2 * YBYTES + 2 * XBYTES;      // dY.H, dY.Q, X.H, X.Q
-  constexpr int XPIECES = XBYTES / 1024, XROWS_PER_PIECE = 1024 / XRB;
-  constexpr int YPIECES = YBYTES / 1024, YROWS_PER_PIECE = 1024 / YRB;     // 8 or 16 pieces per plane: 1 or 2 per wave
+  // a stage: dY.H, dY.Q, X.H, X.Q (the Q plane has a bf16 plane's geometry: 64 bytes per 32 channels)
+  typedef WgradSlabs<KW, MT, CT, 2> Slabs;
+  constexpr int YRB = Slabs::YRB, XRB = Slabs::XRB, YBYTES = Slabs::YBYTES, XBYTES = Slabs::XBYTES, STAGE = Slabs::STAGE;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 2) * (MF * 32), wc0 = (wave & 3) * NC * 32;
-  const int ntile = a.mtiles * a.ctiles;
-  const int id = xcd_remap(blockIdx.x, ntile * a.splits);
-  const int split = id / ntile, t_id = id % ntile;
-  const int m0 = (t_id / a.ctiles) * MT, c0 = (t_id % a.ctiles) * CT;
-  const int vrows = a.nseg * a.total_rows;
-  const int rbeg = split * a.chunks_per_split * 64;
-  const int rend = min(vrows, rbeg + a.chunks_per_split * 64);
-  const int n = (rend - rbeg) / 32;
-
-  // ---- staging: identical to the bf16x3 kernel (the Q plane has a bf16 plane's geometry: 64 bytes per 32 channels)
-  const int y_r = (lane * 16) / YRB, y_s = ((lane * 16) % YRB) >> 4;
-  const int x_r = (lane * 16) / XRB, x_s = ((lane * 16) % XRB) >> 4;
-  auto src_slot = [](int slot, int row) { return (slot & 16) | (((((slot >> 1) & 7) ^ (row & 7)) << 1) | (slot & 1)); };
-  const int last_row = a.total_rows - 1;
-  const unsigned lds0 = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)lds;
-  auto dma = [&](const char* sbase, unsigned voff, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-  };
-  int is_seg = rbeg / a.total_rows;          // segment and first row (inside it) of the K-tile the next issue() stages
-  int is_row = rbeg - is_seg * a.total_rows;
-  auto issue = [&](int stage) {
-    const unsigned dst = lds0 + stage * STAGE;
-    const char* const dy_h = (const char*)a.dy[is_seg];
-    const char* const dy_q = (const char*)(a.dy[is_seg] + a.dy_plane);
-    const char* const x_h = (const char*)a.x[is_seg];
-    const char* const x_q = (const char*)(a.x[is_seg] + a.x_plane);
-#pragma unroll
-    for (int q = 0; q < YPIECES / 8; ++q) {
-      const int p = wave + 8 * q;
-      const int lr = p * YROWS_PER_PIECE + y_r;
-      const int mcol = min(m0 + src_slot(y_s, lr) * 8, a.Mp - 8);
-      const unsigned off = (unsigned)(((long)(is_row + lr) * a.Mp + mcol) * 2);
-      dma(dy_h, off, dst + p * 1024);
-      dma(dy_q, off, dst + YBYTES + p * 1024);
-    }
-#pragma unroll
-    for (int q = 0; q < (XPIECES + 7) / 8; ++q) {
-      const int p = wave + 8 * q;
-      if (p < XPIECES) {
-        const int lr = p * XROWS_PER_PIECE + x_r;
-        int gr = is_row - PAD + lr;
-        gr = gr < 0 ? 0 : (gr > last_row ? last_row : gr);
-        const int ccol = min(c0 + src_slot(x_s, lr) * 8, a.Cp - 8);
-        const unsigned off = (unsigned)(((long)gr * a.Cp + ccol) * 2);
-        dma(x_h, off, dst + 2 * YBYTES + p * 1024);
-        dma(x_q, off, dst + 2 * YBYTES + XBYTES + p * 1024);
-      }
-    }
-    is_row += 32;
-    if (is_row == a.total_rows) {
-      is_row = 0;
-      ++is_seg;
-    }
-  };
+  const WgradWork w = wgrad_work<MT, CT>(a);
+  const int n = w.n;
+  WgradStager<WgradFxArgs, KW, MT, CT, 2, WgradDmaAsm> st(a, wave, lane, w);
 
   // ---- transposed fragment reads.  Lane l: i = l & 15 (lane of its 16-group), blk = (l >> 4) & 1 (which 16-column half
   // of the 32-wide tile), g = l >> 5 (k group of the MFMA).
@@ -126,36 +71,25 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
   //  fp8 (tr_b8: an 8-row x 16-column block; lane 2q+p supplies row q, bytes 8p..8p+7): group g covers rows 16g..16g+15
   //    in two reads, once in the hi8 segment and once in the lo8 segment of the tile's 64-byte chunk.
   const int i16 = lane & 15, blk = (lane >> 4) & 1, g = lane >> 5;
-  const int q4 = i16 >> 2, p4 = i16 & 3;
-  const int krow = 2 * q4 + g;                       // + 8 s for k-step s, + 16 for the second read
   const int qrow = 16 * g + (i16 >> 1);              // + 8 for the second read
   const int qbyte = 16 * blk + 8 * (i16 & 1);
-  typedef short s16x4_t __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) s16x4_t* lds_tr_ptr;
   typedef int i32x2 __attribute__((ext_vector_type(2)));
   typedef __attribute__((address_space(3))) i32x2* lds_tr8_ptr;
-  // Byte offset of (row, 32-byte segment seg) in a slab with ROWB-byte rows: row * ROWB + (seg >> 3) * 256 +
-  // (((seg & 7) ^ (row & 7)) << 5).  The segment of fragment f of a wave is (wave part) + 2 f + (lane part) with the
-  // three parts in disjoint bits, so the XOR factors: offset = LANE BASE ^ (f << 6) (^ 32 for the lo8 segment) -- one
-  // base register per operand and tap instead of one address register per fragment.
+  // H bases: wgrad_frag32_base (wgrad_tile.h).  Q plane, same factoring: byte offset of (row, 32-byte segment seg) in a slab
+  // with ROWB-byte rows = row * ROWB + (seg >> 3) * 256 + (((seg & 7) ^ (row & 7)) << 5); fragment f at LANE BASE ^ (f << 6)
+  // (^ 32 for the lo8 segment).
   const int sA = wm0 >> 4, sB = wc0 >> 4;            // first 16-column block (= 32-byte H segment) of the wave
-  const int aHb = krow * YRB + p4 * 8 + (sA >> 3) * 256 + ((((sA & 7) ^ blk) ^ (krow & 7)) << 5);
+  const int aHb = wgrad_frag32_base<YRB>(i16, blk, g, wm0, 0);
   const int aQb = qrow * YRB + qbyte + (sA >> 3) * 256 + (((sA & 7) ^ (qrow & 7)) << 5);   // Q chunk c = segments 2c, 2c+1
   int bHb[KW], bQb[KW];
 #pragma unroll
   for (int t = 0; t < KW; ++t) {
-    bHb[t] = (krow + t) * XRB + p4 * 8 + (sB >> 3) * 256 + ((((sB & 7) ^ blk) ^ ((krow + t) & 7)) << 5);
+    bHb[t] = wgrad_frag32_base<XRB>(i16, blk, g, wc0, t);
     bQb[t] = (qrow + t) * XRB + qbyte + (sB >> 3) * 256 + (((sB & 7) ^ ((qrow + t) & 7)) << 5);
   }
 
   f16x8_t aH[MF][2], bH[KW][NC][2];
   i32x8 aQ[MF], bQ[KW][NC];
-#define WF_TR16(DST, OFF, ROWB)                                                                                  \
-  {                                                                                                              \
-    const s16x4_t lo_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(lds + (OFF)));                    \
-    const s16x4_t hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(lds + (OFF) + 16 * (ROWB)));      \
-    DST = __builtin_bit_cast(f16x8_t, __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7));                \
-  }
   // FIRST / SECOND: byte offsets of the two 16-row column pieces that form blocks 0 and 1 of the scaled MFMA's operand
 #define WF_TR8(DST, FIRST, SECOND, ROWB)                                                                         \
   {                                                                                                              \
@@ -167,11 +101,12 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
   }
   // A operand (dY), tile MI; B operand (X), tap TP, tile CF: rows shifted by TP; B's blocks are (lo8, hi8) so that block 0
   // pairs dY.hi8 with X.lo8
-#define WF_RDH_A(STAGE_, MI, KS) WF_TR16(aH[MI][KS], (STAGE_) * STAGE + (aHb ^ ((MI) << 6)) + 8 * (KS) * YRB, YRB)
+#define WF_RDH_A(STAGE_, MI, KS) \
+  aH[MI][KS] = wgrad_tr16_pair<f16x8_t>(lds + ((STAGE_) * STAGE + (aHb ^ ((MI) << 6)) + 8 * (KS) * YRB), YRB);
 #define WF_RDQ_A(STAGE_, MI) \
   WF_TR8(aQ[MI], (STAGE_) * STAGE + YBYTES + (aQb ^ ((MI) << 6)), (STAGE_) * STAGE + YBYTES + (aQb ^ ((MI) << 6) ^ 32), YRB)
 #define WF_RDH_B(STAGE_, TP, CF, KS) \
-  WF_TR16(bH[TP][CF][KS], (STAGE_) * STAGE + 2 * YBYTES + (bHb[TP] ^ ((CF) << 6)) + 8 * (KS) * XRB, XRB)
+  bH[TP][CF][KS] = wgrad_tr16_pair<f16x8_t>(lds + ((STAGE_) * STAGE + 2 * YBYTES + (bHb[TP] ^ ((CF) << 6)) + 8 * (KS) * XRB), XRB);
 #define WF_RDQ_B(STAGE_, TP, CF)                                                                 \
   WF_TR8(bQ[TP][CF], (STAGE_) * STAGE + 2 * YBYTES + XBYTES + (bQb[TP] ^ ((CF) << 6) ^ 32),      \
          (STAGE_) * STAGE + 2 * YBYTES + XBYTES + (bQb[TP] ^ ((CF) << 6)), XRB)
@@ -214,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
     __builtin_amdgcn_s_barrier();                                                                                \
   }                                                                                                              \
   /* phase 2: fp8 cross terms; meanwhile the DMA of K-tile t+2 into this stage and the next tile's H fragments */ \
-  if ((MORE) && !(dbg & 1)) issue(S);                                                                            \
+  if ((MORE) && !(dbg & 1)) st.issue(lds, S);                                                                    \
   WF_MMQ(0) WF_SB                                                                                                \
   if (!(dbg & 2)) { WF_ALL_A(WF_RDH_A((S) ^ 1, mi, 0)) WF_ALL_B(WF_RDH_B((S) ^ 1, tp, cf, 0)) } WF_SB            \
   WF_MMQ(1) WF_SB                                                                                                \
@@ -222,16 +157,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
   _Pragma("unroll") for (int mi = 2; mi < MF; ++mi) { WF_MMQ(mi) }                                               \
   WF_SB
 
-  const bool extra = (XPIECES % 8 != 0) && (wave < XPIECES % 8);   // this wave stages one more X piece per K-tile
   if (n > 0) {
-    issue(0);
-    if (n > 1) issue(1);
-    if (n > 1) {   // K-tile 0 landed; K-tile 1's pieces (this wave's count) may stay in flight
-      if (extra) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * ((XPIECES + 7) / 8) + 2 * (YPIECES / 8)) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (XPIECES / 8) + 2 * (YPIECES / 8)) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    st.issue(lds, 0);
+    if (n > 1) st.issue(lds, 1);
+    st.wait_keep(n > 1 ? 1 : 0);   // K-tile 0 landed; K-tile 1's pieces (this wave's count) may stay in flight
     __builtin_amdgcn_s_barrier();
     WF_ALL_A(WF_RDH_A(0, mi, 0) WF_RDH_A(0, mi, 1))
     WF_ALL_B(WF_RDH_B(0, tp, cf, 0) WF_RDH_B(0, tp, cf, 1))
@@ -252,29 +181,13 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
 #undef WF_RDQ_A
 #undef WF_RDH_A
 #undef WF_TR8
-#undef WF_TR16
 
-  // ---- partial[split][t][m][c] = acc / loss scale (fp32); D[i = m][j = c]: lane (j = lane & 31, g), register q holds
-  // m = (q & 3) + 8 (q >> 2) + 4 g
+  // ---- partial[split][t][m][c] = acc / loss scale (fp32)
   if (dbg & 8) {
     if (acc[0][0][0][0] == 12345.678f) a.partial[0] = 1.f;
     return;
   }
-  const float inv = a.inv_scale ? *a.inv_scale : 1.f;
-  const int jc = lane & 31;
-  float* out = a.partial + (long)split * KW * a.M * a.C;
-#pragma unroll
-  for (int t = 0; t < KW; ++t)
-#pragma unroll
-    for (int mi = 0; mi < MF; ++mi)
-#pragma unroll
-      for (int cf = 0; cf < NC; ++cf)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int m = m0 + wm0 + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * g;
-          const int c = c0 + wc0 + cf * 32 + jc;
-          if (m < a.M && c < a.C) out[((long)t * a.M + m) * a.C + c] = acc[t][mi][cf][q] * inv;
-        }
+  wgrad_store32<true, KW, MF, NC>(a, w, lane, g, wm0, wc0, acc, a.inv_scale ? *a.inv_scale : 1.f);
 }
 
 // ---------------------------------------------------------------------------------------------------- bias gradient
@@ -335,7 +248,7 @@ static __global__ __launch_bounds__(256) void wgrad_fx_bias_reduce_kernel(const 
 
 template <int KW, int NC, int MF>
 static constexpr int wgrad_fx_lds() {
-  return 2 * (2 * 32 * (2 * MF * 32 * 2) + 2 * (KW == 1 ? 32 : 36) * (4 * NC * 32 * 2));
+  return 2 * WgradSlabs<KW, 2 * MF * 32, 4 * NC * 32, 2>::STAGE;
 }
 
 // tile of a launch: 128 x 128 x 3 taps for width 3, 256 x 256 for width 1

@@ -3,7 +3,7 @@
 // here, so including it adds nothing to a translation unit's device code.
 //
 // A new instantiation is registered by one put() in its family's table (the slot function takes the template arguments); a
-// new format gets its exports from check_conv_args / check_wgrad_args / check_nlc_dims, a KernelTable and wgrad_plan.
+// new format gets its exports from check_conv_args / check_wgrad_args / check_nlc_dims, a KernelTable and wgrad_plan (wgrad_plan_rows).
 #pragma once
 #include <type_traits>
 
@@ -145,28 +145,35 @@ inline int wgrad_splits(int B, int C, int M, int L, int KW, int nseg, WgradTile 
   return wgrad_split_plan(nseg * (int)alvq_nlc_rows(B, L), t.count(C, M), &cps);
 }
 
-// Fills the argument block of a two-plane weight-gradient launch (WgradX3Args, WgradFxArgs; zero-initialised by the caller):
-// segments, planes, tiles and the split plan, which it holds to what `family`_workspace_bytes sizes.  *bias_partial: where
-// the bias partials start in the workspace.  The launch, the split reduction and the bias reduction are the caller's.
+// Fills what every family's argument block (WgradV2Args, WgradX3Args, WgradFxArgs; zero-initialised by the caller) holds:
+// segments, tiles and the split plan over nseg segments of `rows` rows, which it holds to the bound `family`_workspace_bytes
+// sizes for tile t.  The launch, the split reduction and the bias reduction are the caller's.
 template <class Args>
-inline int wgrad_plan(const char* family, Args& a, const void* const* dy, const void* const* x, int nseg, void* workspace, int B,
-                      int C, int M, int L, int KW, WgradTile t, float** bias_partial) {
+inline int wgrad_plan_rows(const char* family, Args& a, const void* const* dy, const void* const* x, int nseg, void* workspace,
+                           int rows, int C, int M, WgradTile t) {
   static_assert(sizeof(a.dy) / sizeof(a.dy[0]) == WGRAD_MAXSEG && sizeof(a.x) == sizeof(a.dy), "segment count of the family");
-  const int rows = (int)alvq_nlc_rows(B, L);
   for (int i = 0; i < WGRAD_MAXSEG; ++i) {
     a.dy[i] = (const u16*)dy[i < nseg ? i : 0];
     a.x[i] = (const u16*)x[i < nseg ? i : 0];
   }
   a.nseg = nseg;
   a.partial = (float*)workspace;
-  a.dy_plane = nlc_plane_elems(B, L, M);
-  a.x_plane = nlc_plane_elems(B, L, C);
   a.Mp = pad_to(M, 64); a.Cp = pad_to(C, 64); a.M = M; a.C = C;
   a.mtiles = (M + t.mt - 1) / t.mt; a.ctiles = (C + t.ct - 1) / t.ct;
   a.total_rows = rows;
   a.splits = wgrad_split_plan(nseg * rows, a.mtiles * a.ctiles, &a.chunks_per_split);
   ALVQ_REQUIRE(a.splits <= wgrad_split_bound(rows, t.count(C, M), WGRAD_MAXSEG), ALVQ_EINVAL,
                "%s: %d splits exceed what %s_workspace_bytes sizes", family, a.splits, family);
+  return ALVQ_OK;
+}
+
+// The two-plane formats on top of it: the plane offsets too.  *bias_partial: where the bias partials start in the workspace.
+template <class Args>
+inline int wgrad_plan(const char* family, Args& a, const void* const* dy, const void* const* x, int nseg, void* workspace, int B,
+                      int C, int M, int L, int KW, WgradTile t, float** bias_partial) {
+  if (int rc = wgrad_plan_rows(family, a, dy, x, nseg, workspace, (int)alvq_nlc_rows(B, L), C, M, t)) return rc;
+  a.dy_plane = nlc_plane_elems(B, L, M);
+  a.x_plane = nlc_plane_elems(B, L, C);
   *bias_partial = (float*)((char*)workspace + (int64_t)a.splits * KW * M * C * 4);
   return ALVQ_OK;
 }

@@ -7,7 +7,8 @@ Per object: the .hip_fatbin section is dumped, its gfx950 code object unbundled,
 symbol -- the set of kernels, each kernel's disassembly (addresses and address comments stripped) and each kernel's metadata
 entry (registers, LDS, scratch, kernarg layout).  Whole files or whole .text sections are NOT compared: they differ between
 two builds of the same source (the per-build unit id) and whenever the host code names the kernels in another order.
-Prints one line per object and a total; exit status 1 if anything differs."""
+Code and metadata are reported separately ("code of", "metadata of", "code and metadata of"), the changed metadata lines with
+their values.  Prints one line per object and a total; exit status 1 if anything differs."""
 import os
 import re
 import subprocess
@@ -79,12 +80,14 @@ def compare(old_dir, new_dir, tmp):
         for k in bad:
             print("DIFF %s: kernel on one side only: %s" % (f, k))
         for k in sorted(set(a) & set(b)):
-            if a[k][0] != b[k][0]:
+            what = [w for i, w in enumerate(("code", "metadata")) if a[k][i] != b[k][i]]   # reported separately: a kernel whose
+            if what:                                          # code moved may still have to keep its registers, LDS and scratch
                 bad.append(k)
-                print("DIFF %s: code of %s" % (f, k))
-            elif a[k][1] != b[k][1]:
-                bad.append(k)
-                print("DIFF %s: metadata of %s" % (f, k))
+                print("DIFF %s: %s of %s" % (f, " and ".join(what), k))
+            if "metadata" in what:
+                for la, lb in zip(a[k][1].splitlines(), b[k][1].splitlines()):
+                    if la != lb:
+                        print("       %s  ->  %s" % (la.strip(), lb.strip()))
         print("%-28s %3d kernels, %d differences" % (f, len(set(a) | set(b)), len(bad)))
         nobj, nker, ndiff = nobj + 1, nker + len(set(a) | set(b)), ndiff + len(bad)
     return nobj, nker, ndiff
