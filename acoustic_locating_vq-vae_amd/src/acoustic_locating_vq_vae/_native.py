@@ -125,6 +125,14 @@ _SIGNATURES = {
     "alvq_edc_f64": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_room_acoustics_f32": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
     "alvq_room_acoustics_f64": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
+    "alvq_resample_poly_f32": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_resample_poly_f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_stoi_workspace_bytes": (_i64, [_i32] * 2),
+    "alvq_stoi_f64": (_i32, [_c_void_p] * 8 + [_i32] * 2 + [_c_void_p]),
+    "alvq_si_sdr_f32": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
+    "alvq_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
+    "alvq_lsd_f32": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
+    "alvq_lsd_f64": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -908,6 +916,70 @@ def room_acoustics(h, fs, k50, k80, kdirect):
     _call_real("room_acoustics", h.dtype, _ptr(h, h.dtype, "h"), _ptr(out, torch.float64), _ptr(onset, torch.int32),
                _ptr(status, torch.int32), B, n, float(fs), int(k50), int(k80), int(kdirect))
     return out, onset, status
+
+
+# ----------------------------------------------------------------------------------------------- speech measures
+def _row_pair(a, b, who):
+    if a.dim() != 2 or a.dtype not in (torch.float32, torch.float64) or b.shape != a.shape or b.dtype != a.dtype:
+        raise RuntimeError("%s: expected two float32 or two float64 (B, n) tensors of one shape (got %s %s and %s %s)"
+                           % (who, a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    return a.shape[0], a.shape[1]
+
+
+def resample_poly(x, h, up, down):
+    """Rational resampling (alvq_resample_poly_f32 / _f64): x (B, n) float32 or float64 on the GPU, h the (2 half + 1) float64
+    taps on the GPU, up and down coprime -> (B, ceil(n up / down)) float64."""
+    B, n = _responses(x, "resample_poly")
+    if h.dim() != 1 or h.shape[0] % 2 != 1:
+        raise RuntimeError("resample_poly: h must hold an odd number of taps (got %s)" % (tuple(h.shape),))
+    y = torch.empty((B, -(-n * up // down)), device=x.device, dtype=torch.float64)
+    _call_real("resample_poly", x.dtype, _ptr(x, x.dtype, "x"), _ptr(h, torch.float64, "h"), _ptr(y, torch.float64), B, n, int(up),
+               int(down), h.shape[0] // 2)
+    return y
+
+
+def stoi(clean, degraded, band_lo, band_hi):
+    """STOI at 10 kHz (alvq_stoi_f64): clean, degraded (B, n) float64 on the GPU, band_lo / band_hi 15 DFT bins each ->
+    (value (B,) float64, kept_frames (B,) int32, status (B,) int32).  status is the kernel's per-row flag (include/alvq.h) and
+    is not read here."""
+    B, n = _row_pair(clean, degraded, "stoi")
+    if len(band_lo) != 15 or len(band_hi) != 15:
+        raise RuntimeError("stoi: need 15 band edges each (got %d and %d)" % (len(band_lo), len(band_hi)))
+    nbytes = lib().alvq_stoi_workspace_bytes(B, n)
+    if nbytes < 0:
+        raise RuntimeError("stoi: bad dims (B=%d n=%d; need 1 <= B <= 65535, 2 <= n <= 2^24)" % (B, n))
+    dev = clean.device
+    value = torch.empty((B,), device=dev, dtype=torch.float64)
+    kept = torch.empty((B,), device=dev, dtype=torch.int32)
+    status = torch.empty((B,), device=dev, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    lo_c, hi_c = (ctypes.c_int * 15)(*[int(v) for v in band_lo]), (ctypes.c_int * 15)(*[int(v) for v in band_hi])
+    _check(lib().alvq_stoi_f64(_ptr(clean, torch.float64, "clean"), _ptr(degraded, torch.float64, "degraded"),
+                               ctypes.cast(lo_c, _c_void_p), ctypes.cast(hi_c, _c_void_p), _ptr(value, torch.float64),
+                               _ptr(kept, torch.int32), _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, n, _stream()),
+           "alvq_stoi_f64")
+    return value, kept, status
+
+
+def si_sdr(reference, estimate):
+    """Scale-invariant SDR (alvq_si_sdr_f32 / _f64): two (B, n) tensors of one real dtype on the GPU -> (B,) float64 dB."""
+    B, n = _row_pair(reference, estimate, "si_sdr")
+    out = torch.empty((B,), device=reference.device, dtype=torch.float64)
+    _call_real("si_sdr", reference.dtype, _ptr(reference, reference.dtype, "reference"), _ptr(estimate, reference.dtype, "estimate"),
+               _ptr(out, torch.float64), B, n)
+    return out
+
+
+def lsd(p, q, eps):
+    """Log-spectral distance (alvq_lsd_f32 / _f64): power spectrograms p, q (B, F, T) of one real dtype on the GPU -> (B,)
+    float64 dB."""
+    if p.dim() != 3 or p.dtype not in (torch.float32, torch.float64) or q.shape != p.shape or q.dtype != p.dtype:
+        raise RuntimeError("lsd: expected two float32 or two float64 (B, F, T) tensors of one shape (got %s %s and %s %s)"
+                           % (p.dtype, tuple(p.shape), q.dtype, tuple(q.shape)))
+    B, F, T = p.shape
+    out = torch.empty((B,), device=p.device, dtype=torch.float64)
+    _call_real("lsd", p.dtype, _ptr(p, p.dtype, "p"), _ptr(q, p.dtype, "q"), _ptr(out, torch.float64), B, F, T, float(eps))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- t-SNE

@@ -342,6 +342,54 @@ int alvq_room_acoustics_f64(const double* h, double* out, int* onset, int* statu
                             int kdirect, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * What a listener gets from speech (csrc/speech_metrics.hip): rational resampling, STOI, SI-SDR and the log-spectral distance.
+ * Rows are device (B, n), float32 ("_f32") or float64 ("_f64"); all arithmetic and every output is float64 (a float32 sample
+ * is widened first).  1 <= B <= 65535, 2 <= n <= 2^24 (the resampler takes n >= 1).  No atomics, no host sync; every sum runs
+ * in one order that depends on the row's sizes alone: a row has the same bits in any batch and on any run.
+ *
+ * Rational resampling with the semantics of scipy.signal.resample_poly(x, up, down) along the rows.  up and down are coprime,
+ * 1 <= up, down <= 512; h: device (2 half + 1) float64 taps, designed by the caller: with R = max(up, down) and half = 10 R,
+ * h[k] = sinc((k - half) / R) / R * kaiser(beta = 5)[k], normalised to sum 1 and multiplied by up.
+ *   y[m] = sum_j x[j] h[m down - j up + half]  over the j with 0 <= j < n and 0 <= m down - j up + half <= 2 half, j rising,
+ * for 0 <= m < n_out = ceil(n up / down).  y: device (B, n_out) float64.  One launch, no workspace. */
+int alvq_resample_poly_f32(const float* x, const double* h, double* y, int B, int n, int up, int down, int half, void* stream);
+int alvq_resample_poly_f64(const double* x, const double* h, double* y, int B, int n, int up, int down, int half, void* stream);
+
+/* Short-time objective intelligibility (Taal, Hendriks, Heusdens, Jensen 2011) of degraded against clean, both device (B, n)
+ * float64 sampled at 10 kHz.  value: device (B,) float64; kept_frames, status: device (B,) int32.
+ *   W[i]    = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0..255.  Frames of 256 samples at hop 128 lie wholly inside the row:
+ *             nf = (n - 256) / 128 + 1, frame t starts at sample 128 t.
+ *   Silent frames: e_t = 20 log10(|W clean_t|_2 + eps), eps = 2^-52; frame t is kept iff e_t > max_t e_t - 40.  Both signals
+ *             are rebuilt from their kept frames alone (clean's mask for both) by overlap-add of the windowed frames at hop
+ *             128 in their order; M, the number kept, is written to kept_frames.
+ *   Bands:    the rebuilt signals are framed the same way (M frames), windowed with W, zero-padded to 512 and transformed;
+ *             X[j][m] = sqrt(sum_{lo[j] <= k < hi[j]} |DFT_m[k]|^2), 15 one-third-octave bands from 150 Hz.  band_lo_host,
+ *             band_hi_host: 15 host ints each, 0 <= lo < hi <= 257, all within 256 bins of each other -- the caller finds
+ *             the bins nearest the band edges, the library has no rule of its own.
+ *   Segments: for every end s = 30..M and band j, x and y are the 30 envelope values before s of clean and degraded;
+ *             y' = min(y |x| / (|y| + eps), (1 + 10^(15/20)) x); both lose their mean and are divided by their norm + eps;
+ *             d(j, s) is their dot product.  value = the mean of d over the 15 (M - 29) pairs.
+ * status: 0, or 1 = n < 256 or a frame energy of clean is not finite or all are 0 (value NaN, kept_frames 0), or
+ * 2 = M < 30 (value NaN).  The caller reads it when it can sync.  Four launches.  workspace: device,
+ * alvq_stoi_workspace_bytes(B, n) bytes (never 0; -1 for B or n out of range), holding the frame energies, the kept frames'
+ * indices and the envelopes. */
+int64_t alvq_stoi_workspace_bytes(int B, int n);
+int alvq_stoi_f64(const double* clean, const double* degraded, const int* band_lo_host, const int* band_hi_host, double* value,
+                  int* kept_frames, int* status, void* workspace, int B, int n, void* stream);
+
+/* Scale-invariant signal-to-distortion ratio in dB.  With s and e the reference and estimate rows less their means and
+ * a = <e, s> / <s, s>:  out[b] = 10 log10(|a s|^2 / |a s - e|^2); +inf where |a s - e|^2 is 0 (an exact multiple of the
+ * reference); NaN where <s, s> is 0 or not finite.  out: device (B,) float64.  One launch, one workgroup a row. */
+int alvq_si_sdr_f32(const float* reference, const float* estimate, double* out, int B, int n, void* stream);
+int alvq_si_sdr_f64(const double* reference, const double* estimate, double* out, int B, int n, void* stream);
+
+/* Log-spectral distance in dB of power spectrograms p, q: device (B, F, T), T contiguous; F, T >= 1, F T <= 2^30.
+ *   out[b] = mean_t sqrt(mean_f (10 log10((p + eps) / (q + eps)))^2), eps >= 0;
+ * NaN for a spectrogram pair with a negative or non-finite entry.  out: device (B,) float64.  One launch. */
+int alvq_lsd_f32(const float* p, const float* q, double* out, int B, int F, int T, double eps, void* stream);
+int alvq_lsd_f64(const double* p, const double* q, double* out, int B, int F, int T, double eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
