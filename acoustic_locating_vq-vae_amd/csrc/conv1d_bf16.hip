@@ -23,7 +23,7 @@
 
 #include "alvq_common.h"
 #include "bf16_common.h"
-#include "conv1d_bf16_tile256.h"
+#include "conv_tile.h"
 #include "nlc_host.h"
 
 namespace alvq {
@@ -40,9 +40,8 @@ __global__ __launch_bounds__(256, 2) void conv1d_bf16_kernel(ConvBArgs a) {
   const int li = lane & 15, kq = lane >> 4;
   const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
 
-  const int tile = xcd_remap(blockIdx.x, a.mtiles * a.rtiles);
-  const int m0 = (tile % a.mtiles) * TB_M;
-  const int r0 = (tile / a.mtiles) * TB_R;
+  const ConvTileOrigin o = conv_tile_origin<TB_M, TB_R>(a);
+  const int m0 = o.m0, r0 = o.r0;
   const int Cp = a.Cp;
 
   // ---- staging: lane i of a piece writes LDS row (i>>3), 16-B slot (i&7); it fetches source chunk slot^(row&7)
@@ -119,10 +118,12 @@ __global__ __launch_bounds__(256, 2) void conv1d_bf16_kernel(ConvBArgs a) {
     chunk = nchunk;
   }
 
-  if (OUT == 0) {   // NLC bf16: straight from the accumulators (conv1d_bf16_tile256.h)
+  if (OUT == 0) {   // NLC bf16: straight from the accumulators
     wave_epilogue_bf16<4, 4, F16>(a, acc, m0, r0, li, kq, wm0, wn0);
     return;
   }
+  // OUT == 1 keeps its own copy of the fp32-NCL store: through conv_store_ncl (conv_tile.h) the fp16 width-3 instantiation
+  // was 0.6 - 0.8 % slower, above the control's range in both sessions of profiles/conv_tile_ab.txt.
   const float oscale = a.out_scale ? *a.out_scale : 1.f;
   // ---- OUT == 1, step 1: D[i = m][j = row] -> fp32 C tile Cs[row][m] (4 consecutive m per lane = one 16-B write)
   float* Cs = (float*)lds;

@@ -12,14 +12,13 @@
 //           are fetched from the other stage meanwhile)
 // Part A = the weight slabs of taps 0 and 1 (4 DMA pieces per wave), part B = tap 2's weights and the activation
 // slab (4 pieces, wave 7 one more for the two halo rows).  One barrier per 96 MFMAs; every DMA piece has more than
-// a full tap phase to land.  LDS rows are 64 B; the weight slabs carry the v2 slot swizzle (slot = group ^
-// {0,3,2,1}[(row>>2)&3]), the activation slab one that stays conflict-free when read 1 or 2 rows further down
-// (slot = group ^ {0,2,0,2}[(row>>2)&3], derivation at lane_off_x below).
+// a full tap phase to land.  LDS rows are 64 B; the weight slabs carry the v2 slot swizzle, the
+// activation slab one that stays conflict-free when read 1 or 2 rows further down (SLAB_KEY_TAPS, conv_tile.h).
 #include <stdlib.h>
 
 #include "alvq_common.h"
 #include "bf16_common.h"
-#include "conv1d_bf16_tile256.h"
+#include "conv_tile.h"
 #include "nlc_host.h"
 
 namespace alvq {
@@ -27,7 +26,7 @@ namespace alvq {
 constexpr int K3_XSLAB = 17 * 1024;                       // 272 rows x 64 B (258 used)
 constexpr int K3_STAGE = 3 * V2_HALF + K3_XSLAB;          // 66560 B
 constexpr int K3_LDS = 2 * K3_STAGE;                      // 133120 B
-static_assert(V2_EPI_LDS <= K3_LDS, "C slab must fit");
+static_assert(C_SLAB_BYTES <= K3_LDS, "C slab must fit");
 
 template <int OUT, int F16 = 0>
 __global__ __launch_bounds__(512, 2) void conv1d_bf16_k3_kernel(ConvBArgs a) {
@@ -37,38 +36,19 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16_k3_kernel(ConvBArgs a) {
   const int li = lane & 15, kq = lane >> 4;
   const int wm0 = (wave >> 2) * 128, wn0 = (wave & 3) * 64;
 
-  const int tile = xcd_remap(blockIdx.x, a.mtiles * a.rtiles);      // same tile order as the v2 kernel
-  const int m0 = (tile % a.mtiles) * V2_M;
-  const int r0 = (tile / a.mtiles) * V2_R;
+  const ConvTileOrigin o = conv_tile_origin<V2_M, V2_R>(a);
+  const int m0 = o.m0, r0 = o.r0;
   const int Cp = a.Cp;
 
-  // ---- DMA source addressing: a piece is 16 rows x 64 B; lane i -> row i>>2, slot i&3 <- channel group
-  // (i&3) ^ h[(row>>2)&3]
-  const int hsel = (lane >> 4) & 3;
-  const int hval = (hsel == 0) ? 0 : (4 - hsel);              // {0,3,2,1}
-  const int srow = lane >> 2, sgrp = (lane & 3) ^ hval;
-  // One 32-bit per-lane byte offset serves every piece; the rest of a piece's source address is wave-uniform and
-  // goes into the instruction's SGPR base.  Written as inline asm: through the builtin, hipcc hoists
-  // (lane offset + k * 16 rows) into five loop-invariant 64-bit VGPR pairs, which this kernel has no room for.
-  const unsigned lane_off = (unsigned)(srow * Cp + sgrp * 8) * 2u;
-  // The ACTIVATION slab uses its own slot swizzle, slot = group ^ {0,2,0,2}[(row>>2)&3]: the taps read it at row
-  // offsets 0, 1, 2, and under the weight slabs' {0,3,2,1} the shifted reads collide two-fold in two of every sixteen
-  // lanes of a ds_read_b128 bank group (18 % of this kernel's LDS cycles were conflicts).  A 16-lane group takes four
-  // row quads with channel groups (a, b, b, a), b = a ^ 1; rows shifted across a quad boundary keep their lane's group
-  // but take the next quad's key, so the key f must make both {f0, f3, f1^1, f2^1} and {f0, f1, f2^1, f3^1}
-  // permutations of 0..3 -- (0, 2, 0, 2) does, (0, 3, 2, 1) only the first.
-  const unsigned lane_off_x = (unsigned)(srow * Cp + ((lane & 3) ^ ((hsel & 1) * 2)) * 8) * 2u;
+  // ---- DMA source addressing: a piece is 16 rows x 64 B; one 32-bit lane offset per slot swizzle (weights, activations)
+  const int srow = slab64_lane(lane).row;
+  const unsigned lane_off = slab64_lane_off(lane, Cp);
+  const unsigned lane_off_x = slab64_lane_off<SLAB_KEY_TAPS>(lane, Cp);
   const long tap_w = (long)a.Mp128 * Cp;
   const long row16 = (long)Cp * 32;                            // bytes per 16 rows
-  const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) unsigned char*)lds);
-  auto dma = [&](const char* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-  };
-  auto dma_x = [&](const char* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off_x), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-  };
+  const unsigned lds0 = lds_addr(lds);
+  auto dma = [&](const char* sbase, unsigned lds_dst) { lds_dma16(sbase, lds_dst, lane_off); };
+  auto dma_x = [&](const char* sbase, unsigned lds_dst) { lds_dma16(sbase, lds_dst, lane_off_x); };
   // part A: waves 0-3 stage tap 0, waves 4-7 tap 1; 64 weight rows (4 pieces) each
   const char* const wA = (const char*)(a.wp + (wave >> 2) * tap_w + ((long)m0 + (wave & 3) * 64) * Cp);
   const unsigned dA = lds0 + (wave >> 2) * V2_HALF + (wave & 3) * 4096;
@@ -97,14 +77,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16_k3_kernel(ConvBArgs a) {
   };
 
   // ---- fragment read addressing: weights as in v2; activations per tap (slab row = local row + tap)
-  const int hl = (li >> 2) & 3;
-  const int loffA = li * 64 + ((kq ^ (hl == 0 ? 0 : 4 - hl)) << 4);
+  const int loffA = slab64_frag16(li, kq, 0);
   int loffX[3];
 #pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int r = li + t;
-    loffX[t] = r * 64 + ((kq ^ (((r >> 2) & 1) * 2)) << 4);
-  }
+  for (int t = 0; t < 3; ++t) loffX[t] = slab64_frag16<SLAB_KEY_TAPS>(li, kq, t);
   const unsigned char* const abase = lds + wm0 * 64 + loffA;
   const unsigned char* const xbase = lds + 3 * V2_HALF + wn0 * 64;
   // Fragment registers: ONE set of weight fragments, refilled in place half by half (the four fragments an MFMA

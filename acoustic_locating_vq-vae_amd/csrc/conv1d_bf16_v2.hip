@@ -14,12 +14,10 @@
 //   4. waits with a COUNTED s_waitcnt vmcnt(4) (K-tile t+3 may stay in flight; t+2 has landed) and meets the
 //      other waves at one raw s_barrier.
 // So DMA latency has two iterations (>= 1024 MFMA cycles) to hide, LDS read latency one, and the two waves of a
-// SIMD alternate on the matrix pipe while the other's loads issue.  LDS rows are 64 B; the 16-B chunk of row r
-// holding channel group g sits in slot g ^ h[(r>>2)&3], h = {0,3,2,1} (applied on the DMA source address and on
-// the read address), which makes every ds_read_b128 fragment read bank-conflict-free.
+// SIMD alternate on the matrix pipe while the other's loads issue.  LDS rows are 64 B, swizzled as conv_tile.h says.
 #include "alvq_common.h"
 #include "bf16_common.h"
-#include "conv1d_bf16_tile256.h"
+#include "conv_tile.h"
 #include "nlc_host.h"
 
 namespace alvq {
@@ -27,7 +25,7 @@ namespace alvq {
 constexpr int V2_STAGE = 2 * V2_HALF;             // 32768 B
 constexpr int V2_NSTAGE = 4;
 constexpr int V2_LDS = V2_NSTAGE * V2_STAGE;      // 131072 B
-static_assert(V2_EPI_LDS <= V2_LDS, "C slab must fit");
+static_assert(C_SLAB_BYTES <= V2_LDS, "C slab must fit");
 
 template <int OUT, int F16 = 0>
 __global__ __launch_bounds__(512, 2) void conv1d_bf16_v2_kernel(ConvBArgs a, int KW) {
@@ -38,20 +36,13 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16_v2_kernel(ConvBArgs a, int
   const int li = lane & 15, kq = lane >> 4;
   const int wm0 = (wave >> 2) * 128, wn0 = (wave & 3) * 64;
 
-  // tile order: all m-tiles of a row tile are neighbours, and each XCD owns a contiguous run of tiles, so the
-  // workgroups resident on an XCD at one time share both operands through its L2 (W: one miss per m-tile per
-  // wave of workgroups; activation rows: one miss per row tile instead of one per m-tile)
-  const int tile = xcd_remap(blockIdx.x, a.mtiles * a.rtiles);
-  const int m0 = (tile % a.mtiles) * V2_M;
-  const int r0 = (tile / a.mtiles) * V2_R;
+  const ConvTileOrigin o = conv_tile_origin<V2_M, V2_R>(a);
+  const int m0 = o.m0, r0 = o.r0;
   const int Cp = a.Cp;
 
-  // ---- DMA source addressing: piece p (16 rows x 64 B); lane i -> row 16p + (i>>2), slot i&3, which must hold
-  // channel group (i&3) ^ h[(row>>2)&3] = (i&3) ^ h[(i>>4)&3]
-  const int hsel = (lane >> 4) & 3;
-  const int hval = (hsel == 0) ? 0 : (4 - hsel);              // {0,3,2,1}
-  const int srow = lane >> 2, sgrp = (lane & 3) ^ hval;
-  const long lane_off = (long)srow * Cp + sgrp * 8;            // elements
+  // ---- DMA source addressing: piece p (16 rows x 64 B); lane i -> row 16p + (i>>2) and the group its slot must hold
+  const Slab64Lane sl = slab64_lane(lane);
+  const long lane_off = (long)sl.row * Cp + sl.grp * 8;        // elements
   const u16* const wbase = a.wp + ((long)m0 + wave * 32) * Cp + lane_off;              // + tap*Mp*Cp + q*16*Cp + chunk*32
   const u16* const xbase = a.x + ((long)r0 - PAD + wave * 32) * Cp + lane_off;         // + tap*Cp      + q*16*Cp + chunk*32
   const long tap_w = (long)a.Mp128 * Cp;
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16_v2_kernel(ConvBArgs a, int
   };
 
   // ---- fragment read addressing (same lane offset for both operands)
-  const int loff = li * 64 + ((kq ^ ((((li >> 2) & 3) == 0) ? 0 : (4 - ((li >> 2) & 3)))) << 4);
+  const int loff = slab64_frag16(li, kq, 0);
   const unsigned char* const abase = lds + wm0 * 64 + loff;
   const unsigned char* const bbase = lds + V2_HALF + wn0 * 64 + loff;
   auto rd = [&](FragSet& f, int stage) {

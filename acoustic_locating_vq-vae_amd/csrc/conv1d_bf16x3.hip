@@ -17,16 +17,13 @@
 
 #include "alvq_common.h"
 #include "bf16_common.h"
+#include "conv_tile.h"
 #include "nlc_host.h"
 #include "wgrad_bias_reduce.h"
 #include "wgrad_reduce.h"
 #include "wgrad_tile.h"
 
 namespace alvq {
-
-constexpr int X3_M = 256, X3_R = 256, X3_K = 32;
-constexpr int X3_SLAB = X3_M * X3_K * 2;          // 16384 B
-constexpr int X3_CS = X3_M + 4;
 
 struct ConvX3Args {
   ConvBArgs b;          // hi planes (and everything shared)
@@ -48,7 +45,7 @@ __device__ __forceinline__ void split_pack8(const float (&v)[8], u32x4& hi, u32x
 }
 
 // Register-direct epilogue of one wave's 128 (m) x 64 (rows) block, split-bf16 flavour of wave_epilogue_bf16
-// (conv1d_bf16_tile256.h): v_permlane16_swap gives every lane 8 consecutive channels, 16-byte loads and stores.  Written,
+// (conv_tile.h): v_permlane16_swap gives every lane 8 consecutive channels, 16-byte loads and stores.  Written,
 // like that one, for few VALU instructions per value: a row block's offset is formed once, the skip / mask operands of
 // the whole row block are requested before the first group is finished, nothing is computed for absent operands, gap
 // rows are zeroed by a select on the packed words inside a wave-uniform branch.
@@ -150,10 +147,8 @@ __device__ __forceinline__ void wave_epilogue_x3(const ConvX3Args& ax, const f32
   }
 }
 
-// Main kernel.  A K-tile = (32 channels, one tap).  Two LDS-DMA rings: the WEIGHT slabs of a K-tile (W hi, W lo; 32 KB, two
-// stages) and the ACTIVATION slabs of a CHUNK of 32 channels (X hi, X lo; rows r0-PAD .. r0+255+PAD staged once, 34 KB,
-// two stages) -- tap t reads the slab t rows further down, as in conv1d_bf16_k3.hip, so a width-3 layer moves a third
-// less through LDS-DMA.  Per wave a K-tile is three phases of 32 MFMAs on the same 8 x 4 accumulators:
+// Main kernel.  A K-tile = (32 channels, one tap), staged through the two rings of conv_tile.h (ConvRings: W hi, W lo per
+// K-tile; X hi, X lo per chunk).  Per wave a K-tile is three phases of 32 MFMAs on the same 8 x 4 accumulators:
 //   phase 1  hi*hi : A0 = W hi fragments, BX = X hi        | meanwhile: read X lo -> BY, first half of W lo -> A1
 //   phase 2  hi*lo : A0, BY                                 | meanwhile: second half of W lo -> A1
 //            s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier      <- K-tile t+1 has landed; every read of this K-tile is done
@@ -164,12 +159,7 @@ __device__ __forceinline__ void wave_epilogue_x3(const ConvX3Args& ax, const f32
 // behind it, every LDS read has at least half a phase (16 MFMAs) to return, and the X fragment sets swap roles from
 // one K-tile to the next (BX <-> BY).  96 fragment VGPRs + 128 accumulators.  MFMAs are tied inline asm (hipcc does
 // not tie the builtin's destination to its C operand and then shuffles the accumulators through spare registers it
-// does not have here); DMA pieces are inline asm with a scalar base and one 32-bit lane offset.
-constexpr int X3_WSTAGE = 2 * X3_SLAB;            // W hi, W lo of one K-tile
-constexpr int X3_XSLAB = 272 * 64;                // 272 rows x 64 B (258 used)
-constexpr int X3_XSTAGE = 2 * X3_XSLAB;           // X hi, X lo of one chunk
-constexpr int X3_LDS2 = 2 * X3_WSTAGE + 2 * X3_XSTAGE;   // 135168 B
-static_assert(64 * X3_CS * 4 <= X3_LDS2, "C slab must fit");
+// does not have here).
 
 // NNI: 16-row fragments per wave.  4 = the 256 x 256 tile (a wave owns 128 channels x 64 rows); 2 (round 4) = a 128-channel
 // m-tile x 256 rows: every wave owns all 128 channels x 32 rows, waves 0-3 stage the 128 weight rows.  For layers of at most
@@ -181,9 +171,9 @@ static_assert(64 * X3_CS * 4 <= X3_LDS2, "C slab must fit");
 template <int OUT, int KW, int NNI = 4>
 __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
   static_assert(NNI == 4 || NNI == 2 || NNI == 1, "4, 2 or 1 row fragments per wave");
-  constexpr int PAD = (KW - 1) / 2;
-  constexpr int MT = NNI == 4 ? X3_M : 128;
-  constexpr int RT = NNI == 1 ? 128 : X3_R;
+  typedef ConvRings G;
+  constexpr int MT = NNI == 4 ? G::M : 128;
+  constexpr int RT = NNI == 1 ? 128 : G::R;
   const ConvBArgs& a = ax.b;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -191,66 +181,35 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
   const int li = lane & 15, kq = lane >> 4;
   const int wm0 = NNI == 4 ? (wave >> 2) * 128 : 0, wn0 = NNI == 4 ? (wave & 3) * 64 : wave * 16 * NNI;
 
-  const int tile = xcd_remap(blockIdx.x, a.mtiles * a.rtiles);
-  const int m0 = (tile % a.mtiles) * MT;
-  const int r0 = (tile / a.mtiles) * RT;
+  const ConvTileOrigin o = conv_tile_origin<MT, RT>(a);
+  const int m0 = o.m0, r0 = o.r0;
   const int Cp = a.Cp;
-
-  // ---- DMA: a piece is 16 rows x 64 B; lane i -> row i>>2, slot i&3 <- channel group (i&3) ^ h[(row>>2)&3]
-  const int hsel = (lane >> 4) & 3;
-  const int hval = (hsel == 0) ? 0 : (4 - hsel);
-  const int srow = lane >> 2, sgrp = (lane & 3) ^ hval;
-  const unsigned lane_off = (unsigned)(srow * Cp + sgrp * 8) * 2u;
-  const long tap_w = (long)a.Mp128 * Cp * 2;                   // bytes per tap of packed weights
-  const long row16 = (long)Cp * 32;                            // bytes per 16 rows
-  const long wpl = ax.wp_plane * 2, xpl = ax.x_plane * 2;      // hi -> lo plane, bytes
-  const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) unsigned char*)lds);
-  auto dma = [&](const char* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-  };
+  // ---- DMA sources (ConvRingStager, conv_tile.h, says what each is): plane 0 = hi, plane 1 = lo
+  const int srow = slab64_lane(lane).row;
+  const unsigned lane_off = slab64_lane_off(lane, Cp);
+  const long tap_w = (long)a.Mp128 * Cp * 2;
+  const long row16 = (long)Cp * 32;
+  const long wpl = ax.wp_plane * 2, xpl = ax.x_plane * 2;
   const char* const wb = (const char*)(a.wp + ((long)m0 + wave * 32) * Cp);
-  const char* const xb = (const char*)(a.x + ((long)r0 - PAD + wave * 32) * Cp);
-  constexpr unsigned XBASE = 2 * X3_WSTAGE;
-  auto issueW = [&](int t) {   // K-tile t -> weight stage t & 1: 32 rows of W hi and of W lo per wave
-    if (wave * 32 >= MT) return;       // 128-channel m-tile: waves 0-3 stage the weight rows
-    const int chunk = t / KW, tap = t - chunk * KW;
-    const unsigned dst = lds0 + (t & 1) * X3_WSTAGE + wave * 2048;
-    const char* ws = wb + tap * tap_w + chunk * (X3_K * 2);
-    dma(ws, dst);
-    dma(ws + row16, dst + 1024);
-    dma(ws + wpl, dst + X3_SLAB);
-    dma(ws + wpl + row16, dst + X3_SLAB + 1024);
-  };
-  auto issueX = [&](int chunk, int plane) {   // one plane of a chunk's activation slab -> activation stage chunk & 1
-    if (wave * 32 >= RT) return;       // 128-row tile: waves 0-3 stage the activation rows
-    const unsigned dst = lds0 + XBASE + (chunk & 1) * X3_XSTAGE + plane * X3_XSLAB + wave * 2048;
-    const char* xs = xb + plane * xpl + chunk * (X3_K * 2);
-    dma(xs, dst);
-    dma(xs + row16, dst + 1024);
-    if (KW == 3 && wave == RT / 32 - 1 && srow < 2) dma(xs + 2 * row16, dst + 2048);   // halo: slab rows RT, RT + 1
-  };
+  const char* const xb = (const char*)(a.x + ((long)r0 - (KW - 1) / 2 + wave * 32) * Cp);
+  const ConvRingStager<KW, MT, RT, false> st(wave, srow, lane_off, tap_w, row16, wpl, xpl, wb, xb);
 
   // ---- fragment reads (plane 0 = hi, 1 = lo); activations of tap t: slab row = local row + t
-  const int hl = (li >> 2) & 3;
-  const int loffA = li * 64 + ((kq ^ (hl == 0 ? 0 : 4 - hl)) << 4);
+  const int loffA = slab64_frag16(li, kq, 0);
   int loffB[KW];
 #pragma unroll
-  for (int t = 0; t < KW; ++t) {
-    const int r = li + t, h = (r >> 2) & 3;
-    loffB[t] = r * 64 + ((kq ^ (h == 0 ? 0 : 4 - h)) << 4);
-  }
+  for (int t = 0; t < KW; ++t) loffB[t] = slab64_frag16(li, kq, t);
   const unsigned char* const abase = lds + wm0 * 64 + loffA;
-  const unsigned char* const bbase = lds + XBASE + wn0 * 64;
+  const unsigned char* const bbase = lds + G::XBASE + wn0 * 64;
   bf16x8_t fa0[8], fa1[8], fb0[NNI], fb1[NNI];
 #define X3_RDA(DST, HALF, WS, PLANE)                                                               \
   {                                                                                                \
-    const unsigned char* pa_ = abase + (WS) * X3_WSTAGE + (PLANE) * X3_SLAB;                       \
+    const unsigned char* pa_ = abase + (WS) * G::WSTAGE + (PLANE) * G::SLAB;                       \
     _Pragma("unroll") for (int mi = (HALF) * 4; mi < (HALF) * 4 + 4; ++mi) DST[mi] = *(const bf16x8_t*)(pa_ + mi * 1024); \
   }
 #define X3_RDB(DST, XS, TAP, PLANE)                                                                \
   {                                                                                                \
-    const unsigned char* pb_ = bbase + (XS) * X3_XSTAGE + (PLANE) * X3_XSLAB + loffB[TAP];         \
+    const unsigned char* pb_ = bbase + (XS) * G::XSTAGE + (PLANE) * G::XSLAB + loffB[TAP];         \
     _Pragma("unroll") for (int ni = 0; ni < NNI; ++ni) DST[ni] = *(const bf16x8_t*)(pb_ + ni * 1024); \
   }
 
@@ -265,22 +224,13 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
       asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[mi][ni]) : "v"(A[mi]), "v"(B[ni]));
 #define X3_SB __builtin_amdgcn_sched_barrier(0);
 
-  const int nch = Cp / X3_K;        // chunks; even (Cp % 64 == 0)
+  const int nch = Cp / G::K;        // chunks; even (Cp % 64 == 0)
   const int n = nch * KW;           // K-tiles
   const bool early = wave < 4;      // the two waves of a SIMD issue their DMA at different points of phase 3
 
   // ---- prologue: chunk 0's activation slabs, K-tiles 0 and 1 (and, for width 1, chunk 1's slabs) staged; hi fragments
   // of K-tile 0 in A0 / fb0
-  issueX(0, 0);
-  issueX(0, 1);
-  issueW(0);
-  if (n > 1) issueW(1);
-  if (KW == 1 && nch > 1) {
-    issueX(1, 0);
-    issueX(1, 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  st.prologue(lds, n, nch);
   X3_RDA(fa0, 0, 0, 0)
   X3_RDA(fa0, 1, 0, 0)
   X3_RDB(fb0, 0, 0, 0)
@@ -303,17 +253,17 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
     // two chunks (six K-tiles) per iteration: every stage index and the BX / BY roles are constants
     for (int c = 0; c < nch; c += 2) {
       const int t = 3 * c;
-      X3_TILE(0, 0, 0, 1, 0, 1, fb0, fb1, if (t + 2 < n) issueW(t + 2); if (c + 1 < nch) issueX(c + 1, 0);)
-      X3_TILE(1, 0, 1, 0, 0, 2, fb1, fb0, if (t + 3 < n) issueW(t + 3); if (c + 1 < nch) issueX(c + 1, 1);)
-      X3_TILE(0, 0, 2, 1, 1, 0, fb0, fb1, if (t + 4 < n) issueW(t + 4);)
-      X3_TILE(1, 1, 0, 0, 1, 1, fb1, fb0, if (t + 5 < n) issueW(t + 5); if (c + 2 < nch) issueX(c + 2, 0);)
-      X3_TILE(0, 1, 1, 1, 1, 2, fb0, fb1, if (t + 6 < n) issueW(t + 6); if (c + 2 < nch) issueX(c + 2, 1);)
-      X3_TILE(1, 1, 2, 0, 0, 0, fb1, fb0, if (t + 7 < n) issueW(t + 7);)
+      X3_TILE(0, 0, 0, 1, 0, 1, fb0, fb1, if (t + 2 < n) st.issueW(lds, t + 2); if (c + 1 < nch) st.issueX(lds, c + 1, 0);)
+      X3_TILE(1, 0, 1, 0, 0, 2, fb1, fb0, if (t + 3 < n) st.issueW(lds, t + 3); if (c + 1 < nch) st.issueX(lds, c + 1, 1);)
+      X3_TILE(0, 0, 2, 1, 1, 0, fb0, fb1, if (t + 4 < n) st.issueW(lds, t + 4);)
+      X3_TILE(1, 1, 0, 0, 1, 1, fb1, fb0, if (t + 5 < n) st.issueW(lds, t + 5); if (c + 2 < nch) st.issueX(lds, c + 2, 0);)
+      X3_TILE(0, 1, 1, 1, 1, 2, fb0, fb1, if (t + 6 < n) st.issueW(lds, t + 6); if (c + 2 < nch) st.issueX(lds, c + 2, 1);)
+      X3_TILE(1, 1, 2, 0, 0, 0, fb1, fb0, if (t + 7 < n) st.issueW(lds, t + 7);)
     }
   } else {
     for (int t = 0; t < n; t += 2) {
-      X3_TILE(0, 0, 0, 1, 1, 0, fb0, fb1, if (t + 2 < n) { issueW(t + 2); issueX(t + 2, 0); issueX(t + 2, 1); })
-      X3_TILE(1, 1, 0, 0, 0, 0, fb1, fb0, if (t + 3 < n) { issueW(t + 3); issueX(t + 3, 0); issueX(t + 3, 1); })
+      X3_TILE(0, 0, 0, 1, 1, 0, fb0, fb1, if (t + 2 < n) { st.issueW(lds, t + 2); st.issueX(lds, t + 2, 0); st.issueX(lds, t + 2, 1); })
+      X3_TILE(1, 1, 0, 0, 0, 0, fb1, fb0, if (t + 3 < n) { st.issueW(lds, t + 3); st.issueX(lds, t + 3, 0); st.issueX(lds, t + 3, 1); })
     }
   }
 #undef X3_TILE
@@ -330,33 +280,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
     return;
   }
   __syncthreads();   // the C slab overlays the stages: the trailing fragment reads of every wave must be done
-  // ---- OUT == 1 (fp32 NCL, bias only): four 64-row slabs through an fp32 LDS tile
-  float* Cs = (float*)lds;
-  const int Lp1 = a.L + 1, ndata = a.B * Lp1;
-  for (int slab = 0; slab < RT / 64; ++slab) {
-    if ((wn0 >> 6) == slab) {          // the waves that own rows of this 64-row slab (four of them; two / four in the narrow tiles)
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NNI; ++ni) {
-          const int rl = (wn0 & 63) + ni * 16 + li, ml = wm0 + mi * 16 + kq * 4;
-          *(f32x4*)(Cs + rl * X3_CS + ml) = acc[mi][ni];
-        }
-    }
-    __syncthreads();
-    {
-      const int rl = tid & 63, row = r0 + slab * 64 + rl;
-      int b, l;
-      if (row_valid(row, Lp1, ndata, &b, &l)) {
-        for (int ml = tid >> 6; ml < MT; ml += 8) {
-          const int m = m0 + ml;
-          if (m >= a.M) break;
-          a.y_ncl[((long)b * a.M + m) * a.L + l] = Cs[rl * X3_CS + ml] + (a.bias ? a.bias[m] : 0.f);
-        }
-      }
-    }
-    __syncthreads();
-  }
+  // ---- OUT == 1: 64-row slabs, each written by the waves that own rows of it (four of them; two / four in the narrow tiles)
+  conv_store_ncl<false, MT, RT>(a, lds, m0, r0, tid, nullptr, [&](float* Cs, int slab) {
+    if ((wn0 >> 6) == slab) store_frags16<C_SLAB_STRIDE>(Cs, acc, li, kq, wm0, wn0 & 63);
+  });
 }
 
 // ------------------------------------------------------------------------------------------- weight-gradient
@@ -385,7 +312,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16x3_kernel(WgradX3Args
   const int wm0 = (wave >> 2) * 64, wc0 = (wave & 3) * NCF * 16;
   const WgradWork w = wgrad_work<MT, CT>(a);
   const int n = w.n;
-  WgradStager<WgradX3Args, KW, MT, CT, 2, WgradDmaAsm> st(a, wave, lane, w);
+  WgradStager<WgradX3Args, KW, MT, CT, 2, LdsDmaAsm> st(a, wave, lane, w);
 
   int ybase, xbase[KW], yseg[4], xseg[NCF], xline[NCF];
   wgrad_frag16_bases<KW, NCF, YRB, XRB>(lane, wm0, wc0, ybase, xbase, yseg, xseg, xline);
@@ -608,7 +535,7 @@ typedef KernelTable<void (*)(ConvX3Args), 12> X3Table;
 static X3Table x3_table() {
   X3Table t;
   for_values<1, 2, 4>([&](auto nni) { for_values<0, 1>([&](auto out) { for_values<1, 3>([&](auto kw) {
-    t.put(x3_slot(out, kw, nni), conv1d_bf16x3_kernel<out, kw, nni>, X3_LDS2);
+    t.put(x3_slot(out, kw, nni), conv1d_bf16x3_kernel<out, kw, nni>, ConvRings::LDS);
   }); }); });
   return t;
 }
@@ -622,7 +549,7 @@ extern "C" int alvq_conv1d_bf16x3(const void* x, const void* wp, const float* bi
   const long rows = alvq_nlc_rows(B, L);
   ConvX3Args a{{(const u16*)x, (const u16*)wp, bias, (const u16*)skip1, (const u16*)skip2, (const u16*)mask, (const u16*)post,
                 (u16*)y, (u16*)y2, y_ncl, B, L, pad_to(C, 64), M, pad_to(M, 64), pad_to(M, WP_ROWS), relu ? 1 : 0,
-                (int)(rows / X3_R), pad_to(M, X3_M) / X3_M},
+                (int)(rows / ConvRings::R), pad_to(M, ConvRings::M) / ConvRings::M},
                nlc_plane_elems(B, L, C), (long)alvq_packed_weight_elems(M, C, KW), nlc_plane_elems(B, L, M)};
   static const X3Table table = x3_table();
   static DeviceOnce attr;

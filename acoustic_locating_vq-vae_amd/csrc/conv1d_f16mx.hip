@@ -2,9 +2,9 @@
 // layers alike, plus the boundary conversions of the format.
 //
 // Tiling is that of conv1d_bf16x3.hip -- 256 out-channels x 256 rows per workgroup, 8 waves, a wave owns 128 x 64;
-// K-tile = (32 channels, one tap) -- with two LDS-DMA rings: the weight slabs (W.H, W.Q; 32 KB) per K-tile and the
-// activation slabs (X.H, X.Q; 34 KB) per CHUNK of 32 channels, shared by the taps as in conv1d_bf16_k3.hip.  The wave's
-// block is 4 x 2 tiles of 32x32 and a K-tile is TWO phases of 512 matrix-pipe cycles:
+// K-tile = (32 channels, one tap) -- with the two LDS-DMA rings of conv_tile.h (ConvRings: W.H, W.Q per K-tile; X.H, X.Q
+// per chunk, shared by the taps).  The wave's block is 4 x 2 tiles of 32x32 and a K-tile is TWO phases of 512 matrix-pipe
+// cycles:
 //   phase 1  fp16 main term : 2 k-steps x 8 v_mfma_f32_32x32x16_f16          | meanwhile: the Q fragments of this K-tile
 //            s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier    <- K-tile t+1 landed; every read of this stage is done
 //   phase 2  fp8 cross terms: 8 v_mfma_scale_f32_32x32x64_f8f6f4              | meanwhile: DMA of K-tile t+2 into THIS
@@ -13,19 +13,11 @@
 #include <stdlib.h>
 
 #include "alvq_common.h"
+#include "conv_tile.h"
 #include "f16mx_common.h"
 #include "nlc_host.h"
 
 namespace alvq {
-
-constexpr int FX_M = 256, FX_R = 256, FX_K = 32;
-constexpr int FX_SLAB = FX_M * FX_K * 2;          // 16384 B
-constexpr int FX_WSTAGE = 2 * FX_SLAB;            // W.H, W.Q of one K-tile
-constexpr int FX_XSLAB = 272 * 64;                // 272 rows x 64 B (258 used: 256 + a halo row either side)
-constexpr int FX_XSTAGE = 2 * FX_XSLAB;           // X.H, X.Q of one chunk
-constexpr int FX_LDS = 2 * FX_WSTAGE + 2 * FX_XSTAGE;   // 135168 B
-constexpr int FX_CS = FX_M + 4;
-static_assert(64 * FX_CS * 4 <= FX_LDS, "C slab must fit");
 
 struct ConvFxArgs {
   ConvBArgs b;                        // H planes (and everything shared); mask_bits / bits_out unused
@@ -234,7 +226,7 @@ __device__ __forceinline__ void wave_epilogue_fx(const ConvFxArgs& ax, const f32
 // NIN = 1) for layers of at most 128 output channels, whose 256-wide tile would spend half of its MFMAs on padding.
 template <int OUT, int KW, int DBG = 0, int NIN = 2, int MIN = 4>
 __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
-  constexpr int PAD = (KW - 1) / 2;
+  typedef ConvRings G;
   constexpr int RT = 128 * NIN;          // rows per workgroup
   constexpr int MT = 64 * MIN;           // output channels per workgroup
   const int dbg = DBG ? ax.dbg : 0;
@@ -244,92 +236,48 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 2) * 32 * MIN, wn0 = (wave & 3) * 32 * NIN;
 
-  const int tile = xcd_remap(blockIdx.x, a.mtiles * a.rtiles);
-  const int m0 = (tile % a.mtiles) * MT;
-  const int r0 = (tile / a.mtiles) * RT;
+  const ConvTileOrigin o = conv_tile_origin<MT, RT>(a);
+  const int m0 = o.m0, r0 = o.r0;
   const int Cp = a.Cp;
-
-  // ---- DMA (a piece is 16 rows x 64 B; lane i -> row i>>2, slot i&3 <- 16-byte group (i&3) ^ h[(row>>2)&3] of the
-  // row's 64-byte chunk; plane 0 = H, plane 1 = Q).  Two rings: the WEIGHT slabs of one K-tile (32 channels, one tap) and
-  // the ACTIVATION slabs of one CHUNK (32 channels, all taps): rows r0-PAD .. r0+255+PAD are staged once and tap t reads
-  // the slab t rows further down, so a width-3 layer moves 3 x 32 KB of weights + 34 KB of activations per chunk through
-  // LDS-DMA instead of 3 x 64 KB -- a third less DMA issue and L2 -> LDS traffic for the same MFMAs.
-  const int hsel = (lane >> 4) & 3;
-  const int hval = (hsel == 0) ? 0 : (4 - hsel);
-  const int srow = lane >> 2, sgrp = (lane & 3) ^ hval;
-  const unsigned lane_off = (unsigned)(srow * Cp + sgrp * 8) * 2u;
+  // ---- DMA sources (ConvRingStager, conv_tile.h, says what each is): plane 0 = H, plane 1 = Q; the pieces are issued one at a
+  // time so that each can sit in the shadow of an MFMA
+  const int srow = slab64_lane(lane).row;
+  const unsigned lane_off = slab64_lane_off(lane, Cp);
   const long tap_w = (long)a.Mp128 * Cp * 2;
   const long row16 = (long)Cp * 32;
   const long wpl = ax.wp_plane * 2, xpl = ax.x_plane * 2;
-  const unsigned lds0 = (unsigned)(unsigned long)((__attribute__((address_space(3))) unsigned char*)lds);
-  auto dma = [&](const char* sbase, unsigned lds_dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-  };
   const char* const wb = (const char*)(a.wp + ((long)m0 + wave * 32) * Cp);
-  const char* const xb = (const char*)(a.x + ((long)r0 - PAD + wave * 32) * Cp);
-  constexpr unsigned XBASE = 2 * FX_WSTAGE;
-  // K-tile t -> weight stage t & 1: 32 rows of W.H and of W.Q per wave = pieces 0..3 (issued one at a time so that each
-  // can sit in the shadow of an MFMA)
-  auto pieceW = [&](int t, int k) {
-    if (wave * 32 >= MT) return;          // 128-channel m-tile: waves 0-3 stage the weight rows
-    const int chunk = t / KW, tap = t - chunk * KW;
-    const unsigned dst = lds0 + (t & 1) * FX_WSTAGE + wave * 2048 + (k >> 1) * FX_SLAB + (k & 1) * 1024;
-    dma(wb + tap * tap_w + chunk * (FX_K * 2) + (k >> 1) * wpl + (k & 1) * row16, dst);
-  };
-  auto issueW = [&](int t) {
-    pieceW(t, 0);
-    pieceW(t, 1);
-    pieceW(t, 2);
-    pieceW(t, 3);
-  };
-  // one plane of a chunk's activation slab -> activation stage chunk & 1: pieces 0, 1 (+ the halo rows 256, 257)
-  auto pieceX = [&](int chunk, int plane, int k) {
-    const unsigned dst = lds0 + XBASE + (chunk & 1) * FX_XSTAGE + plane * FX_XSLAB + wave * 2048;
-    const char* xs = xb + plane * xpl + chunk * (FX_K * 2);
-    if (wave * 32 >= RT) return;          // 128-row tile: waves 0-3 stage the activation rows
-    if (k < 2) dma(xs + k * row16, dst + k * 1024);
-    else if (KW == 3 && wave == RT / 32 - 1 && srow < 2) dma(xs + 2 * row16, dst + 2048);
-  };
-  auto issueX = [&](int chunk, int plane) {
-    pieceX(chunk, plane, 0);
-    pieceX(chunk, plane, 1);
-    pieceX(chunk, plane, 2);
-  };
+  const char* const xb = (const char*)(a.x + ((long)r0 - (KW - 1) / 2 + wave * 32) * Cp);
+  const ConvRingStager<KW, MT, RT, true> st(wave, srow, lane_off, tap_w, row16, wpl, xpl, wb, xb);
 
   // ---- fragment reads for the 32x32 shapes: lane (r = lane & 31, g = lane >> 5) takes the 16-byte groups g and 2 + g of
   // row r of a 32-row block.  H slab: group g = k-step 0 (channels 8g..8g+7), group 2+g = k-step 1.  Q slab: group g =
   // hi8[16g..16g+15], group 2+g = lo8[16g..16g+15]; the A operand wants (hi8, lo8), the B operand (lo8, hi8), so that
-  // block 0 of the scaled MFMA pairs A.hi8 with B.lo8 and block 1 A.lo8 with B.hi8.  The slot swizzle of the staging
-  // (slot = group ^ {0,3,2,1}[(row>>2)&3]) makes the un-shifted reads conflict-free for this lane pattern too; the
-  // activation reads of tap t use slab row r + t.
+  // block 0 of the scaled MFMA pairs A.hi8 with B.lo8 and block 1 A.lo8 with B.hi8.  The slot swizzle of the staging makes
+  // the un-shifted reads conflict-free for this lane pattern too; the activation reads of tap t use slab row r + t.
   const int r32 = lane & 31, g = lane >> 5;
   int offA[2], offB[KW][2];
-  {
-    const int hq = (r32 >> 2) & 3, hsw = hq == 0 ? 0 : 4 - hq;
-    offA[0] = r32 * 64 + ((g ^ hsw) << 4);
-    offA[1] = r32 * 64 + (((2 + g) ^ hsw) << 4);
-  }
+  offA[0] = slab64_frag32(r32, g, 0);
+  offA[1] = slab64_frag32(r32, 2 + g, 0);
 #pragma unroll
   for (int t = 0; t < KW; ++t) {
-    const int rr = r32 + t, hq = (rr >> 2) & 3, hsw = hq == 0 ? 0 : 4 - hq;
-    offB[t][0] = rr * 64 + ((g ^ hsw) << 4);
-    offB[t][1] = rr * 64 + (((2 + g) ^ hsw) << 4);
+    offB[t][0] = slab64_frag32(r32, g, t);
+    offB[t][1] = slab64_frag32(r32, 2 + g, t);
   }
   const unsigned char* const abase = lds + wm0 * 64;
-  const unsigned char* const bbase = lds + XBASE + wn0 * 64;
+  const unsigned char* const bbase = lds + G::XBASE + wn0 * 64;
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   f16x8_t aH[4][2], bH[2][2];
   i32x8 aQ[4], bQ[2];
-#define FX_RDH_A(WS, MI, KS) if ((MI) < MIN) aH[MI][KS] = *(const f16x8_t*)(abase + (WS) * FX_WSTAGE + (MI) * 2048 + offA[KS]);
-#define FX_RDH_B(XS, TAP, NI, KS) if ((NI) < NIN) bH[NI][KS] = *(const f16x8_t*)(bbase + (XS) * FX_XSTAGE + (NI) * 2048 + offB[TAP][KS]);
+#define FX_RDH_A(WS, MI, KS) if ((MI) < MIN) aH[MI][KS] = *(const f16x8_t*)(abase + (WS) * G::WSTAGE + (MI) * 2048 + offA[KS]);
+#define FX_RDH_B(XS, TAP, NI, KS) if ((NI) < NIN) bH[NI][KS] = *(const f16x8_t*)(bbase + (XS) * G::XSTAGE + (NI) * 2048 + offB[TAP][KS]);
 #define FX_RDQ(DST, P, FIRST, SECOND)                                                           \
   {                                                                                             \
     const i32x4 q0_ = *(const i32x4*)((P) + (FIRST)), q1_ = *(const i32x4*)((P) + (SECOND));    \
     DST = __builtin_shufflevector(q0_, q1_, 0, 1, 2, 3, 4, 5, 6, 7);                            \
   }
-#define FX_RDQ_A(WS, MI) if ((MI) < MIN) FX_RDQ(aQ[MI], abase + (WS) * FX_WSTAGE + FX_SLAB + (MI) * 2048, offA[0], offA[1])
-#define FX_RDQ_B(XS, TAP, NI) if ((NI) < NIN) FX_RDQ(bQ[NI], bbase + (XS) * FX_XSTAGE + FX_XSLAB + (NI) * 2048, offB[TAP][1], offB[TAP][0])
+#define FX_RDQ_A(WS, MI) if ((MI) < MIN) FX_RDQ(aQ[MI], abase + (WS) * G::WSTAGE + G::SLAB + (MI) * 2048, offA[0], offA[1])
+#define FX_RDQ_B(XS, TAP, NI) if ((NI) < NIN) FX_RDQ(bQ[NI], bbase + (XS) * G::XSTAGE + G::XSLAB + (NI) * 2048, offB[TAP][1], offB[TAP][0])
 
   // block scales of the fp8 MFMA: lanes 0-31 supply block 0, lanes 32-63 block 1.  Opaque to the compiler so that it keeps
   // them in registers instead of re-materialising them by VALU moves in front of the inline-asm MFMAs (no hazard padding
@@ -351,7 +299,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
         : "+v"(acc[MI][NI]) : "v"(aQ[MI]), "v"(bQ[NI]), "v"(sa), "v"(sb));
 #define FX_SB __builtin_amdgcn_sched_barrier(0);
 
-  const int nch = Cp / FX_K;        // chunks; even (Cp % 64 == 0)
+  const int nch = Cp / G::K;        // chunks; even (Cp % 64 == 0)
   const int n = nch * KW;           // K-tiles
   const bool early = wave < 4;      // the two waves of a SIMD issue their DMA at different points of phase 2
 
@@ -359,16 +307,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
   if (DBG) st0 = __builtin_amdgcn_s_memrealtime();
   // ---- prologue: chunk 0's activation slabs, K-tiles 0 and 1 (and, for width 1, chunk 1's slabs) staged; H fragments of
   // K-tile 0 in registers
-  issueX(0, 0);
-  issueX(0, 1);
-  issueW(0);
-  if (n > 1) issueW(1);
-  if (KW == 1 && nch > 1) {
-    issueX(1, 0);
-    issueX(1, 1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  st.prologue(lds, n, nch);
   if (DBG) st1 = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
   for (int mi = 0; mi < MIN; ++mi) { FX_RDH_A(0, mi, 0) FX_RDH_A(0, mi, 1) }
@@ -398,14 +337,14 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                          \
     __builtin_amdgcn_s_barrier();                                                                                        \
   }                                                                                                                      \
-  FX_Q(0, 0) FX_SB FX_DMA_E(if ((TW) >= 0) pieceW(TW, 0);) FX_RD(FX_RDH_B(NXS, NTAP, 0, 0) FX_RDH_A(NWS, 0, 0)) FX_SB     \
-  FX_Q(0, 1) FX_SB FX_DMA_E(if ((TW) >= 0) pieceW(TW, 1);) FX_RD(FX_RDH_B(NXS, NTAP, 1, 0) FX_RDH_A(NWS, 1, 0)) FX_SB     \
-  FX_Q(1, 0) FX_SB FX_DMA_E(if ((TW) >= 0) pieceW(TW, 2);) FX_RD(FX_RDH_A(NWS, 2, 0) FX_RDH_A(NWS, 3, 0)) FX_SB           \
-  FX_Q(1, 1) FX_SB FX_DMA_E(if ((TW) >= 0) pieceW(TW, 3);) FX_RD(FX_RDH_B(NXS, NTAP, 0, 1) FX_RDH_B(NXS, NTAP, 1, 1)) FX_SB \
-  FX_Q(2, 0) FX_SB FX_DMA_L(if ((TW) >= 0) { pieceW(TW, 0); pieceW(TW, 1); }) FX_RD(FX_RDH_A(NWS, 0, 1) FX_RDH_A(NWS, 1, 1)) FX_SB \
-  FX_Q(2, 1) FX_SB FX_DMA_L(if ((TW) >= 0) { pieceW(TW, 2); pieceW(TW, 3); }) FX_RD(FX_RDH_A(NWS, 2, 1) FX_RDH_A(NWS, 3, 1)) FX_SB \
-  FX_Q(3, 0) FX_SB if (!(dbg & 1) && (XC) >= 0) { pieceX(XC, XP, 0); pieceX(XC, XP, 1); pieceX(XC, XP, 2); } FX_SB       \
-  FX_Q(3, 1) FX_SB if (KW == 1 && !(dbg & 1) && (XC) >= 0) { pieceX(XC, 1, 0); pieceX(XC, 1, 1); } FX_SB
+  FX_Q(0, 0) FX_SB FX_DMA_E(if ((TW) >= 0) st.pieceW(lds, TW, 0);) FX_RD(FX_RDH_B(NXS, NTAP, 0, 0) FX_RDH_A(NWS, 0, 0)) FX_SB     \
+  FX_Q(0, 1) FX_SB FX_DMA_E(if ((TW) >= 0) st.pieceW(lds, TW, 1);) FX_RD(FX_RDH_B(NXS, NTAP, 1, 0) FX_RDH_A(NWS, 1, 0)) FX_SB     \
+  FX_Q(1, 0) FX_SB FX_DMA_E(if ((TW) >= 0) st.pieceW(lds, TW, 2);) FX_RD(FX_RDH_A(NWS, 2, 0) FX_RDH_A(NWS, 3, 0)) FX_SB           \
+  FX_Q(1, 1) FX_SB FX_DMA_E(if ((TW) >= 0) st.pieceW(lds, TW, 3);) FX_RD(FX_RDH_B(NXS, NTAP, 0, 1) FX_RDH_B(NXS, NTAP, 1, 1)) FX_SB \
+  FX_Q(2, 0) FX_SB FX_DMA_L(if ((TW) >= 0) { st.pieceW(lds, TW, 0); st.pieceW(lds, TW, 1); }) FX_RD(FX_RDH_A(NWS, 0, 1) FX_RDH_A(NWS, 1, 1)) FX_SB \
+  FX_Q(2, 1) FX_SB FX_DMA_L(if ((TW) >= 0) { st.pieceW(lds, TW, 2); st.pieceW(lds, TW, 3); }) FX_RD(FX_RDH_A(NWS, 2, 1) FX_RDH_A(NWS, 3, 1)) FX_SB \
+  FX_Q(3, 0) FX_SB if (!(dbg & 1) && (XC) >= 0) { st.pieceX(lds, XC, XP, 0); st.pieceX(lds, XC, XP, 1); st.pieceX(lds, XC, XP, 2); } FX_SB       \
+  FX_Q(3, 1) FX_SB if (KW == 1 && !(dbg & 1) && (XC) >= 0) { st.pieceX(lds, XC, 1, 0); st.pieceX(lds, XC, 1, 1); } FX_SB
 
   if (KW == 3) {
     // two chunks (six K-tiles) per iteration so that every stage index is a constant.  The next chunk's activation slabs
@@ -462,37 +401,20 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
     return;
   }
   __syncthreads();   // the C slab overlays the stages: the trailing fragment reads of every wave must be done
-  // ---- OUT == 1 (fp32 NCL, bias only, optional output scale): 64-row slabs through an fp32 LDS tile
-  float* Cs = (float*)lds;
-  const int Lp1 = a.L + 1, ndata = a.B * Lp1;
-  const float oscale = ax.out_scale ? *ax.out_scale : 1.f;
-  for (int slab = 0; slab < RT / 64; ++slab) {
-    if ((wn0 >> 6) == slab) {
+  // ---- OUT == 1 (optional output scale): 64-row slabs; a 32 x 32 fragment is four 16-byte groups of consecutive m per lane
+  conv_store_ncl<true, MT, RT>(a, lds, m0, r0, tid, ax.out_scale, [&](float* Cs, int slab) {
+    if ((wn0 >> 6) != slab) return;
 #pragma unroll
-      for (int mi = 0; mi < MIN; ++mi)
+    for (int mi = 0; mi < MIN; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NIN; ++ni)
+      for (int ni = 0; ni < NIN; ++ni)
 #pragma unroll
-          for (int q4 = 0; q4 < 4; ++q4) {
-            const int rl = (wn0 & 63) + ni * 32 + r32, ml = wm0 + mi * 32 + 8 * q4 + 4 * g;
-            *(f32x4*)(Cs + rl * FX_CS + ml) =
-                f32x4{acc[mi][ni][4 * q4], acc[mi][ni][4 * q4 + 1], acc[mi][ni][4 * q4 + 2], acc[mi][ni][4 * q4 + 3]};
-          }
-    }
-    __syncthreads();
-    {
-      const int rl = tid & 63, row = r0 + slab * 64 + rl;
-      int b, l;
-      if (row_valid(row, Lp1, ndata, &b, &l)) {
-        for (int ml = tid >> 6; ml < MT; ml += 8) {
-          const int m = m0 + ml;
-          if (m >= a.M) break;
-          a.y_ncl[((long)b * a.M + m) * a.L + l] = (Cs[rl * FX_CS + ml] + (a.bias ? a.bias[m] : 0.f)) * oscale;
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const int rl = (wn0 & 63) + ni * 32 + r32, ml = wm0 + mi * 32 + 8 * q4 + 4 * g;
+          *(f32x4*)(Cs + rl * C_SLAB_STRIDE + ml) =
+              f32x4{acc[mi][ni][4 * q4], acc[mi][ni][4 * q4 + 1], acc[mi][ni][4 * q4 + 2], acc[mi][ni][4 * q4 + 3]};
         }
-      }
-    }
-    __syncthreads();
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ boundary conversions
@@ -743,9 +665,9 @@ static FxTable fx_table() {
   FxTable t;
   for_values<1, 3>([&](auto kw) {
     for_values<0, 1>([&](auto out) { for_values<2, 1>([&](auto nin) {
-      t.put(fx_slot(out, kw, nin, 4), conv1d_f16mx_kernel<out, kw, 0, nin, 4>, FX_LDS);
+      t.put(fx_slot(out, kw, nin, 4), conv1d_f16mx_kernel<out, kw, 0, nin, 4>, ConvRings::LDS);
     }); });
-    t.put(fx_slot(1, kw, 1, 2), conv1d_f16mx_kernel<1, kw, 0, 1, 2>, FX_LDS);
+    t.put(fx_slot(1, kw, 1, 2), conv1d_f16mx_kernel<1, kw, 0, 1, 2>, ConvRings::LDS);
   });
   return t;
 }
@@ -759,7 +681,7 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
   const long rows = alvq_nlc_rows(B, L);
   ConvFxArgs a{{(const u16*)x, (const u16*)wp, bias, (const u16*)skip1, (const u16*)skip2, (const u16*)mask, (const u16*)post,
                 (u16*)y, (u16*)y2, y_ncl, B, L, pad_to(C, 64), M, pad_to(M, 64), pad_to(M, WP_ROWS), relu ? 1 : 0,
-                (int)(rows / FX_R), pad_to(M, FX_M) / FX_M,   /* rtiles: see below */
+                (int)(rows / ConvRings::R), pad_to(M, ConvRings::M) / ConvRings::M,   /* rtiles: see below */
                 (const unsigned char*)mask_bits, (unsigned char*)relu_bits_out},
                nlc_plane_elems(B, L, C), (long)alvq_packed_weight_elems(M, C, KW), nlc_plane_elems(B, L, M),
                FX_E_W, FX_E_ACT, out_scale, fx_range_flag_ptr(), nullptr, 0};
@@ -775,10 +697,10 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
   if (attr.need()) {
     table.raise_lds_limit();
 #ifdef ALVQ_DEBUG_KERNELS
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
-    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, FX_LDS);
+    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvRings::LDS);
+    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvRings::LDS);
+    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvRings::LDS);
+    (void)hipFuncSetAttribute((const void*)conv1d_f16mx_kernel<0, 3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvRings::LDS);
 #endif
   }
   // fewer than ~3/4 of the CUs covered by 256-row tiles (one m-tile: M <= 256; short batches): 128-row tiles
@@ -796,10 +718,10 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
     if ((dbg_env & (256 | 512)) && !stamps) (void)hipMalloc(&stamps, 4096 * 4 * sizeof(unsigned long long));
     a.stamps = stamps;
     if (grid.x > 4096) a.dbg &= ~(256 | 512);
-    if (KW == 3 && (dbg_env & 16)) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 2>), grid, block, FX_LDS, s, a);
-    else if (KW == 3 && (dbg_env & 32)) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 3>), grid, block, FX_LDS, s, a);
-    else if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 1>), grid, block, FX_LDS, s, a);
-    else hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 1, 1>), grid, block, FX_LDS, s, a);
+    if (KW == 3 && (dbg_env & 16)) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 2>), grid, block, ConvRings::LDS, s, a);
+    else if (KW == 3 && (dbg_env & 32)) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 3>), grid, block, ConvRings::LDS, s, a);
+    else if (KW == 3) hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 3, 1>), grid, block, ConvRings::LDS, s, a);
+    else hipLaunchKernelGGL((conv1d_f16mx_kernel<0, 1, 1>), grid, block, ConvRings::LDS, s, a);
     if (a.dbg & (256 | 512)) {     // phase durations of this launch (means over its workgroups; first / last round by start time)
       (void)hipStreamSynchronize(s);
       static unsigned long long h[4096 * 4];

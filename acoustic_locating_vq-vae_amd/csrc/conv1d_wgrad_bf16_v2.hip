@@ -72,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16_v2_kernel(WgradV2Arg
   const int wm0 = (wave >> 2) * 64, wc0 = (wave & 3) * NCF * 16;
   const WgradWork w = wgrad_work<MT, CT>(a);
   const int n = w.n;
-  WgradStager<WgradV2Args, KW, MT, CT, 1, WgradDmaBuiltin> st(a, wave, lane, w);   // glds: the compiler counts them too
+  WgradStager<WgradV2Args, KW, MT, CT, 1, LdsDmaBuiltin> st(a, wave, lane, w);   // glds: the compiler counts them too
 
   // ---- transposed fragment reads
   int ybase, xbase[KW], yseg[4], xseg[NCF], xline[NCF];
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_bf16_v3_kernel(WgradV2Arg
   const int wm0 = (wave >> 2) * (MF * 32), wc0 = (wave & 3) * NC * 32;
   const WgradWork w = wgrad_work<MT, CT>(a);
   const int n = w.n;
-  WgradStager<WgradV2Args, KW, MT, CT, 1, WgradDmaAsm> st(a, wave, lane, w);
+  WgradStager<WgradV2Args, KW, MT, CT, 1, LdsDmaAsm> st(a, wave, lane, w);
 
   // ---- transposed fragment reads
   const int i16 = lane & 15, blk = (lane >> 4) & 1, g = lane >> 5;

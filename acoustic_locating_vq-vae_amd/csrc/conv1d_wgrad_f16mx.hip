@@ -56,7 +56,7 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad_f16mx_kernel(WgradFxArgs 
   const int wm0 = (wave >> 2) * (MF * 32), wc0 = (wave & 3) * NC * 32;
   const WgradWork w = wgrad_work<MT, CT>(a);
   const int n = w.n;
-  WgradStager<WgradFxArgs, KW, MT, CT, 2, WgradDmaAsm> st(a, wave, lane, w);
+  WgradStager<WgradFxArgs, KW, MT, CT, 2, LdsDmaAsm> st(a, wave, lane, w);
 
   // ---- transposed fragment reads.  Lane l: i = l & 15 (lane of its 16-group), blk = (l >> 4) & 1 (which 16-column half
   // of the 32-wide tile), g = l >> 5 (k group of the MFMA).

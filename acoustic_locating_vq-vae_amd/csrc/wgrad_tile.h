@@ -13,6 +13,7 @@
 #pragma once
 #include "alvq_common.h"
 #include "bf16_common.h"
+#include "conv_tile.h"   // the DMA primitives LdsDmaBuiltin / LdsDmaAsm
 
 namespace alvq {
 
@@ -40,25 +41,6 @@ __device__ __forceinline__ int wgrad_src_slot(int slot, int row) {
 }
 
 // --------------------------------------------------------------------------------------------------------------- staging
-// The two DMA primitives: 16 bytes per lane from base[elem] to lds + stage + off (stage, off: wave-uniform byte offsets, kept
-// apart because the two forms add them differently -- the builtin to the pointer stage first, the asm form to the LDS address of
-// `lds` itself, a constant; a sum formed the other way costs either kernel address-space checks inside its loop).
-struct WgradDmaBuiltin {   // visible to the compiler, whose waits the v2 kernel counts against
-  static __device__ __forceinline__ void copy(const u16* base, long elem, unsigned char* lds, int stage, int off) {
-    unsigned char* const dst = lds + stage;
-    glds16(base + elem, dst + off);
-  }
-};
-// Inline asm (scalar base + 32-bit lane offset): invisible to the compiler, which would otherwise drain the whole ring
-// (s_waitcnt vmcnt(0)) in front of every fragment read.
-struct WgradDmaAsm {
-  static __device__ __forceinline__ void copy(const u16* base, long elem, unsigned char* lds, int stage, int off) {
-    const unsigned dst = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)lds + stage + off;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"((unsigned)(elem * 2)), "s"((const char*)base), "s"(dst)
-                 : "memory");
-  }
-};
-
 // One stage of the LDS ring: plane by plane the dY slabs, then the X slabs.  (Host code sizes the ring from STAGE.)
 template <int KW, int MT, int CT, int PLANES>
 struct WgradSlabs {

@@ -3,7 +3,9 @@ library build (ALVQ_LIB=...), diff the JSON lines.  A kernel rewrite that claims
 unchanged.     ALVQ_LIB=$PWD/acoustic_locating_vq-vae_amd/lib/libalvq_base.so python3 tools/ab_bits.py > a.json
                python3 tools/ab_bits.py > b.json && diff a.json b.json
 The modes above are the default; ``python3 tools/ab_bits.py dsp`` fingerprints the waveform front end instead (STFT power and
-complex, the inverse STFT of each complex result, Griffin-Lim), in fp32 and fp64."""
+complex, the inverse STFT of each complex result, Griffin-Lim), in fp32 and fp64.  The ten cases reach only the tiles the default
+dispatch picks: ``python3 tools/ab_bits.py tiles`` repeats the convolution entries of all four modes on two small shapes under
+every forcing of the dispatch options (TILE_FORCINGS), which reaches every instantiation of every forward kernel family."""
 import hashlib
 import json
 import os
@@ -60,10 +62,46 @@ def dsp():
     return out
 
 
+# (B, C, M, L) of tests/test_conv_tile_variants_gpu.py (its docstring says why these), each at widths 1 and 3
+TILE_SHAPES = [(2, 40, 250, 300), (2, 130, 100, 300)]
+# per mode the options that steer its dispatch; "wide_min_tiles" is 1 throughout
+TILE_FORCINGS = {m: [dict(), dict(conv_v2=0), dict(conv_k3=0)] for m in ("bf16", "f16")}
+TILE_FORCINGS.update({m: [dict(fx_narrow=n, fx_rows=r) for n in (0, 1) for r in (0, 128, 256)] for m in ("bf16x3", "f16mx")})
+
+
+def tiles():
+    out = {}
+    for mode, (planes, wpl, fmt) in MODES.items():
+        enter = (lambda t, gs=None: N.ncl_to_nlc(t, planes, fmt, gs)) if fmt else (lambda t, gs=None: N.ncl_to_nlc(t, planes))
+        for (B, C, M, L) in TILE_SHAPES:
+            for KW in (1, 3):
+                g = torch.Generator(device="cuda").manual_seed(B * 1000 + C + M + L + KW)
+                r = lambda *shape: torch.randn(*shape, device="cuda", generator=g)
+                x, w, b = r(B, C, L), r(M, C, KW) / (C * KW) ** 0.5, r(M)
+                s1, s2, mk, post, dy, ds, dm = r(B, M, L), r(B, M, L), r(B, M, L), r(B, M, L), r(B, M, L), r(B, C, L), r(B, C, L)
+                xn, pk, pki = enter(x), N.pack_weight(w, N.W_OIK, wpl), N.pack_weight(w, N.W_IOK, wpl)
+                gs = N.grad_scale(dy) if fmt else None
+                for opts in TILE_FORCINGS[mode]:
+                    prev = {k: N.set_option(k, v) for k, v in dict(opts, wide_min_tiles=1).items()}
+                    try:
+                        res = {"relu": digest(N.conv1d_bf16(xn, pk, b, relu=True)),
+                               "all": digest(*N.conv1d_bf16(xn, pk, b, enter(s1), enter(s2), enter(mk), enter(post), relu=True)),
+                               "ncl": digest(N.conv1d_bf16(xn, pk, b, out_ncl=True)),
+                               "dgrad_skip_mask": digest(N.conv1d_bf16(enter(dy, gs), pki, skip1=enter(ds, gs), mask=enter(dm)))}
+                    finally:
+                        for k, v in prev.items():
+                            N.set_option(k, v)
+                    tag = ",".join("%s=%d" % kv for kv in sorted(opts.items())) or "default"
+                    out["tiles:%s:%s:%s" % (mode, (B, C, M, L, KW), tag)] = res
+    return out
+
+
 def main():
     modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3", "f16"]
     out = dsp() if "dsp" in modes else {}
-    modes = [m for m in modes if m != "dsp"]
+    if "tiles" in modes:
+        out.update(tiles())
+    modes = [m for m in modes if m not in ("dsp", "tiles")]
     shapes = [(2, 7, 16, 13, 3), (3, 72, 136, 95, 1), (2, 201, 1024, 500, 3), (2, 1024, 128, 500, 3), (2, 1024, 1024, 201, 1),
               (5, 130, 130, 129, 3), (4, 1024, 1024, 500, 1), (4, 1024, 1024, 500, 3), (3, 1024, 201, 500, 3), (2, 500, 1024, 201, 3)]
     for mode in modes:

@@ -6,7 +6,9 @@ object file of two build directories (acoustic_locating_vq-vae_amd/build or buil
 Per object: the .hip_fatbin section is dumped, its gfx950 code object unbundled, and three things are compared keyed by kernel
 symbol -- the set of kernels, each kernel's disassembly (addresses and address comments stripped) and each kernel's metadata
 entry (registers, LDS, scratch, kernarg layout).  Whole files or whole .text sections are NOT compared: they differ between
-two builds of the same source (the per-build unit id) and whenever the host code names the kernels in another order.
+two builds of the same source (the per-build unit id) and whenever the host code names the kernels in another order.  The
+literal of the s_add_u32 behind an s_getpc_b64 (the distance from there to a __device__ variable) is blanked: it moves with the
+size of every kernel that lies between, so an untouched kernel of an object whose other kernels changed would differ by it alone.
 Code and metadata are reported separately ("code of", "metadata of", "code and metadata of"), the changed metadata lines with
 their values.  Prints one line per object and a total; exit status 1 if anything differs."""
 import os
@@ -59,7 +61,10 @@ def kernels(co):
             sym = m.group(1)
             code[sym] = []
         elif sym is not None and line.strip() and line.strip() != "...":   # "...": zero padding after the section's last kernel
-            code[sym].append(re.sub(r"\s*//.*$", "", line).strip())
+            ins = re.sub(r"\s*//.*$", "", line).strip()
+            if code[sym] and code[sym][-1].startswith("s_getpc_b64") and ins.startswith("s_add_u32"):
+                ins = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins)
+            code[sym].append(ins)
     return {k: ("\n".join(code.get(k, ["<no code>"])), by_name[k]) for k in by_name}
 
 
