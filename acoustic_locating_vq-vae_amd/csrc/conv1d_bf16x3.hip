@@ -147,6 +147,97 @@ __device__ __forceinline__ void wave_epilogue_x3(const ConvX3Args& ax, const f32
   }
 }
 
+// wave_epilogue_x3 for the two operand sets the forward launches of a train step are made of, on a wave block that lies
+// inside Mop: OPS == 1 skip1 alone, OPS == 2 bias alone (ReLU either way, at run time: it loads nothing).  Same values
+// combined in the same order and stored to the same addresses, but no wait on a load issued behind one of the wave's own
+// stores (gfx950 counts vector loads and stores in ONE counter and retires it in issue order: such a wait also waits for the
+// store's write acknowledgement), and the set is a template argument because behind a branch on an operand's presence the
+// compiler cannot count the loads in flight and waits for all of them, stores included.
+//  * skip1 is 4 bytes per element: all NNI row blocks at once would be 128 registers next to the 128 accumulators.  It goes
+//    one row block ahead through ONE 32-register buffer: block ni + 1 is requested after block ni has been packed (32
+//    registers of hi / lo words, while its 32 accumulators die) and before block ni is stored.
+//  * the bias is added into the accumulators in front of everything: lane (li, kq) of fragment mi holds channels
+//    mi*16 + kq*4 .. +3 of every row block, so a fragment's bias is one 16-byte load for all row blocks, and acc + bias is the
+//    same float on either side of the lane swap.  The loop then loads nothing.
+template <int NNI, int OPS>
+__device__ __forceinline__ void wave_epilogue_x3_ordered(const ConvX3Args& ax, f32x4 (&acc)[8][NNI], int m0, int r0, int li,
+                                                         int kq, int wm0, int wn0) {
+  const ConvBArgs& a = ax.b;
+  const int Lp1 = a.L + 1, ndata = a.B * Lp1;
+  const int mb0 = m0 + wm0 + (kq & 1) * 16 + (kq >> 1) * 8;
+  const long pl = ax.y_plane;
+  const long o00 = (long)(r0 + wn0 + li) * a.Mop + mb0, oblk = (long)16 * a.Mop;
+  u16x8 s1h[4], s1l[4];
+  auto request = [&](int ni) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      s1h[p] = *(const u16x8*)(a.skip1 + o00 + ni * oblk + p * 32);
+      s1l[p] = *(const u16x8*)(a.skip1 + pl + o00 + ni * oblk + p * 32);
+    }
+  };
+  if (OPS == 1) request(0);
+  if (OPS == 2) {
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi) {
+      const int c0 = m0 + wm0 + mi * 16 + kq * 4;
+      f32x4 bv;
+      if (m0 + wm0 + (mi & ~1) * 16 + 32 <= a.M) {     // the pair lies inside M
+        bv = *(const f32x4*)(a.bias + c0);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bv[e] = (c0 + e < a.M) ? a.bias[c0 + e] : 0.f;
+      }
+#pragma unroll
+      for (int ni = 0; ni < NNI; ++ni)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[mi][ni][e] += bv[e];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ni = 0; ni < NNI; ++ni) {
+    int b, l;
+    const bool ok = row_valid(r0 + wn0 + ni * 16 + li, Lp1, ndata, &b, &l);
+    const bool gaps = !__all(ok);
+    u32x4 hi[4], lo[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[2 * p][ni][e]), __float_as_uint(acc[2 * p + 1][ni][e]),
+                                                         false, false);
+        v[e] = __uint_as_float(r[0]);
+        v[e + 4] = __uint_as_float(r[1]);
+      }
+      if (OPS == 1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += bf2f(s1h[p][e]) + bf2f(s1l[p][e]);
+      }
+      if (a.relu & 1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      split_pack8(v, hi[p], lo[p]);
+      if (gaps) {                                           // gap / tail rows stay zero in both planes
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          hi[p][e] = ok ? hi[p][e] : 0u;
+          lo[p][e] = ok ? lo[p][e] : 0u;
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (OPS == 1 && ni + 1 < NNI) request(ni + 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      *(u32x4*)(a.y + o00 + ni * oblk + p * 32) = hi[p];
+      *(u32x4*)(a.y + pl + o00 + ni * oblk + p * 32) = lo[p];
+    }
+  }
+}
+
 // Main kernel.  A K-tile = (32 channels, one tap), staged through the two rings of conv_tile.h (ConvRings: W hi, W lo per
 // K-tile; X hi, X lo per chunk).  Per wave a K-tile is three phases of 32 MFMAs on the same 8 x 4 accumulators:
 //   phase 1  hi*hi : A0 = W hi fragments, BX = X hi        | meanwhile: read X lo -> BY, first half of W lo -> A1
@@ -276,7 +367,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_bf16x3_kernel(ConvX3Args ax) {
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
 
   if constexpr (OUT == 0) {   // bf16 hi + lo planes, straight from the accumulators
-    wave_epilogue_x3(ax, acc, m0, r0, li, kq, wm0, wn0);
+    const bool plain = !a.skip2 && !a.mask && !a.y2 && m0 + wm0 + 128 <= a.Mop;
+    if (plain && a.skip1 && !a.bias) wave_epilogue_x3_ordered<NNI, 1>(ax, acc, m0, r0, li, kq, wm0, wn0);
+    else if (plain && a.bias && !a.skip1) wave_epilogue_x3_ordered<NNI, 2>(ax, acc, m0, r0, li, kq, wm0, wn0);
+    else wave_epilogue_x3(ax, acc, m0, r0, li, kq, wm0, wn0);
     return;
   }
   __syncthreads();   // the C slab overlays the stages: the trailing fragment reads of every wave must be done

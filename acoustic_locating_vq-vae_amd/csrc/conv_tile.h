@@ -254,13 +254,32 @@ template <int NMI, int NNI, int F16 = 0>
 __device__ __forceinline__ void wave_epilogue_bf16(const ConvBArgs& a, const f32x4 (&acc)[NMI][NNI], int m0, int r0, int li,
                                                    int kq, int wm0, int wn0);
 
+// The same for the operand sets of the data gradients, no load behind a store (below).
+template <int NMI, int NNI, int F16, bool S1, bool S2, bool BITS>
+__device__ __forceinline__ void wave_epilogue_dgrad16(const ConvBArgs& a, const f32x4 (&acc)[NMI][NNI], int m0, int r0, int li,
+                                                      int kq, int wm0, int wn0);
+
 // Epilogue of a 256 x 256 tile held as 8 x 4 MFMA fragments per wave (wave w: out-channels (w>>2)*128.., rows (w&3)*64..):
 // OUT == 0 the register-direct one, OUT == 1 (rare at this tile size) four 64-row slabs through conv_store_ncl.
 template <int OUT, int F16 = 0>
 __device__ __forceinline__ void tile256_epilogue(const ConvBArgs& a, const f32x4 (&acc)[8][4], unsigned char* lds, int m0,
                                                  int r0, int wave, int tid, int li, int kq, int wm0) {
   if (OUT == 0) {
-    wave_epilogue_bf16<8, 4, F16>(a, acc, m0, r0, li, kq, wm0, (wave & 3) * 64);
+    // the data gradients' operand sets (a mask, as sign bits or as a tensor; + skip1; + skip1 + skip2) on a wave block that
+    // lies inside Mop take the epilogue whose loads all go out in front of the stores; every other launch the general one
+    const int wn0 = (wave & 3) * 64;
+    const bool dgrad = (a.mask_bits || a.mask) && !a.bias && !a.y2 && !a.bits_out && !(a.relu & 1) && (a.skip1 || !a.skip2) &&
+                       m0 + wm0 + 128 <= a.Mop;
+    if (!dgrad) wave_epilogue_bf16<8, 4, F16>(a, acc, m0, r0, li, kq, wm0, wn0);
+    else if (a.mask_bits) {
+      if (a.skip2) wave_epilogue_dgrad16<8, 4, F16, true, true, true>(a, acc, m0, r0, li, kq, wm0, wn0);
+      else if (a.skip1) wave_epilogue_dgrad16<8, 4, F16, true, false, true>(a, acc, m0, r0, li, kq, wm0, wn0);
+      else wave_epilogue_dgrad16<8, 4, F16, false, false, true>(a, acc, m0, r0, li, kq, wm0, wn0);
+    } else {
+      if (a.skip2) wave_epilogue_dgrad16<8, 4, F16, true, true, false>(a, acc, m0, r0, li, kq, wm0, wn0);
+      else if (a.skip1) wave_epilogue_dgrad16<8, 4, F16, true, false, false>(a, acc, m0, r0, li, kq, wm0, wn0);
+      else wave_epilogue_dgrad16<8, 4, F16, false, false, false>(a, acc, m0, r0, li, kq, wm0, wn0);
+    }
     return;
   }
   conv_store_ncl<true, V2_M, V2_R>(a, lds, m0, r0, tid, a.out_scale, [&](float* Cs, int slab) {
@@ -381,6 +400,111 @@ __device__ __forceinline__ void wave_epilogue_bf16(const ConvBArgs& a, const f32
           bt = __builtin_amdgcn_alignbit(bt, 0u - (unsigned)t, 31);
         }
         a.bits_out[o >> 3] = (unsigned char)bt;
+      }
+    }
+  }
+  if (F16) fp16_report(watch, a.range_flag);
+}
+
+// wave_epilogue_bf16 for what the data gradients of a train step pass -- y = (acc [+ skip1 [+ skip2]]) under a mask (BITS: the
+// sign bits of a 16-bit tensor; else a tensor, as the layers behind a bf16x3 forward pass it), no bias, ReLU, post or
+// bits_out, every fragment pair inside Mop -- with the same values combined in the same order and stored
+// to the same addresses, but NO wait on a load that was issued behind one of the wave's own stores.  gfx950 has one counter
+// (vmcnt) for vector loads and stores and retires it in issue order, so waiting for such a load also waits for the store's
+// write acknowledgement; the general epilogue reads its mask byte inside the group loop and requests every row block's skip
+// operands behind the stores of the block before, which made a wave's sixteen groups sixteen store round trips in series,
+// each as long as an acknowledgement takes when all 256 CUs drain a round together.  Which operands are present is a
+// template argument here, not a branch: behind a branch the compiler cannot count the loads in flight and waits for all of
+// them, stores included (s_waitcnt vmcnt(0)).  Requested before the first store: the lane's sixteen mask bytes and skip1 of
+// all NNI row blocks (64 registers next to the 128 accumulators; the fragment registers are dead).  skip2, which only the
+// stack's first layer passes, would be 64 more, and so would a mask tensor: they go one row block ahead -- block ni + 1's
+// request is issued after block ni has been packed (16 registers) and before block ni's stores, so its wait leaves those
+// stores outstanding.
+template <int NMI, int NNI, int F16, bool S1, bool S2, bool BITS>
+__device__ __forceinline__ void wave_epilogue_dgrad16(const ConvBArgs& a, const f32x4 (&acc)[NMI][NNI], int m0, int r0, int li,
+                                                      int kq, int wm0, int wn0) {
+  static_assert(NMI % 2 == 0, "fragments are swapped in pairs");
+  constexpr int NP = NMI / 2;
+  elem_saturate<F16>();
+  unsigned watch = 0;
+  const int Lp1 = a.L + 1, ndata = a.B * Lp1;
+  const int mb0 = m0 + wm0 + (kq & 1) * 16 + (kq >> 1) * 8;      // this lane's 8 channels of fragment pair 0
+  const long o00 = (long)(r0 + wn0 + li) * a.Mop + mb0;          // element offset of the lane's first group of row block 0
+  const long oblk = (long)16 * a.Mop;                            // ... from one row block to the next
+  int mbits[NNI][NP];
+  u16x8 s1[NNI][NP], s2[NP], mk[NP];
+  auto ahead = [&](int ni) {      // the operands that go one row block ahead
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      if (S2) s2[p] = *(const u16x8*)(a.skip2 + o00 + ni * oblk + p * 32);
+      if (!BITS) mk[p] = *(const u16x8*)(a.mask + o00 + ni * oblk + p * 32);
+    }
+  };
+  if (S1) {
+#pragma unroll
+    for (int ni = 0; ni < NNI; ++ni)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) s1[ni][p] = *(const u16x8*)(a.skip1 + o00 + ni * oblk + p * 32);
+  }
+  ahead(0);
+  // (the mask bytes last: were they the first thing every instantiation does, the compiler would merge them across the
+  // caller's branch on the operand set and wait for them in front of it, one round trip before skip1 is even requested)
+  if (BITS) {
+#pragma unroll
+    for (int ni = 0; ni < NNI; ++ni)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) mbits[ni][p] = (int)a.mask_bits[(o00 + ni * oblk + p * 32) >> 3];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ni = 0; ni < NNI; ++ni) {
+    int b, l;
+    const bool ok = row_valid(r0 + wn0 + ni * 16 + li, Lp1, ndata, &b, &l);
+    const bool gaps = !__all(ok);
+    u32x4 out[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        // odd rows (of 16 lanes) of the first operand <-> even rows of the second
+        const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[2 * p][ni][e]), __float_as_uint(acc[2 * p + 1][ni][e]),
+                                                         false, false);
+        v[e] = __uint_as_float(r[0]);
+        v[e + 4] = __uint_as_float(r[1]);
+      }
+      if (S1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += elem2f<F16>(s1[ni][p][e]);
+      }
+      if (S2) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += elem2f<F16>(s2[p][e]);
+      }
+      if (BITS) {
+        const int bt = mbits[ni][p];     // sign-extend bit e to a word and AND
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = __uint_as_float(__float_as_uint(v[e]) & (unsigned)((bt << (31 - e)) >> 31));
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (short)mk[p][e] > 0 ? v[e] : 0.f;   // a positive bf16 / fp16 is a positive int16
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) out[p][e] = elem_pk<F16>(v[2 * e], v[2 * e + 1]);
+      if (gaps) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[p][e] = ok ? out[p][e] : 0u;
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (ni + 1 < NNI) ahead(ni + 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      *(u32x4*)(a.y + o00 + ni * oblk + p * 32) = out[p];
+      if (F16) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) fp16_watch(watch, out[p][e]);
       }
     }
   }
