@@ -133,6 +133,9 @@ _SIGNATURES = {
     "alvq_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
     "alvq_lsd_f32": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
     "alvq_lsd_f64": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
+    "alvq_wpe_workspace_bytes": (_i64, [_i32] * 5),
+    "alvq_wpe_f32": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
+    "alvq_wpe_f64": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -983,6 +986,27 @@ def lsd(p, q, eps):
 
 
 # ----------------------------------------------------------------------------------------------- t-SNE
+def wpe(spec4d, taps, delay, iterations, psd_context, eps, loading):
+    """WPE dereverberation (alvq_wpe_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 on the GPU -> (out of the same
+    shape and dtype, status (B, F) int32).  status is the kernel's per-bin flag (include/alvq.h) and is not read here."""
+    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
+        raise RuntimeError("wpe: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
+                           % (spec4d.dtype, tuple(spec4d.shape)))
+    B, D, F, T = spec4d.shape
+    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
+    nbytes = lib().alvq_wpe_workspace_bytes(B, D, F, T, int(taps))
+    if nbytes < 0:
+        raise RuntimeError("wpe: bad dims (B=%d D=%d F=%d T=%d taps=%d; need 1 <= B <= 65535, 1 <= D <= 8, D taps <= 64, "
+                           "1 <= T <= 65535)" % (B, D, F, T, taps))
+    xr = torch.view_as_real(spec4d.resolve_conj().contiguous())
+    out = torch.empty_like(xr)
+    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=spec4d.device, dtype=torch.uint8) if nbytes else None
+    _call_real("wpe", real, _ptr(xr, real, "spec"), _ptr(out, real), _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T,
+               int(taps), int(delay), int(iterations), int(psd_context), float(eps), float(loading))
+    return torch.view_as_complex(out), status
+
+
 def tsne_code_sqdist(codes):
     """int32 (N, L) code sequences -> (N, N) fp32 squared distances of their one-hot expansions (alvq_tsne_code_sqdist_f32)."""
     if codes.dim() != 2:

@@ -390,6 +390,35 @@ int alvq_lsd_f32(const float* p, const float* q, double* out, int B, int F, int 
 int alvq_lsd_f64(const double* p, const double* q, double* out, int B, int F, int T, double eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weighted prediction error (WPE) dereverberation of complex spectrograms (csrc/wpe.hip; Nakatani, Yoshioka, Kinoshita,
+ * Miyoshi, Juang 2010).  X, Y: device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128
+ * ("_f64"); D microphones; X and Y must not overlap.  status: device (B, F) int32.  All arithmetic is float64 (a complex64
+ * value is widened first); only Y is rounded to the input's type.  Every (b, f) bin is a problem of its own, M = D taps:
+ *   x~_t in C^M  entry k D + d is x_d[t - delay - k], k = 0 .. taps - 1; 0 where t - delay - k < 0.
+ *   y <- x, then `iterations` times:
+ *     p_t      = the mean of |y_d[u]|^2 over d and over the frames u in [t - psd_context, t + psd_context] that exist
+ *                (the window clipped to [0, T), divided by D times the frames in it)
+ *     lambda_t = max(p_t, eps max_t p_t)
+ *     R_ij     = sum_t x~_i[t] conj(x~_j[t]) / lambda_t,   P_id = sum_t x~_i[t] conj(x_d[t]) / lambda_t
+ *     R       <- R + loading (tr R / M) I
+ *     G        = R^-1 P by a Cholesky factorisation and two triangular solves
+ *     y_d[t]   = x_d[t] - sum_i conj(G_id) x~_i[t]
+ *   Y = the last y.
+ * status: 0, or 1 = some p_t was not finite (a NaN or an infinity in the bin, or a power beyond the float64 range) or every
+ * p_t was 0, or 2 = a Cholesky pivot was <= 0 or not finite (always the case where T <= delay: R = 0), in any iteration; with
+ * status != 0 the bin leaves with Y = X, bit for bit.  The caller reads status when it can sync.
+ * 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 1 <= D <= 8; taps >= 1, M <= 64; 0 <= delay <= 64; 1 <= iterations <= 16;
+ * 0 <= psd_context <= 64; 1 <= T <= 65535; eps, loading finite and >= 0.
+ * One launch, one workgroup a bin; no atomics, no host sync; every sum runs in one order that depends on the bin's sizes alone:
+ * a bin has the same bits in any batch and on any run.  workspace: device, alvq_wpe_workspace_bytes(B, D, F, T, taps) bytes --
+ * 0 (the pointer may be NULL) where a bin's rows fit in the workgroup's LDS, 16 B F T otherwise; -1 for sizes out of range. */
+int64_t alvq_wpe_workspace_bytes(int B, int D, int F, int T, int taps);
+int alvq_wpe_f32(const float* X, float* Y, int* status, void* workspace, int B, int D, int F, int T, int taps, int delay,
+                 int iterations, int psd_context, double eps, double loading, void* stream);
+int alvq_wpe_f64(const double* X, double* Y, int* status, void* workspace, int B, int D, int F, int T, int taps, int delay,
+                 int iterations, int psd_context, double eps, double loading, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
