@@ -66,17 +66,6 @@ typedef short bf16x4 __attribute__((ext_vector_type(4)));
 int* fx_range_flag_ptr();
 int* fx_range_sticky_ptr();
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// the same, read back from lane 0 (the form the float64 kernels of kmeans.hip and tsne.hip were written with)
-__device__ __forceinline__ double wave_sum_lane0(double v) { return __shfl(wave_sum(v), 0, 64); }
-
 }  // namespace alvq
+
+#include "block_reduce.h"  // wave_sum and the other fixed-order reductions and scans

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void rows_to_nlc_kernel(const float* x, u16* y
     rn_store8<FMT>(y, plane, 1 + (long)b * (L + 1) + l, Cp, c0 + cg, v, range);
   }
   if (FMT == RN_FMT_F16MX && __any(range)) {
-    for (int o = 32; o > 0; o >>= 1) range |= __shfl_xor(range, o, 64);
+    range = wave_or(range);
     if ((tid & 63) == 0 && range_flag) atomicOr(range_flag, range);
   }
 }

@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256) void ncl_to_nlc_fx_kernel(const float* x, u16*
     range |= (fabsf(v) >= 65504.f ? 1 : 0) | (v != v ? 2 : 0);
   }
   if (__any(range)) {                       // rare: one atomic per wave that saw such a value
-    for (int o = 32; o > 0; o >>= 1) range |= __shfl_xor(range, o, 64);
+    range = wave_or(range);
     if ((threadIdx.x & 63) == 0) atomicOr(&g_fx_range_flag, range);
   }
   __syncthreads();
@@ -583,15 +583,11 @@ __global__ __launch_bounds__(256) void grad_amax_kernel(const float* x, long n, 
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
   }
   for (long j = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; j < n; j += stride) m = fmaxf(m, fabsf(x[j]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
   // one atomic per workgroup (thousands of same-address atomics serialise at the L2: they, not the 26 MB read, set the
   // 51 us this pass took with one atomic per wave on 2048 workgroups)
   __shared__ float wm[4];
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
+  m = block_max<kPairwise4, false>(m, wm);
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
     if (m > 0.f) atomicMax((unsigned*)state + 2, __float_as_uint(m));
   }
 }

@@ -349,12 +349,9 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* dy, float* 
     const int b = e / L, l = e - b * L;
     s += dy[((long)b * M + m) * L + l];
   }
-  s = wave_sum(s);
   __shared__ float red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const float tot = block_sum<kPairwise4, false>(s, red);
   if (threadIdx.x == 0) {
-    const float tot = (red[0] + red[1]) + (red[2] + red[3]);
     dbias[m] = accumulate ? dbias[m] + tot : tot;
   }
 }

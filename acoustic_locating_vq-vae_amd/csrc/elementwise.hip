@@ -106,11 +106,9 @@ __global__ __launch_bounds__(256) void mse_partial_kernel(const float* a, const 
     const float d = a[e] - b[e];
     s += d * d;
   }
-  s = wave_sum(s);
   __shared__ float red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum<kPairwise4, false>(s, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void mse_final_kernel(const float* partials, int nparts, float* loss, long n) {
@@ -118,13 +116,8 @@ __global__ __launch_bounds__(256) void mse_final_kernel(const float* partials, i
   const int t = threadIdx.x;
   float s = 0.f;
   for (int i = t; i < nparts; i += 256) s += partials[i];
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  if (t == 0) loss[0] = red[0] / (float)n;
+  s = tree256_sum<false>(s, red);
+  if (t == 0) loss[0] = s / (float)n;
 }
 
 __global__ __launch_bounds__(256) void mse_backward_kernel(const float* a, const float* b, const float* gscale,

@@ -71,15 +71,8 @@ __global__ __launch_bounds__(GC_THREADS) void grad_sumsq_kernel(const float* __r
     a2 += z * z;
     a3 += w * w;
   }
-  double s = wave_sum((a0 + a1) + (a2 + a3));
-  if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = wave_tot[0];
-#pragma unroll
-    for (int w = 1; w < GC_THREADS / 64; ++w) t += wave_tot[w];
-    partial[blockIdx.x] = t;
-  }
+  const double t = block_sum<kSequential, false>((a0 + a1) + (a2 + a3), wave_tot);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
 // sc = the FlatAdam device state {lr/bc1, sqrt(bc2), grad_scale, step, skipped, norm, coef, clipped steps}

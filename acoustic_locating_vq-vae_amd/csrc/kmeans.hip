@@ -35,46 +35,6 @@ constexpr int PP_ROWS = 64;     // rows per k-means++ block
 constexpr int PP_DC = 128;      // dims per staged chunk
 constexpr int PP_MAX_T = 16;    // candidates per round (one wave each in pick_kernel)
 
-// exclusive scan over the workgroup (threads in order); `total` = the sum of all.  sh: >= 16 ints of LDS.
-__device__ int block_scan_excl(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-  for (int w = 0; w < nw; ++w) {
-    const int t = sh[w];
-    if (w < wave) before += t;
-    total += t;
-  }
-  return before + inc - v;
-}
-
-// fp64 version: wave scan (Hillis-Steele), then the wave totals in wave order; every value the same on every run
-__device__ double block_scan_excl_f64(double v, double* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  double ex = __shfl_up(inc, 1, 64);
-  __syncthreads();
-  if (lane == 63) sh[wave] = inc;
-  __syncthreads();
-  double before = 0.0;
-  for (int w = 0; w < wave; ++w) before += sh[w];
-  return lane == 0 ? before : before + ex;
-}
-
 // ---------------------------------------------------------------------------------------------------- Lloyd update
 __global__ __launch_bounds__(64) void hist_kernel(const int64_t* __restrict__ labels, const int64_t* __restrict__ labels_old,
                                                   int* __restrict__ H, int* __restrict__ rank, int* __restrict__ blk_changed,
@@ -124,7 +84,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(int* __restrict__ HO, const 
   int s = 0;
   for (long e = lo; e < hi; ++e) s += HO[e];
   int total = 0;
-  int ex = block_scan_excl(s, sh, total);
+  int ex = block_scan_excl<true>(s, sh, total);
   for (long e = lo; e < hi; ++e) {
     const int v = HO[e];
     HO[e] = ex;
@@ -143,17 +103,17 @@ __global__ __launch_bounds__(1024) void scan_kernel(int* __restrict__ HO, const 
     empty += en == st;
   }
   int nseg = 0;
-  int sx = block_scan_excl(segs, sh, nseg);
+  int sx = block_scan_excl<true>(segs, sh, nseg);
   for (int k = klo; k < khi; ++k) {
     seg_start[k] = sx;
     sx += (cnt[k] + KM_SEG - 1) / KM_SEG;
   }
   int n_empty = 0;
-  (void)block_scan_excl(empty, sh, n_empty);
+  (void)block_scan_excl<true>(empty, sh, n_empty);
   int ch = 0;
   for (int b = tid; b < NB; b += 1024) ch |= blk_changed[b];
   int n_changed = 0;
-  (void)block_scan_excl(ch, sh, n_changed);
+  (void)block_scan_excl<true>(ch, sh, n_changed);
   if (tid == 0) {
     seg_start[K] = nseg;
     state[0] = n_changed > 0;
@@ -261,7 +221,7 @@ __global__ __launch_bounds__(1024) void relocate_kernel(const float* __restrict_
   int mine = 0;
   for (int k = klo; k < khi; ++k) mine += wcnt[k] == 0;
   int total = 0;
-  int pos = block_scan_excl(mine, sh, total);
+  int pos = block_scan_excl<true>(mine, sh, total);
   for (int k = klo; k < khi; ++k)
     if (wcnt[k] == 0) elist[pos++] = k;
   __threadfence_block();
@@ -341,11 +301,9 @@ __global__ __launch_bounds__(128) void finalize_kernel(const double* __restrict_
     const double df = (double)v - (double)c_old[(long)k * D + d];
     acc += df * df;
   }
-  acc = wave_sum_lane0(acc);
-  if ((tid & 63) == 0) sh[tid >> 6] = acc;
-  __syncthreads();
+  acc = block_sum<kSequential, false>(acc, sh);
   if (tid == 0) {
-    shift[k] = sqrt(sh[0] + sh[1]);
+    shift[k] = sqrt(acc);
     if (counts) counts[k] = n;
   }
 }
@@ -358,11 +316,8 @@ __global__ __launch_bounds__(256) void verdict_kernel(const double* __restrict__
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int k = tid; k < K; k += 256) s += shift[k] * shift[k];
-  s = wave_sum_lane0(s);
-  if ((tid & 63) == 0) sh[tid >> 6] = s;
-  __syncthreads();
+  const double tot = block_sum<kSequential, false>(s, sh);
   if (tid == 0) {
-    const double tot = ((sh[0] + sh[1]) + sh[2]) + sh[3];
     const int changed = state[0];
     flags[0] = !changed ? 1 : (tot <= tol ? 2 : 0);
     flags[1] = changed;
@@ -379,14 +334,8 @@ __global__ __launch_bounds__(1024) void sum_kernel(const double* __restrict__ v,
   const long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
   double s = 0.0;
   for (long i = lo; i < hi; ++i) s += v[i];
-  s = wave_sum_lane0(s);
-  if ((tid & 63) == 0) sh[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int w = 0; w < 16; ++w) t += sh[w];
-    out[0] = t;
-  }
+  s = block_sum<kSequential, false>(s, sh);  // no wave total is -0.0: s starts at +0.0 and only adds
+  if (tid == 0) out[0] = s;
 }
 
 // ---------------------------------------------------------------------------------------------------- EMA codebook
@@ -401,11 +350,7 @@ __global__ __launch_bounds__(1024) void ema_size_kernel(const float* __restrict_
   const double omd = 1.0 - decay;
   double s = 0.0;
   for (int k = tid; k < K; k += 1024) s += decay * (double)cs[k] + omd * (double)counts[k];
-  s = wave_sum_lane0(s);
-  if ((tid & 63) == 0) sh[tid >> 6] = s;
-  __syncthreads();
-  double n = 0.0;
-  for (int w = 0; w < 16; ++w) n += sh[w];
+  const double n = block_sum<kSequential, false>(s, sh);  // no wave total is -0.0: s starts at +0.0 and only adds
   const double den = n + (double)K * eps;
   for (int k = tid; k < K; k += 1024) {
     const double v = decay * (double)cs[k] + omd * (double)counts[k];
@@ -536,12 +481,7 @@ __global__ __launch_bounds__(1024) void pick_kernel(const double* __restrict__ u
   if (b != 0x7fffffff) {
     const long row = (long)b * PP_ROWS + lane;
     const double v = row < N ? closest[row] : 0.0;
-    double inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
+    const double inc = wave_scan_incl(v);
     const bool hit = row < N && bex[wave] + inc >= r[wave];
     const unsigned long long m = __ballot(hit);
     id = m ? (long)b * PP_ROWS + (__ffsll(m) - 1) : min(N - 1, (long)b * PP_ROWS + PP_ROWS - 1);
@@ -598,7 +538,7 @@ __global__ __launch_bounds__(256) void ppdist_kernel(const float* __restrict__ x
     if (lane == 0) sh[wave][t] = bs;
   }
   __syncthreads();
-  if (tid < T) part[(long)tid * NBK + blockIdx.x] = ((sh[0][tid] + sh[1][tid]) + sh[2][tid]) + sh[3][tid];
+  if (tid < T) part[(long)tid * NBK + blockIdx.x] = combine_waves<4, kSequential, PP_MAX_T>(&sh[0][tid]);
 }
 
 // pot_t = sum of part[t][.] in block order; the least (lowest t on ties) is round c's centre
@@ -619,8 +559,7 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ 
     int best = 0;
     double bp = 0.0;
     for (int t = 0; t < T; ++t) {
-      double p = 0.0;
-      for (int w = 0; w < 16; ++w) p += sh[t][w];
+      const double p = combine_waves<16, kSequential>(sh[t]);  // no wave total is -0.0: s starts at +0.0 and only adds
       if (t == 0 || p < bp) {
         bp = p;
         best = t;
@@ -657,31 +596,49 @@ struct UpdateWs {
   int *HO, *rank, *perm, *blk_changed, *start, *cnt, *wcnt, *seg_start, *elist, *state;
 };
 
+// carves a workspace into 256-byte aligned pieces; with a null base it only sizes (every piece null, off = the bytes needed)
+struct Carver {
+  char* base;
+  int64_t off = 0;
+  template <typename T>
+  void take(T*& p, int64_t count) {
+    p = base ? (T*)(base + off) : nullptr;
+    off += (count * (int64_t)sizeof(T) + 255) / 256 * 256;
+  }
+};
+
 static int64_t update_layout(int64_t N, int K, int D, char* base, UpdateWs* w) {
   const int64_t NB = (N + KM_SB - 1) / KM_SB, NS = (N + KM_SEG - 1) / KM_SEG + K;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver c{base};
   UpdateWs v;
-  v.part = (double*)take(NS * D * 8);
-  v.sums = (double*)take((int64_t)K * D * 8);
-  v.dist = (double*)take(N * 8);
-  v.shift = (double*)take((int64_t)K * 8);
-  v.HO = (int*)take((int64_t)K * NB * 4);
-  v.rank = (int*)take(N * 4);
-  v.perm = (int*)take(N * 4);
-  v.blk_changed = (int*)take(NB * 4);
-  v.start = (int*)take((int64_t)K * 4);
-  v.cnt = (int*)take((int64_t)K * 4);
-  v.wcnt = (int*)take((int64_t)K * 4);
-  v.seg_start = (int*)take((int64_t)(K + 1) * 4);
-  v.elist = (int*)take((int64_t)K * 4);
-  v.state = (int*)take(8 * 4);
+  c.take(v.part, NS * D);
+  c.take(v.sums, (int64_t)K * D);
+  c.take(v.dist, N);
+  c.take(v.shift, K);
+  c.take(v.HO, (int64_t)K * NB);
+  c.take(v.rank, N);
+  c.take(v.perm, N);
+  c.take(v.blk_changed, NB);
+  c.take(v.start, K);
+  c.take(v.cnt, K);
+  c.take(v.wcnt, K);
+  c.take(v.seg_start, K + 1);
+  c.take(v.elist, K);
+  c.take(v.state, 8);
   if (w) *w = v;
-  return off;
+  return c.off;
+}
+
+// the sort by label and the fp64 segment sums that the Lloyd update and the EMA statistics share: hist .. segsum
+static void launch_sorted_segsums(const float* x, const int64_t* labels, const int64_t* labels_old, const UpdateWs& w, int64_t N,
+                                  int K, int D, hipStream_t s) {
+  const int nb = (int)((N + KM_SB - 1) / KM_SB);
+  hipLaunchKernelGGL(hist_kernel, dim3(nb), dim3(64), (size_t)K * sizeof(int), s, labels, labels_old, w.HO, w.rank,
+                     w.blk_changed, (long)N, K, nb);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.HO, w.blk_changed, w.start, w.cnt, w.seg_start, w.state, K, nb);
+  hipLaunchKernelGGL(scatter_kernel, dim3(km_grid(N, 256)), dim3(256), 0, s, labels, w.HO, w.rank, w.perm, (long)N, K, nb);
+  const int nseg_max = (int)((N + KM_SEG - 1) / KM_SEG + K);
+  hipLaunchKernelGGL(segsum_kernel, dim3(nseg_max), dim3(128), 0, s, x, w.perm, w.start, w.cnt, w.seg_start, w.state, w.part, K, D);
 }
 
 extern "C" int64_t alvq_kmeans_update_workspace_bytes(int64_t N, int K, int D) {
@@ -702,13 +659,7 @@ extern "C" int alvq_kmeans_update_f32(const float* x, const int64_t* labels, con
   hipStream_t s = (hipStream_t)stream;
   UpdateWs w;
   update_layout(N, K, D, (char*)workspace, &w);
-  const int nb = (int)NB;
-  hipLaunchKernelGGL(hist_kernel, dim3(nb), dim3(64), (size_t)K * sizeof(int), s, labels, labels_old, w.HO, w.rank,
-                     w.blk_changed, (long)N, K, nb);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.HO, w.blk_changed, w.start, w.cnt, w.seg_start, w.state, K, nb);
-  hipLaunchKernelGGL(scatter_kernel, dim3(km_grid(N, 256)), dim3(256), 0, s, labels, w.HO, w.rank, w.perm, (long)N, K, nb);
-  const int nseg_max = (int)((N + KM_SEG - 1) / KM_SEG + K);
-  hipLaunchKernelGGL(segsum_kernel, dim3(nseg_max), dim3(128), 0, s, x, w.perm, w.start, w.cnt, w.seg_start, w.state, w.part, K, D);
+  launch_sorted_segsums(x, labels, labels_old, w, N, K, D, s);
   hipLaunchKernelGGL((clustersum_kernel<double, int>), dim3(K), dim3(128), 0, s, w.part, w.seg_start, w.cnt, w.sums, w.wcnt, D);
   hipLaunchKernelGGL(rowdist_kernel, dim3(km_grid(N, 4, 2048)), dim3(256), 0, s, x, labels, centers_old, w.dist,
                      (const int*)(w.state + 1), (long)N, K, D);
@@ -731,17 +682,10 @@ extern "C" int alvq_vq_ema_stats_f32(const float* x, const int64_t* idx, float* 
   ALVQ_REQUIRE(x && idx && counts && sums && workspace, ALVQ_EINVAL, "%s: null pointer", who);
   if (int rc = km_check(N, K, D, who)) return rc;
   ALVQ_REQUIRE(N < (1L << 24), ALVQ_EUNSUPPORTED, "%s: N=%ld >= 2^24 rows (counts travel as fp32)", who, (long)N);
-  const int64_t NB = (N + KM_SB - 1) / KM_SB;
   hipStream_t s = (hipStream_t)stream;
   UpdateWs w;
   update_layout(N, K, D, (char*)workspace, &w);
-  const int nb = (int)NB;
-  hipLaunchKernelGGL(hist_kernel, dim3(nb), dim3(64), (size_t)K * sizeof(int), s, idx, (const int64_t*)nullptr, w.HO, w.rank,
-                     w.blk_changed, (long)N, K, nb);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.HO, w.blk_changed, w.start, w.cnt, w.seg_start, w.state, K, nb);
-  hipLaunchKernelGGL(scatter_kernel, dim3(km_grid(N, 256)), dim3(256), 0, s, idx, w.HO, w.rank, w.perm, (long)N, K, nb);
-  const int nseg_max = (int)((N + KM_SEG - 1) / KM_SEG + K);
-  hipLaunchKernelGGL(segsum_kernel, dim3(nseg_max), dim3(128), 0, s, x, w.perm, w.start, w.cnt, w.seg_start, w.state, w.part, K, D);
+  launch_sorted_segsums(x, idx, nullptr, w, N, K, D, s);
   hipLaunchKernelGGL((clustersum_kernel<float, float>), dim3(K), dim3(128), 0, s, w.part, w.seg_start, w.cnt, sums, counts, D);
   return check_launch(who);
 }
@@ -813,16 +757,11 @@ extern "C" int alvq_kmeans_add_rows_f32(const float* x, const float* v, float* y
 
 static int64_t pp_layout(int64_t N, int T, char* base, double** dist, double** part, PPState** st) {
   const int64_t NBK = (N + PP_ROWS - 1) / PP_ROWS;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
-  for (int i = 0; i < 2; ++i) dist[i] = (double*)take((int64_t)T * N * 8);
-  for (int i = 0; i < 2; ++i) part[i] = (double*)take((int64_t)T * NBK * 8);
-  *st = (PPState*)take(sizeof(PPState));
-  return off;
+  Carver c{base};
+  for (int i = 0; i < 2; ++i) c.take(dist[i], (int64_t)T * N);
+  for (int i = 0; i < 2; ++i) c.take(part[i], (int64_t)T * NBK);
+  c.take(*st, 1);
+  return c.off;
 }
 
 extern "C" int64_t alvq_kmeans_plusplus_workspace_bytes(int64_t N, int T) {

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void onehot_to_index_kernel(const float* enc, 
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {  // three butterflies interleaved: as block_reduce.h's wave_* calls they cost 3 VGPRs
     cnt += __shfl_xor(cnt, o, 64);
     bad |= __shfl_xor(bad, o, 64);
     pos = max(pos, __shfl_xor(pos, o, 64));

@@ -251,10 +251,7 @@ __global__ __launch_bounds__(RA_THREADS) void room_acoustics_kernel(const T* __r
   __syncthreads();
   if (tid != 0) return;
   double s[15];
-  for (int i = 0; i < 15; ++i) {
-    s[i] = s_red[0][i];
-    for (int w = 1; w < RA_WAVES; ++w) s[i] += s_red[w][i];
-  }
+  for (int i = 0; i < 15; ++i) s[i] = combine_waves<RA_WAVES, kSequential, 15>(&s_red[0][i]);
   int st = 0;
   double* o = out + 7 * (long)b;
   for (int r = 0; r < 3; ++r) o[r] = ra_decay_time(s + 5 * r, fs, st);

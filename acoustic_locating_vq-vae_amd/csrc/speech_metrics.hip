@@ -45,25 +45,6 @@ constexpr double ST_CLIP = 6.623413251903491;    // 1 + 10^(15 / 20): beta = -15
 constexpr int ST_BAD_ENERGY = 1;          // fewer than 256 samples, or a clean row of zero or non-finite energy
 constexpr int ST_FEW_FRAMES = 2;          // fewer than 30 frames kept
 
-// Sums of K values a thread over the workgroup: butterfly within a wave, then the waves in order.  Every thread returns with
-// the sums.  red is free for reuse after the next __syncthreads().
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[K]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();
-  if (lane == 0)
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double s = red[0][k];
-    for (int w = 1; w < SM_WAVES; ++w) s += red[w][k];
-    v[k] = s;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- resampling
 constexpr int RS_LDS_TAPS = 4096;         // a filter of up to this many taps (R <= 204) is staged in LDS
 
@@ -136,20 +117,7 @@ __global__ __launch_bounds__(SM_THREADS) void stoi_mask_kernel(const double* __r
       top = fmax(top, stoi_level_db(s));
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    top = fmax(top, __shfl_xor(top, o, kWave));
-    flag |= __shfl_xor(flag, o, kWave);
-  }
-  if (lane == 0) {
-    s_max[wv] = top;
-    s_flag[wv] = flag;
-  }
-  __syncthreads();
-  for (int w = 0; w < SM_WAVES; ++w) {
-    top = fmax(top, s_max[w]);
-    flag |= s_flag[w];
-  }
+  block_max_or<false>(top, flag, s_max, s_flag);
   if (flag != 2) {                         // no frame at all, an energy that is not finite, or no energy
     if (tid == 0) {
       kept_frames[b] = 0;
@@ -252,7 +220,7 @@ __global__ __launch_bounds__(SM_THREADS) void stoi_correlate_kernel(const double
                                                                     const int* __restrict__ kept_frames,
                                                                     const int* __restrict__ status, double* __restrict__ value,
                                                                     int nf) {
-  __shared__ double s_red[SM_WAVES][1];
+  __shared__ double s_red[1][SM_WAVES];
   const int tid = threadIdx.x, b = blockIdx.x;
   if (status[b] != 0) {
     if (tid == 0) value[b] = NAN;
@@ -298,7 +266,7 @@ __global__ __launch_bounds__(SM_THREADS) void stoi_correlate_kernel(const double
     for (int i = 0; i < ST_SEG; ++i) d += (xs[i] / nx) * (ys[i] / ny);
     acc[0] += d;
   }
-  block_sum(acc, s_red);
+  block_sum<kSequential, true>(acc, s_red);
   if (tid == 0) value[b] = acc[0] / (double)pairs;
 }
 
@@ -306,7 +274,7 @@ __global__ __launch_bounds__(SM_THREADS) void stoi_correlate_kernel(const double
 template <typename T>
 __global__ __launch_bounds__(SM_THREADS) void si_sdr_kernel(const T* __restrict__ reference, const T* __restrict__ estimate,
                                                             double* __restrict__ out, int n) {
-  __shared__ double s_red[SM_WAVES][2];
+  __shared__ double s_red[2][SM_WAVES];
   const int tid = threadIdx.x;
   const T* s = reference + (long)blockIdx.x * n;
   const T* e = estimate + (long)blockIdx.x * n;
@@ -315,7 +283,7 @@ __global__ __launch_bounds__(SM_THREADS) void si_sdr_kernel(const T* __restrict_
     v[0] += (double)s[t];
     v[1] += (double)e[t];
   }
-  block_sum(v, s_red);
+  block_sum<kSequential, true>(v, s_red);
   const double ms = v[0] / (double)n, me = v[1] / (double)n;
   v[0] = v[1] = 0.0;
   for (int t = tid; t < n; t += SM_THREADS) {
@@ -323,7 +291,7 @@ __global__ __launch_bounds__(SM_THREADS) void si_sdr_kernel(const T* __restrict_
     v[0] += a * a;
     v[1] += c * a;
   }
-  block_sum(v, s_red);
+  block_sum<kSequential, true>(v, s_red);
   const double ss = v[0];
   if (!(ss > 0.0 && ss <= DBL_MAX)) {
     if (tid == 0) out[blockIdx.x] = NAN;
@@ -336,7 +304,7 @@ __global__ __launch_bounds__(SM_THREADS) void si_sdr_kernel(const T* __restrict_
     v[0] += target * target;
     v[1] += (target - c) * (target - c);
   }
-  block_sum(v, s_red);
+  block_sum<kSequential, true>(v, s_red);
   if (tid != 0) return;
   double r;
   if (v[0] != v[0] || v[1] != v[1]) r = NAN;
@@ -349,7 +317,7 @@ __global__ __launch_bounds__(SM_THREADS) void si_sdr_kernel(const T* __restrict_
 template <typename T>
 __global__ __launch_bounds__(SM_THREADS) void lsd_kernel(const T* __restrict__ p, const T* __restrict__ q,
                                                          double* __restrict__ out, int F, int T_frames, double eps) {
-  __shared__ double s_red[SM_WAVES][2];
+  __shared__ double s_red[2][SM_WAVES];
   const long row = (long)blockIdx.x * F * T_frames;
   double v[2] = {0.0, 0.0};                // the frames' distances; how many entries were negative or not finite
   for (int t = threadIdx.x; t < T_frames; t += SM_THREADS) {
@@ -362,7 +330,7 @@ __global__ __launch_bounds__(SM_THREADS) void lsd_kernel(const T* __restrict__ p
     }
     v[0] += sqrt(s / (double)F);
   }
-  block_sum(v, s_red);
+  block_sum<kSequential, true>(v, s_red);
   if (threadIdx.x == 0) out[blockIdx.x] = v[1] != 0.0 ? NAN : v[0] / (double)T_frames;
 }
 

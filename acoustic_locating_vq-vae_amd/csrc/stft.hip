@@ -106,17 +106,6 @@ __device__ __forceinline__ cplx ratio(float sr, float si, double er, double ei) 
   const double dr = er + 1e-8, d = dr * dr + ei * ei;       // S / (E + 1e-8)
   return cplx{((double)sr * dr + (double)si * ei) / d, ((double)si * dr - (double)sr * ei) / d};
 }
-__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
-  red[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 __global__ __launch_bounds__(256) void spec_stats_kernel(const float* S, const double* E, float* speech_pow, double* echoed_pow,
                                                          double* wiener, double* binmax, int F, int T) {
   __shared__ double red[256];
@@ -135,19 +124,14 @@ __global__ __launch_bounds__(256) void spec_stats_kernel(const float* S, const d
     speech_pow[row + t] = sr * sr + si * si;
     echoed_pow[row + t] = er * er + ei * ei;
   }
-  nr = block_sum(nr, red, tid);
-  ni = block_sum(ni, red, tid);
-  den = block_sum(den, red, tid);
-  red[tid] = mx;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = red[tid] > red[tid + s] ? red[tid] : red[tid + s];
-    __syncthreads();
-  }
+  nr = tree256_sum<true>(nr, red);
+  ni = tree256_sum<true>(ni, red);
+  den = tree256_sum<true>(den, red);
+  mx = tree256_max<false>(mx, red);
   if (tid == 0) {
     const double d = den + 1e-8, wr = nr / d, wi = ni / d;
     wiener[(long)b * F + f] = wr * wr + wi * wi;
-    binmax[(long)b * F + f] = red[0];
+    binmax[(long)b * F + f] = mx;
   }
 }
 __global__ __launch_bounds__(256) void spec_rir_kernel(const float* S, const double* E, const double* binmax, double* rir_pow,

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(TS_SEARCH_THREADS) void search_kernel(float* __rest
                                                                    double* __restrict__ S_out, int N, double target) {
   extern __shared__ float hi[];  // [max(N - TS_REG_N, 0)]
   __shared__ double part[2][2][TS_SEARCH_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int i = blockIdx.x;
   float* row = P + (int64_t)i * N;
   float d[TS_REG];
@@ -102,28 +102,17 @@ __global__ __launch_bounds__(TS_SEARCH_THREADS) void search_kernel(float* __rest
   const double inf = __builtin_inf();
   double beta = 1.0, bmin = -inf, bmax = inf, used = 1.0, S = 1.0;
   for (int step = 0; step < 100; ++step) {
-    double s = 0.0, sd = 0.0;
+    double v[2] = {0.0, 0.0};  // s, sd: from +0.0 and only added to, so no wave total is -0.0
 #pragma unroll
     for (int k = 0; k < TS_REG; ++k) {
       const int j = tid + TS_SEARCH_THREADS * k;
-      if (j < N && j != i) search_term((double)d[k], beta, s, sd);
+      if (j < N && j != i) search_term((double)d[k], beta, v[0], v[1]);
     }
     for (int j = TS_REG_N + tid; j < N; j += TS_SEARCH_THREADS)
-      if (j != i) search_term((double)hi[j - TS_REG_N], beta, s, sd);
-    s = wave_sum_lane0(s);
-    sd = wave_sum_lane0(sd);
-    double* pp = &part[step & 1][0][0];  // alternate buffers: one barrier per step
-    if (lane == 0) {
-      pp[wave] = s;
-      pp[TS_SEARCH_THREADS / 64 + wave] = sd;
-    }
-    __syncthreads();
-    s = 0.0;
-    sd = 0.0;
-    for (int w = 0; w < TS_SEARCH_THREADS / 64; ++w) {
-      s += pp[w];
-      sd += pp[TS_SEARCH_THREADS / 64 + w];
-    }
+      if (j != i) search_term((double)hi[j - TS_REG_N], beta, v[0], v[1]);
+    block_sum<kSequential, false>(v, part[step & 1]);  // alternate buffers: one barrier per step
+    double s = v[0];
+    const double sd = v[1];
     if (s == 0.0) s = 1e-8;
     const double H = log(s) + beta * (sd / s);
     used = beta;
@@ -188,13 +177,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ 
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int k = tid; k < n; k += 256) s += x[k];
-  part[tid] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) part[tid] += part[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) out[0] = take_sqrt ? sqrt(part[0]) : part[0];
+  s = tree256_sum<false>(s, part);
+  if (tid == 0) out[0] = take_sqrt ? sqrt(s) : s;
 }
 
 __global__ __launch_bounds__(256) void normalize_kernel(float* __restrict__ P, const double* __restrict__ total, int N) {

@@ -352,11 +352,9 @@ __global__ __launch_bounds__(256) void vq_gather_loss_kernel(const float* x, con
     for (int k = threadIdx.x; k < K; k += 256)
       if (lhist[k]) atomicAdd(&hist[k], lhist[k]);
   }
-  s = wave_sum(s);
   __shared__ float red[4];
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum<kPairwise4, false>(s, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 // QLAT: the loss carries the q-latent term (VectorQuantizer); without it, beta * m alone (VectorQuantizerEMA, whose codebook
@@ -368,29 +366,17 @@ __global__ __launch_bounds__(256) void vq_finalize_kernel(const float* partials,
   const int t = threadIdx.x;
   float s = 0.f;
   for (int i = t; i < nparts; i += 256) s += partials[i];
-  red[t] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  const float sq = red[0];
-  __syncthreads();
+  const float sq = tree256_sum<true>(s, red);
   float h = 0.f;
   for (int k = t; k < K; k += 256) {
     const float p = (float)hist[k] / (float)N;
     h += p * logf(p + 1e-10f);
   }
-  red[t] = h;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
+  h = tree256_sum<false>(h, red);
   if (t == 0) {
     const float m = sq / (float)((double)N * (double)D);
     out[0] = QLAT ? m + beta * m : beta * m;  // q_latent + beta * e_latent, both equal m in value (:46-52)
-    out[1] = expf(-red[0]);
+    out[1] = expf(-h);
   }
 }
 
@@ -425,7 +411,7 @@ __global__ __launch_bounds__(256) void vq_codebook_grad_kernel(const float* grad
   __shared__ int list[VQL_CAP];
   __shared__ int wave_tot[4];
   __shared__ vec_t comb[256];
-  const int k = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
   const float se = (grad_loss ? grad_loss[0] : 1.f) * ce;
   const int TD = D / VEC;                          // lanes along d (<= 128 for VEC = 4, <= 256 for VEC = 1)
   const int G = 256 / TD;                          // thread groups
@@ -458,21 +444,8 @@ __global__ __launch_bounds__(256) void vq_codebook_grad_kernel(const float* grad
       const long r = base + 4 * tid + j;
       if (r < rend && idx[r] == k) mine[cnt++] = (int)r;
     }
-    int incl = cnt;                                // inclusive prefix over the wave, then over the block
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int up = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) before += wave_tot[w];
-      total += wave_tot[w];
-    }
-    const int pos = nlist + before + incl - cnt;
+    int total;                                     // wave_tot: the loop's last barrier lies behind its previous use
+    const int pos = nlist + block_scan_excl<false>(cnt, wave_tot, total);
     for (int j = 0; j < cnt; ++j) list[pos + j] = mine[j];
     nlist += total;
     __syncthreads();

@@ -70,28 +70,6 @@ __device__ __forceinline__ double2 wpe_mul_conj(double2 a, double2 b) {     // a
   return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
 }
 
-// the workgroup's maximum of v (>= 0 or NaN-free by construction) and the OR of flag, through LDS; every thread gets both
-__device__ __forceinline__ void wpe_block_max_or(double& v, int& flag, double* s_max, int* s_flag) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    v = fmax(v, __shfl_xor(v, o, 64));
-    flag |= __shfl_xor(flag, o, 64);
-  }
-  __syncthreads();                                  // the previous use of s_max / s_flag is over
-  if ((threadIdx.x & 63) == 0) {
-    s_max[threadIdx.x >> 6] = v;
-    s_flag[threadIdx.x >> 6] = flag;
-  }
-  __syncthreads();
-  v = s_max[0];
-  flag = s_flag[0];
-#pragma unroll
-  for (int i = 1; i < WPE_WAVES; ++i) {
-    v = fmax(v, s_max[i]);
-    flag |= s_flag[i];
-  }
-}
-
 template <typename R, bool ROW_LDS>
 __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
   typedef typename WpeCplx<R>::type C;
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
       else pmax = fmax(pmax, p);
       w[t] = p;
     }
-    wpe_block_max_or(pmax, bad, s_max, s_flag);
+    block_max_or<true>(pmax, bad, s_max, s_flag);
     if (bad || pmax == 0.0) {
       fail = WPE_BAD_POWER;
       break;

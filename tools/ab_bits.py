@@ -5,7 +5,10 @@ unchanged.     ALVQ_LIB=$PWD/acoustic_locating_vq-vae_amd/lib/libalvq_base.so py
 The modes above are the default; ``python3 tools/ab_bits.py dsp`` fingerprints the waveform front end instead (STFT power and
 complex, the inverse STFT of each complex result, Griffin-Lim), in fp32 and fp64.  The ten cases reach only the tiles the default
 dispatch picks: ``python3 tools/ab_bits.py tiles`` repeats the convolution entries of all four modes on two small shapes under
-every forcing of the dispatch options (TILE_FORCINGS), which reaches every instantiation of every forward kernel family."""
+every forcing of the dispatch options (TILE_FORCINGS), which reaches every instantiation of every forward kernel family.
+``python3 tools/ab_bits.py reduce`` fingerprints the entry points behind csrc/block_reduce.h's workgroup reductions and scans
+(losses, quantiser, gradient clipping, k-means, EMA codebook, t-SNE, spectrogram statistics, speech metrics, WPE, the layout
+kernels that raise the fp16 range flag) on small seeded inputs."""
 import hashlib
 import json
 import os
@@ -96,12 +99,83 @@ def tiles():
     return out
 
 
+def reduce():
+    from acoustic_locating_vq_vae import speech_metrics as SM
+    g = torch.Generator(device="cuda").manual_seed(20261019)
+    f64, i32 = torch.float64, torch.int32
+    r = lambda *shape, dtype=torch.float32: torch.randn(*shape, device="cuda", dtype=dtype, generator=g)
+    u = lambda *shape, dtype=torch.float32: torch.rand(*shape, device="cuda", dtype=dtype, generator=g)
+    ints = lambda hi, *shape: torch.randint(0, hi, shape, device="cuda", generator=g)
+    z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, device="cuda", dtype=dtype)
+    out = {}
+    out["mse"] = {str(n): digest(N.mse(r(n), r(n))) for n in (1, 257, 300001)}
+    for (n, K, D) in ((777, 64, 24), (1500, 10, 23)):
+        flat, book, gl = r(n, D), r(K, D), u(1) + 0.5
+        idx = N.vq_argmin(flat, book)
+        res = {"loss": digest(*N.vq_gather_loss(flat, book, idx, 0.25)), "loss_ema": digest(*N.vq_gather_loss(flat, book, idx, 0.25, ema=True)),
+               "backward": digest(*N.vq_backward(r(n, D), gl, flat, book, idx, 0.25))}
+        counts, sums, size, ema_w = z(K), z(K, D), u(K) + 0.5, r(K, D)
+        N.vq_ema_stats(flat, idx, counts, sums)
+        res["ema_stats"] = digest(counts, sums)
+        N.vq_ema_update(counts, sums, size, ema_w, book, 0.99, 1e-5)
+        res["ema_update"] = digest(size, ema_w, book)
+        out["vq:%s" % ((n, K, D),)] = res
+    dy, x = r(3, 20, 301), r(3, 7, 301)
+    out["conv1d_wgrad_f32"] = {"dw_db": digest(*N.conv1d_wgrad(dy, x, 3, want_bias=True))}
+    out["grad_scale"] = {str(n): digest(N.grad_scale(r(n) * 37.0)) for n in (5, 1031, 2 ** 20 + 3)}
+    for n in (1, 65, 2 ** 20 + 3):
+        sc, ws = z(N.ADAM_SCALARS), N.grad_clip_workspace("cuda")
+        N.adam_advance(sc, 1e-3, 0.9, 0.999, 0.5)
+        N.grad_clip(r(n), sc, 0.75, workspace=ws)
+        out["grad_clip:%d" % n] = {"scalars": digest(sc), "sum": digest(ws[-1:]), "partials": digest(ws)}
+    for (n, K, D) in ((1025, 5, 129), (300, 3, 5)):
+        x, old = r(n, D), r(K, D)
+        labels = ints(K - 1, n)                                       # cluster K - 1 is empty: the relocation runs
+        new, counts, stats, flags = z(K, D), z(K, dtype=i32), z(1, dtype=f64), z(4, dtype=i32)
+        N.kmeans_update(x, labels, None, old, new, counts, stats, flags, 1e-4)
+        res = {"update": digest(new, counts, stats, flags), "inertia": digest(N.kmeans_inertia(x, labels, new))}
+        N.kmeans_update(x, ints(K, n), labels, old, new, counts, stats, flags, 1e-4)
+        res["update_full"] = digest(new, counts, stats, flags)
+        res["plusplus"] = digest(*N.kmeans_plusplus(x, K, 7, u(K - 1, 4, dtype=f64)))
+        out["kmeans:%s" % ((n, K, D),)] = res
+    for n in (2, 257):
+        P = N.tsne_code_sqdist(ints(16, n, 12).to(i32))
+        beta, S = N.tsne_affinities(P, min(30.0, n / 2.0))
+        Y, upd, gains, grad, stats = r(n, 2, dtype=f64) * 1e-4, z(n, 2, dtype=f64), z(n, 2, dtype=f64) + 1.0, z(n, 2, dtype=f64), z(2, dtype=f64)
+        N.tsne_descend(P, Y, upd, gains, grad, stats, 5, 12.0, 0.5, 200.0)
+        out["tsne:%d" % n] = {"affinities": digest(P, beta, S), "descend": digest(Y, upd, gains, grad, stats)}
+    S, E = torch.view_as_complex(r(2, 5, 300, 2)), torch.view_as_complex(r(2, 5, 300, 2, dtype=f64))
+    out["spec_rir_wiener"] = {"all": digest(*N.spec_rir_wiener(S, E))}
+    clean = r(2, 6000, dtype=f64)
+    clean[0, 2000:3000] *= 1e-4                                       # frames more than 40 dB down: dropped by the mask
+    noisy = clean + 0.3 * r(2, 6000, dtype=f64)
+    out["stoi"] = {"all": digest(*N.stoi(clean, noisy, *SM.stoi_band_edges()))}
+    for dt, tag in ((torch.float32, "f32"), (f64, "f64")):
+        a, b = r(3, 1001, dtype=dt), r(3, 1001, dtype=dt)
+        p, q = u(2, 9, 300, dtype=dt), u(2, 9, 300, dtype=dt)
+        out["metrics:%s" % tag] = {"si_sdr": digest(N.si_sdr(a, b)), "lsd": digest(N.lsd(p, q, 1e-10))}
+    for (B, D, F, T, taps, delay) in ((2, 2, 5, 200, 8, 2), (1, 4, 2, 2000, 16, 3)):     # the row in LDS; too long for it
+        for dt, tag in ((torch.float32, "c64"), (f64, "c128")):
+            X = torch.view_as_complex(r(B, D, F, T, 2, dtype=dt))
+            out["wpe:%s:%s" % (tag, (B, D, F, T, taps))] = {"all": digest(*N.wpe(X, taps, delay, 3, 0, 1e-10, 1e-10))}
+    out["onehot_to_index"] = {"all": digest(*N.onehot_to_index(N.onehot(ints(130, 300), 130)))}
+    x = r(2, 40, 300)
+    x[1, 3, 5], x[0, 7, 250] = 7.0e4, float("nan")                    # raises both bits of the fp16 range flag
+    N.f16mx_range_flag()
+    res = {"rows_to_nlc": digest(N.rows_to_nlc(x.permute(0, 2, 1).contiguous(), 2, "f16mx")), "flag_rows": N.f16mx_range_flag()}
+    res.update({"ncl_to_nlc": digest(N.ncl_to_nlc(x, 2, "f16mx")), "flag_ncl": N.f16mx_range_flag()})
+    out["layout:f16mx"] = res
+    return {"reduce:" + k: v for k, v in out.items()}
+
+
 def main():
     modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3", "f16"]
     out = dsp() if "dsp" in modes else {}
     if "tiles" in modes:
         out.update(tiles())
-    modes = [m for m in modes if m not in ("dsp", "tiles")]
+    if "reduce" in modes:
+        out.update(reduce())
+    modes = [m for m in modes if m not in ("dsp", "tiles", "reduce")]
     shapes = [(2, 7, 16, 13, 3), (3, 72, 136, 95, 1), (2, 201, 1024, 500, 3), (2, 1024, 128, 500, 3), (2, 1024, 1024, 201, 1),
               (5, 130, 130, 129, 3), (4, 1024, 1024, 500, 1), (4, 1024, 1024, 500, 3), (3, 1024, 201, 500, 3), (2, 500, 1024, 201, 3)]
     for mode in modes:
