@@ -95,7 +95,9 @@ int alvq_conv1d_wgrad_f32(const float* dy, const float* x, float* dw, float* dbi
  * (N,D) rows in memory order (no permute, :32); codebook is (K,D).
  * ---------------------------------------------------------------------------------------------- */
 /* idx[n] = argmin_k fl(fl(|x_n|^2 + |e_k|^2) - 2 x_n.e_k), lowest k on ties (:34-38).
- * min_dist may be NULL.  workspace: alvq_vq_argmin_workspace_bytes(N,K) bytes. */
+ * min_dist may be NULL.  workspace: alvq_vq_argmin_workspace_bytes(N,K) bytes.
+ * Every index is in [0, K).  A row that holds a NaN or an infinity has no distance below +inf: it gets index 0 and
+ * distance +inf.  A code row that holds a NaN or an infinity is never chosen by a finite row. */
 int64_t alvq_vq_argmin_workspace_bytes(int64_t N, int K, int D);
 int alvq_vq_argmin_f32(const float* x, const float* codebook, int64_t* idx, float* min_dist, void* workspace,
                        int64_t N, int K, int D, void* stream);
