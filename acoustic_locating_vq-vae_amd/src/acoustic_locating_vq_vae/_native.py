@@ -136,6 +136,11 @@ _SIGNATURES = {
     "alvq_wpe_workspace_bytes": (_i64, [_i32] * 5),
     "alvq_wpe_f32": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
     "alvq_wpe_f64": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
+    "alvq_phat_cross_spectra_f32": (_i32, [_c_void_p] * 3 + [_i32] * 6 + [_c_void_p]),
+    "alvq_phat_cross_spectra_f64": (_i32, [_c_void_p] * 3 + [_i32] * 6 + [_c_void_p]),
+    "alvq_gcc_phat_f64": (_i32, [_c_void_p] * 2 + [_i32] * 6 + [_c_void_p]),
+    "alvq_srp_phat_f64": (_i32, [_c_void_p] * 6 + [_i32] * 3 + [_i64] * 2 + [ctypes.c_double, _i32, ctypes.c_double, _i32, _i32,
+                                                                            _c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1005,6 +1010,66 @@ def wpe(spec4d, taps, delay, iterations, psd_context, eps, loading):
     _call_real("wpe", real, _ptr(xr, real, "spec"), _ptr(out, real), _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T,
                int(taps), int(delay), int(iterations), int(psd_context), float(eps), float(loading))
     return torch.view_as_complex(out), status
+
+
+# ----------------------------------------------------------------------------------------------- source localisation
+def phat_cross_spectra(spec4d, f_lo, f_hi):
+    """PHAT-weighted cross-spectra of the microphone pairs (alvq_phat_cross_spectra_f32 / _f64): spec4d (B, D, F, T) complex64 /
+    complex128 on the GPU -> (psi (B, D (D - 1) / 2, F) complex128, 0 outside the bins f_lo .. f_hi; status (B,) int32).
+    status is the kernel's per-item flag (include/alvq.h) and is not read here."""
+    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
+        raise RuntimeError("phat_cross_spectra: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
+                           % (spec4d.dtype, tuple(spec4d.shape)))
+    B, D, F, T = spec4d.shape
+    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
+    xr = torch.view_as_real(spec4d.resolve_conj().contiguous())
+    psi = torch.empty((B, D * (D - 1) // 2, F, 2), device=spec4d.device, dtype=torch.float64)
+    status = torch.empty((B,), device=spec4d.device, dtype=torch.int32)
+    _call_real("phat_cross_spectra", real, _ptr(xr, real, "spec"), _ptr(psi, torch.float64), _ptr(status, torch.int32), B, D, F, T,
+               int(f_lo), int(f_hi))
+    return torch.view_as_complex(psi), status
+
+
+def _psi_dims(psi, n_fft, who):
+    if psi.dim() != 3 or psi.dtype != torch.complex128 or psi.shape[2] != n_fft // 2 + 1:
+        raise RuntimeError("%s: expected complex128 (B, P, n_fft / 2 + 1) cross-spectra (got %s %s, n_fft=%d)"
+                           % (who, psi.dtype, tuple(psi.shape), n_fft))
+    B, P, F = psi.shape
+    D = next((d for d in range(2, 9) if d * (d - 1) // 2 == P), None)
+    if D is None:
+        raise RuntimeError("%s: %d pairs are not those of 2 .. 8 microphones" % (who, P))
+    return B, D, torch.view_as_real(psi.resolve_conj().contiguous())
+
+
+def gcc_phat(psi, n_fft, max_lag, f_lo, f_hi):
+    """GCC-PHAT at the integer lags -max_lag .. max_lag (alvq_gcc_phat_f64): psi (B, P, F) complex128 on the GPU ->
+    (B, P, 2 max_lag + 1) float64."""
+    B, D, pr = _psi_dims(psi, int(n_fft), "gcc_phat")
+    r = torch.empty((B, psi.shape[1], 2 * int(max_lag) + 1), device=psi.device, dtype=torch.float64)
+    _check(lib().alvq_gcc_phat_f64(_ptr(pr, torch.float64, "psi"), _ptr(r, torch.float64), B, D, int(n_fft), int(max_lag), int(f_lo),
+                                   int(f_hi), _stream()), "alvq_gcc_phat_f64")
+    return r
+
+
+def srp_phat(psi, mics, cand, fs, n_fft, c, f_lo, f_hi):
+    """The SRP-PHAT map (alvq_srp_phat_f64): psi (B, P, F) complex128, microphones mics (D, 3) or (B, D, 3) and candidates
+    cand (G, 3) or (B, G, 3), float64, all on the GPU -> (map (B, G) float64, best (B,) int32, status (B,) int32).  A
+    two-dimensional mics / cand serves every item.  status is the kernel's per-item flag (include/alvq.h) and is not read here."""
+    B, D, pr = _psi_dims(psi, int(n_fft), "srp_phat")
+    if mics.dim() not in (2, 3) or tuple(mics.shape[-2:]) != (D, 3) or (mics.dim() == 3 and mics.shape[0] != B):
+        raise RuntimeError("srp_phat: mics must be (%d, 3) or (%d, %d, 3) (got %s)" % (D, B, D, tuple(mics.shape)))
+    if cand.dim() not in (2, 3) or cand.shape[-1] != 3 or (cand.dim() == 3 and cand.shape[0] != B):
+        raise RuntimeError("srp_phat: cand must be (G, 3) or (%d, G, 3) (got %s)" % (B, tuple(cand.shape)))
+    mics, cand = mics.contiguous(), cand.contiguous()
+    G = cand.shape[-2]
+    out = torch.empty((B, G), device=psi.device, dtype=torch.float64)
+    best = torch.empty((B,), device=psi.device, dtype=torch.int32)
+    status = torch.empty((B,), device=psi.device, dtype=torch.int32)
+    _check(lib().alvq_srp_phat_f64(_ptr(pr, torch.float64, "psi"), _ptr(mics, torch.float64, "mics"), _ptr(cand, torch.float64, "cand"),
+                                   _ptr(out, torch.float64), _ptr(best, torch.int32), _ptr(status, torch.int32), B, D, G,
+                                   3 * D if mics.dim() == 3 else 0, 3 * G if cand.dim() == 3 else 0, float(fs), int(n_fft),
+                                   float(c), int(f_lo), int(f_hi), _stream()), "alvq_srp_phat_f64")
+    return out, best, status
 
 
 def tsne_code_sqdist(codes):

@@ -30,6 +30,11 @@ For data that spans rooms, ``SceneConfig`` / ``sample_scenes`` draw a room, T60,
     scenes = sample_scenes(64, SceneConfig(), generator)      # rooms 3-8 m, T60 0.25-0.8 s, receivers, theta
     samples = generate_samples(wave, scenes=scenes)           # the same 6-tuple, a room per item
 
+A microphone array in a room, for ``localization`` (GCC-PHAT, SRP-PHAT) and multi-microphone ``dereverberation.wpe``:
+
+    h = array_impulse_responses(src, mics, room, reverberation_time=0.4, nsample=6400)      # (B, D, nsample)
+    spec = array_spectrograms(wave, h)                                                      # (B, D, F, T) complex128
+
 Parity with ``rir_generator`` itself is unpinned (the package is absent and the reference holds no fixture); the RIR is
 pinned by the closed-form direct path, reciprocity, scipy's lfilter for the high-pass and a float64 restatement.
 Any other (Nh,) or (B, Nh) float64 response can still be passed to ``specs_from_waveform``.
@@ -205,6 +210,40 @@ def room_impulse_responses(src, receiver, room, reverberation_time=None, beta=No
     if not torch.cuda.is_current_stream_capturing() and bool((src == rcv).all(dim=1).any()):
         raise ValueError("room_impulse_responses: a source coincides with its receiver (distance 0, infinite gain)")
     return N.rir(src, rcv, L, beta, c, fs, nsample, order, hp_filter)
+
+
+def array_impulse_responses(src, mics, room, **rir_kwargs):
+    """Room impulse responses from every source to every microphone of an array, (B, D, nsample) float64 on the GPU: sources
+    src (B, 3) and microphones mics (D, 3) (one array for every source) or (B, D, 3), float64 on the GPU.  One
+    ``room_impulse_responses`` call over B D rows (its keywords: rir_kwargs), so row (b, d) is bit for bit the response that
+    call gives for source b and receiver mics[b, d]."""
+    if not isinstance(src, torch.Tensor) or src.dim() != 2 or src.shape[1] != 3 or src.dtype != torch.float64:
+        raise ValueError("array_impulse_responses: src must be a float64 (B, 3) tensor")
+    if not isinstance(mics, torch.Tensor) or mics.dim() not in (2, 3) or mics.shape[-1] != 3 or mics.dtype != torch.float64 \
+            or mics.shape[-2] < 1 or (mics.dim() == 3 and mics.shape[0] != src.shape[0]):
+        raise ValueError("array_impulse_responses: mics must be a float64 (D, 3) or (B, D, 3) tensor for src's B = %d"
+                         % src.shape[0])
+    _check_device(src, "array_impulse_responses")
+    _check_device(mics, "array_impulse_responses")
+    B, D = src.shape[0], mics.shape[-2]
+    rcv = (mics[None] if mics.dim() == 2 else mics).expand(B, D, 3).reshape(B * D, 3)
+    h = room_impulse_responses(src[:, None, :].expand(B, D, 3).reshape(B * D, 3), rcv, room, **rir_kwargs)
+    return h.view(B, D, h.shape[1])
+
+
+def array_spectrograms(wave, h, n_fft=N_FFT, hop=HOP):
+    """What the microphones of an array record, as spectrograms: wave (B, S) float32 clean signals and h (B, D, Nh) float64
+    impulse responses on the GPU -> (B, D, F, T) complex128, ``N.stft_complex(N.fir_same(wave, h))`` over the B D rows."""
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32:
+        raise ValueError("array_spectrograms: wave must be a float32 (B, S) tensor")
+    if not isinstance(h, torch.Tensor) or h.dim() != 3 or h.dtype != torch.float64 or h.shape[0] != wave.shape[0]:
+        raise ValueError("array_spectrograms: h must be a float64 (B, D, Nh) tensor for wave's B = %d" % wave.shape[0])
+    _check_device(wave, "array_spectrograms")
+    _check_device(h, "array_spectrograms")
+    B, D, Nh = h.shape
+    rows = wave[:, None, :].expand(B, D, wave.shape[1]).reshape(B * D, wave.shape[1])
+    spec = N.stft_complex(N.fir_same(rows, h.reshape(B * D, Nh).contiguous()), n_fft, hop)
+    return spec.view(B, D, spec.shape[1], spec.shape[2])
 
 
 def rir_generate(c, fs, r, s, L, beta=None, reverberation_time=None, nsample=None, mtype="omnidirectional", order=-1, dim=3,

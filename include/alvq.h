@@ -54,6 +54,8 @@ const char* alvq_last_error(void);
  *                        (outputs of <= 128 channels, problems with fewer than 192 tiles of 256 x 256)
  *   vq_reg 1             quantiser argmin, D <= 256: x rows in registers + double-buffered codebook tile (0: the
  *                        LDS-stationary kernel; bit-identical results)
+ *   phat_lds 1           PHAT cross-spectra / SRP-PHAT: a bin's normalised rows / an item's psi band in LDS where they fit
+ *                        (0: always re-read from global memory; bit-identical results)
  * alvq_set_option returns ALVQ_EINVAL for an unknown name; alvq_get_option returns INT64_MIN. */
 int alvq_set_option(const char* name, int64_t value);
 int64_t alvq_get_option(const char* name);
@@ -419,6 +421,62 @@ int alvq_wpe_f32(const float* X, float* Y, int* status, void* workspace, int B, 
                  int iterations, int psd_context, double eps, double loading, void* stream);
 int alvq_wpe_f64(const double* X, double* Y, int* status, void* workspace, int B, int D, int F, int T, int taps, int delay,
                  int iterations, int psd_context, double eps, double loading, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Source localisation from a microphone array's complex spectrograms (csrc/srp_phat.hip): PHAT-weighted cross-spectra,
+ * generalised cross-correlation (GCC-PHAT; Knapp, Carter 1976) and the steered response power map (SRP-PHAT; DiBiase 2000).
+ * All arithmetic is float64 (a complex64 value is widened first).  No atomics, no host sync, graph-capturable; every sum
+ * runs in one order that depends on sizes alone: an item has the same bits alone or in any batch and on any run, and a
+ * candidate has the same bits alone or in any grid.
+ *   X      device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128 ("_f64"); D microphones,
+ *          F = n_fft / 2 + 1 bins.
+ *   pairs  p = (i, j), i < j, in lexicographic order: (0,1), (0,2), ... (0,D-1), (1,2), ...;  P = D (D - 1) / 2.
+ *   band   the bins f_lo .. f_hi inclusive, 0 <= f_lo <= f_hi < F.
+ *   u(z)   = z / hypot(re z, im z), and 0 for z = 0: the unit phasor, taken per microphone, so no product |X_i| |X_j| is
+ *          formed that could overflow or underflow.
+ *   w_f    = 1 for f = 0 and for f = n_fft / 2 when n_fft is even, 2 otherwise;  W1 = sum of w_f over the band.
+ *
+ * PHAT cross-spectrum:
+ *   psi[b, p, f] = (1 / T) sum_t u(X_i[b, f, t]) conj(u(X_j[b, f, t]))   inside the band, exactly 0 outside it.
+ * psi: device (B, P, F) complex128.  status: device (B,) int32, the bits 1 and 2 of the table below.  Two launches (one
+ * workgroup a (b, f) bin, then one an item for status).  The D rows of a bin are normalised once and kept in LDS where
+ * 16 D T bytes fit, and normalised again at every use otherwise; both ways give the same bits (option phat_lds = 0 forces
+ * the second).  A pair's sum: lane l of a wave adds t = l, l + 64, ... rising, the 64 lane sums meet in wave_sum's
+ * butterfly, and the total is divided by T. */
+int alvq_phat_cross_spectra_f32(const float* X, double* psi, int* status, int B, int D, int F, int T, int f_lo, int f_hi,
+                                void* stream);
+int alvq_phat_cross_spectra_f64(const double* X, double* psi, int* status, int B, int D, int F, int T, int f_lo, int f_hi,
+                                void* stream);
+
+/* GCC-PHAT at the integer lags l = -L .. L (F = n_fft / 2 + 1):
+ *   r[b, p, L + l] = (1 / W1) sum_f w_f Re(psi[b, p, f] e^{+j 2 pi f l / n_fft})   over the band, f rising.
+ * With this sign the peak lag is (arrival at i) minus (arrival at j), in samples.  The angle is reduced exactly, as
+ * 2 pi ((f l) mod n_fft) / n_fft.  r: device (B, P, 2 L + 1) float64.  0 <= L <= n_fft / 2.  One launch. */
+int alvq_gcc_phat_f64(const double* psi, double* r, int B, int D, int n_fft, int L, int f_lo, int f_hi, void* stream);
+
+/* SRP-PHAT over candidate positions.  mics: device float64, D positions (x, y, z) per item, item b at mics + b mics_stride;
+ * cand: G positions per item at cand + b cand_stride (strides in doubles; 0 = one array / one grid serves every item).
+ *   tau_d(q)  = |q - m_d| / c
+ *   S[b, g]   = (1 / (P W1)) sum_p sum_f w_f Re(psi[b, p, f] e^{+j 2 pi f (fs / n_fft) (tau_i(q_g) - tau_j(q_g))})
+ * so S = 1 for perfectly coherent arrivals from q_g.  map: device (B, G) float64; best: device (B,) int32, the arg-max of
+ * the item's row with the lowest index winning ties; status: device (B,) int32 bit flags:
+ *   1  a non-finite spectrogram value inside the band (seen as a non-finite psi)   map row all NaN, best -1
+ *   2  every psi of the item inside the band is 0 (silence)                        map row all 0,   best -1
+ *   4  a non-finite microphone or candidate coordinate of the item                 map row all NaN, best -1
+ * (NaN wins where bit 2 meets bit 4.)  Nothing on the host reads status: the caller does, when it can sync.
+ * How it is evaluated: a thread owns a candidate.  For every bin f of the band, rising, it holds the D phasors
+ * z_d = e^{j pi x}, x = (2 f (fs / n_fft)) tau_d: from sincospi at the bins f_lo + 8 n (the anchors), and at the bins between
+ * from the rotation recurrence z_d <- z_d w_d, w_d = e^{j pi (2 (fs / n_fft)) tau_d}, in fused multiply-adds.  Then
+ *   s_f = sum_{i = 0}^{D - 2} Re(z_i sum_{j = i + 1}^{D - 1} psi[(i, j), f] conj(z_j))      i and j rising, fused
+ *         multiply-adds, the inner sum from 0
+ * and S = (sum_f w_f s_f) / (P W1), f rising from 0: an order (and anchors) that depend on (D, f_lo, f_hi) alone.  The item's
+ * psi[:, band] is staged in the workgroup's LDS where 16 P F_band bytes fit and read from global memory otherwise; both
+ * ways give the same bits (option phat_lds = 0 forces the second).  Three launches: status, map, arg-max.
+ * Limits of all four: 1 <= B <= 65535; 2 <= D <= 8; 1 <= T <= 65535; B F <= 2^31 - 1; n_fft >= 2; G >= 1,
+ * B G <= 2^31 - 1; fs, c > 0 and finite; mics_stride 0 or >= 3 D, cand_stride 0 or >= 3 G. */
+int alvq_srp_phat_f64(const double* psi, const double* mics, const double* cand, double* map, int* best, int* status, int B,
+                      int D, int G, int64_t mics_stride, int64_t cand_stride, double fs, int n_fft, double c, int f_lo,
+                      int f_hi, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
