@@ -141,6 +141,12 @@ _SIGNATURES = {
     "alvq_gcc_phat_f64": (_i32, [_c_void_p] * 2 + [_i32] * 6 + [_c_void_p]),
     "alvq_srp_phat_f64": (_i32, [_c_void_p] * 6 + [_i32] * 3 + [_i64] * 2 + [ctypes.c_double, _i32, ctypes.c_double, _i32, _i32,
                                                                             _c_void_p]),
+    "alvq_spatial_covariance_f32": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
+    "alvq_spatial_covariance_f64": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
+    "alvq_steering_vectors_f64": (_i32, [_c_void_p] * 4 + [_i32] * 3 + [ctypes.c_double, _i32, ctypes.c_double, _i32, _i32, _c_void_p]),
+    "alvq_beamform_weights_f64": (_i32, [_c_void_p] * 5 + [_i32] * 5 + [ctypes.c_double, _c_void_p]),
+    "alvq_beamform_apply_f32": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_beamform_apply_f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1070,6 +1076,95 @@ def srp_phat(psi, mics, cand, fs, n_fft, c, f_lo, f_hi):
                                    3 * D if mics.dim() == 3 else 0, 3 * G if cand.dim() == 3 else 0, float(fs), int(n_fft),
                                    float(c), int(f_lo), int(f_hi), _stream()), "alvq_srp_phat_f64")
     return out, best, status
+
+
+# ----------------------------------------------------------------------------------------------- beamforming
+def _spec4_real(spec4d, who):
+    """(real dtype, (B, D, F, T), the contiguous interleaved view) of a complex (B, D, F, T) spectrogram."""
+    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
+        raise RuntimeError("%s: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
+                           % (who, spec4d.dtype, tuple(spec4d.shape)))
+    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
+    return real, tuple(spec4d.shape), torch.view_as_real(spec4d.resolve_conj().contiguous())
+
+
+def _c128(t, shape, who, name):
+    """The contiguous interleaved view of a complex128 tensor of the given shape."""
+    if t.dtype != torch.complex128 or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s: %s must be complex128 %s (got %s %s)" % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
+    return torch.view_as_real(t.resolve_conj().contiguous())
+
+
+def spatial_covariance(spec4d, mask=None):
+    """Mask-weighted spatial covariances (alvq_spatial_covariance_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 and
+    mask (B, F, T) float64 or None on the GPU -> (Phi (B, F, D, D) complex128, status (B, F) int32).  status is the kernel's
+    per-bin flag (include/alvq.h) and is not read here."""
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "spatial_covariance")
+    if mask is not None:
+        if mask.dtype != torch.float64 or tuple(mask.shape) != (B, F, T):
+            raise RuntimeError("spatial_covariance: mask must be float64 (%d, %d, %d) (got %s %s)"
+                               % (B, F, T, mask.dtype, tuple(mask.shape)))
+        mask = mask.contiguous()
+    phi = torch.empty((B, F, D, D, 2), device=spec4d.device, dtype=torch.float64)
+    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
+    _call_real("spatial_covariance", real, _ptr(xr, real, "spec"), _ptr(mask, torch.float64, "mask"), _ptr(phi, torch.float64),
+               _ptr(status, torch.int32), B, D, F, T)
+    return torch.view_as_complex(phi), status
+
+
+def steering_vectors(mics, src, F, fs, n_fft, c, ref):
+    """Steering vectors (alvq_steering_vectors_f64): microphones mics (D, 3) or (B, D, 3) and positions src (B, 3), float64 on
+    the GPU -> (A (B, D, F) complex128, status (B,) int32).  A two-dimensional mics serves every item."""
+    if src.dim() != 2 or src.shape[1] != 3:
+        raise RuntimeError("steering_vectors: src must be (B, 3) (got %s)" % (tuple(src.shape),))
+    B = src.shape[0]
+    if mics.dim() not in (2, 3) or mics.shape[-1] != 3 or (mics.dim() == 3 and mics.shape[0] != B):
+        raise RuntimeError("steering_vectors: mics must be (D, 3) or (%d, D, 3) (got %s)" % (B, tuple(mics.shape)))
+    mics, src = mics.contiguous(), src.contiguous()
+    D = mics.shape[-2]
+    A = torch.empty((B, D, int(F), 2), device=src.device, dtype=torch.float64)
+    status = torch.empty((B,), device=src.device, dtype=torch.int32)
+    _check(lib().alvq_steering_vectors_f64(_ptr(mics, torch.float64, "mics"), _ptr(src, torch.float64, "src"), _ptr(A, torch.float64),
+                                           _ptr(status, torch.int32), B, D, int(F), float(fs), int(n_fft), float(c), int(ref),
+                                           1 if mics.dim() == 3 else 0, _stream()), "alvq_steering_vectors_f64")
+    return torch.view_as_complex(A), status
+
+
+BEAMFORM_DAS, BEAMFORM_MVDR, BEAMFORM_SOUDEN = 0, 1, 2
+
+
+def beamform_weights(mode, B, D, F, phi_n=None, phi_s=None, steering=None, ref=0, loading=0.0):
+    """Beamformer weights (alvq_beamform_weights_f64): mode BEAMFORM_DAS (steering), BEAMFORM_MVDR (phi_n, steering) or
+    BEAMFORM_SOUDEN (phi_n, phi_s); phi_* (B, F, D, D) and steering (B, D, F), complex128 on the GPU -> (W (B, F, D)
+    complex128, status (B, F) int32).  What a mode does not read is not passed on."""
+    who = "beamform_weights"
+    need = {BEAMFORM_DAS: (False, False, True), BEAMFORM_MVDR: (True, False, True), BEAMFORM_SOUDEN: (True, True, False)}.get(mode)
+    if need is None:
+        raise RuntimeError("%s: mode must be 0, 1 or 2 (got %r)" % (who, mode))
+    given = ((phi_n, (B, F, D, D), "phi_n"), (phi_s, (B, F, D, D), "phi_s"), (steering, (B, D, F), "steering"))
+    views = []
+    for wanted, (t, shape, name) in zip(need, given):
+        if wanted and t is None:
+            raise RuntimeError("%s: mode %d needs %s" % (who, mode, name))
+        views.append(_c128(t, shape, who, name) if wanted else None)
+    device = next(v for v in views if v is not None).device
+    W = torch.empty((B, F, D, 2), device=device, dtype=torch.float64)
+    status = torch.empty((B, F), device=device, dtype=torch.int32)
+    _check(lib().alvq_beamform_weights_f64(_ptr(views[0], torch.float64, "phi_n"), _ptr(views[1], torch.float64, "phi_s"),
+                                           _ptr(views[2], torch.float64, "steering"), _ptr(W, torch.float64),
+                                           _ptr(status, torch.int32), B, D, F, int(mode), int(ref), float(loading), _stream()),
+           "alvq_beamform_weights_f64")
+    return torch.view_as_complex(W), status
+
+
+def beamform_apply(spec4d, w):
+    """y = w^H x (alvq_beamform_apply_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 and w (B, F, D) complex128 on the
+    GPU -> (B, F, T) of spec4d's dtype."""
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "beamform_apply")
+    wr = _c128(w, (B, F, D), "beamform_apply", "w")
+    out = torch.empty((B, F, T, 2), device=spec4d.device, dtype=real)
+    _call_real("beamform_apply", real, _ptr(xr, real, "spec"), _ptr(wr, torch.float64, "w"), _ptr(out, real), B, D, F, T)
+    return torch.view_as_complex(out)
 
 
 def tsne_code_sqdist(codes):

@@ -479,6 +479,67 @@ int alvq_srp_phat_f64(const double* psi, const double* mics, const double* cand,
                       int f_hi, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Beamforming of a microphone array's complex spectrograms (csrc/beamform.hip): D channels into one.  Delay-and-sum, MVDR
+ * with a steering vector (Capon 1969; MPDR where the covariance is the observed mixture's) and MVDR from two covariances
+ * (Souden, Benesty, Affes 2010).  All arithmetic is float64 (a complex64 value is widened first); only Y is rounded.  No
+ * atomics, no host sync, graph-capturable; every sum runs in one order that depends on the bin's sizes alone: a bin has the
+ * same bits alone, in any batch and on any run.  Every (b, f) bin is a problem of its own.
+ * Limits of all: 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 1 <= D <= 8; 1 <= T <= 65535.  Every launch caps its grid at 65536
+ * workgroups and strides over the bins beyond, so every size within the limits launches.
+ *   X      device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128 ("_f64"); D microphones.
+ *
+ * Spatial covariance.  mask: device (B, F, T) float64 weights m_t >= 0, or NULL: every m_t = 1.
+ *   Phi[b, f][i][j] = sum_t m_t x_i[t] conj(x_j[t]) / sum_t m_t
+ * Phi: device (B, F, D, D) complex128.  Only i >= j is computed: the upper triangle is written as the exact conjugate of the
+ * lower, and the diagonal's imaginary part is exactly +0.  status: device (B, F) int32: 0, or 1 = a non-finite value of X in
+ * the bin, a negative or non-finite mask value, or sum_t m_t = 0 (not > 0); Phi of such a bin is all zeros.
+ * One launch.  A wave owns a bin where T <= 1024 (four bins a workgroup), the workgroup of four waves above that.  A thread
+ * adds the frames t = l, l + 64 W, l + 128 W, ... rising (W the waves a bin has, l the lane, or the thread's index where
+ * W = 4).  A frame's term: y = m_t x_i (two products), then by fused multiply-adds re += y.re x_j.re, re += y.im x_j.im,
+ * im += y.im x_j.re, im -= y.re x_j.im, in that order; the diagonal has the real part alone.  The lane sums meet in wave_sum's
+ * butterfly and the four wave totals are added in wave order; each total is divided by the mask's sum, which is added the
+ * same way. */
+int alvq_spatial_covariance_f32(const float* X, const double* mask, double* Phi, int* status, int B, int D, int F, int T,
+                                void* stream);
+int alvq_spatial_covariance_f64(const double* X, const double* mask, double* Phi, int* status, int B, int D, int F, int T,
+                                void* stream);
+
+/* Steering vectors of a position.  mics: device float64, D positions (x, y, z), one array for every item or (mics_batched
+ * != 0) one per item, (B, D, 3); src: device (B, 3) float64.  With tau_d = |q - m_d| / c for the item's position q,
+ *   A[b, d, f] = exp(-j 2 pi f (fs / n_fft) (tau_d - tau_ref))
+ * evaluated as cos - j sin of pi x, x = (2 f) (fs / n_fft) (tau_d - tau_ref), by sincospi.  This is the sign of a spectrogram
+ * whose channel d carries S e^{-j omega r_d / c} (tests/helpers/srp_ref.py::case), so the arg-max position of
+ * alvq_srp_phat_f64 steers at its source; A[b, ref, f] = 1.  A: device (B, D, F) complex128.  status: device (B,) int32,
+ * bit 4 (the bit alvq_srp_phat_f64 uses) for a non-finite coordinate of the item; its A is then all NaN.
+ * 2 <= n_fft <= 2^24, F <= 2^24 (F need not be n_fft / 2 + 1); fs, c > 0 and finite; 0 <= ref < D.  One launch. */
+int alvq_steering_vectors_f64(const double* mics, const double* src, double* A, int* status, int B, int D, int F, double fs,
+                              int n_fft, double c, int ref, int mics_batched, void* stream);
+
+/* Beamformer weights.  Phi_n, Phi_s: device (B, F, D, D) complex128, Hermitian (of Phi_n only the lower triangle, i >= j, and
+ * the real part of its diagonal are read); A: device (B, D, F) complex128; W: device (B, F, D) complex128.
+ *   Phi' = Phi_n + loading (tr Phi_n / D) I                                        (WPE's loading rule)
+ *   mode 0  delay-and-sum:                w = a / D.  Phi_n and Phi_s are not read (may be NULL); status is 0.
+ *   mode 1  MVDR with a steering vector:  z = Phi'^-1 a by a Cholesky factorisation and two triangular solves,
+ *                                         w = z / Re(a^H z).  Phi_s is not read.  With Phi_n the mixture's covariance: MPDR.
+ *   mode 2  MVDR from two covariances:    G = Phi'^-1 Phi_s (D right-hand sides), w = G[:, ref] / Re tr G.  A is not read.
+ * status: device (B, F) int32: 0, or 2 = a Cholesky pivot <= 0 or not finite, or the denominator (Re(a^H z), Re tr G) <= 0
+ * or not finite; such a bin gets w = e_ref, which passes the reference microphone through.
+ * loading finite and >= 0; 0 <= ref < D.  One launch, a wave a bin.  tr Phi_n, Re(a^H z) = sum_r Re(conj(a_r) z_r) and
+ * Re tr G are added from 0 with the index rising; the factorisation and the solves take column k = 0 .. D - 1 (the back
+ * substitution D - 1 .. 0) with one subtraction per column on every entry. */
+int alvq_beamform_weights_f64(const double* Phi_n, const double* Phi_s, const double* A, double* W, int* status, int B, int D,
+                              int F, int mode, int ref, double loading, void* stream);
+
+/* The beamformer's output:  Y[b, f, t] = sum_d conj(W[b, f, d]) X[b, d, f, t], d rising, starting from the first product.
+ * A weight of exactly 0 adds no term (its microphone may hold anything), and a weight whose imaginary part is exactly 0
+ * multiplies both parts of x as a real number; for finite values neither changes the sum's value, and w = e_ref returns
+ * x_ref bit for bit, a NaN included: a bin that alvq_beamform_weights_f64 refused comes back as its reference microphone.
+ * Every weight 0 gives 0.  Y: device (B, F, T) of X's type; X and Y must not overlap.  One streaming launch, a thread an
+ * output. */
+int alvq_beamform_apply_f32(const float* X, const double* W, float* Y, int B, int D, int F, int T, void* stream);
+int alvq_beamform_apply_f64(const double* X, const double* W, double* Y, int B, int D, int F, int T, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
