@@ -24,6 +24,10 @@
 //                    order.  tr Phi_n, Re(a^H z) and Re tr G are added from 0 with the index rising.  The problem is 8 x 8 at
 //                    most, so v_mfma_f64 is not used, for the reason csrc/wpe.hip gives: it buys no arithmetic at the float64
 //                    vector rate and would bring a sum order of its own.
+// bf_gev_kernel      the same layout, factorisation and substitutions (bf_cholesky, bf_forward, bf_backward serve both
+//                    kernels): Y = L^-1 Phi_s, then L^-1 Y^H after a conjugate transposition by one shuffle, whose lower
+//                    triangle is C = L^-1 Phi_s L^-H; csrc/herm_eig.h takes its eigendecomposition in place; the top
+//                    eigenvector u goes back through L^H (v) and forward through L (a, k rising from the first term).
 // bf_apply_kernel<R, D>  one streaming pass: a thread an output (b, f, t) of the flattened B F T outputs, so that a row
 //                    shorter than the workgroup leaves no thread idle; it holds the bin's D weights in registers (lanes of a
 //                    wave read the same 16 D bytes: one cache line or two), has its D loads of X in flight together, and
@@ -39,6 +43,7 @@
 #include <cmath>
 
 #include "alvq_common.h"
+#include "herm_eig.h"
 
 namespace alvq {
 
@@ -240,6 +245,61 @@ __global__ __launch_bounds__(BF_THREADS) void bf_das_kernel(BfWeightArgs a) {
   }
 }
 
+// The factorisation and the two substitutions of bf_mvdr_kernel and bf_gev_kernel, on the wave's layout: lane 8 r + c holds
+// entry (r, c) of the matrix and entry r of right-hand side c.  Right-looking Cholesky on the lower triangle: column k of L
+// replaces column k of m, the pivot stays on the diagonal.  BF_BAD_SOLVE where a pivot is <= 0 or not finite.
+__device__ __forceinline__ int bf_cholesky(double2& m, int D, int r, int c, bool in) {
+  int fail = 0;
+  for (int k = 0; k < D; ++k) {
+    const double piv = __shfl(m.x, 9 * k, 64);
+    if (!(piv > 0.0 && piv <= DBL_MAX)) fail = BF_BAD_SOLVE;
+    const double l = sqrt(piv);
+    if (in && c == k && r > k) {
+      m.x /= l;
+      m.y /= l;
+    }
+    const double2 lr = bf_shfl(m, 8 * r + k), lc = bf_shfl(m, 8 * c + k);
+    if (in && c > k && r >= c) {
+      const double2 p = bf_mul_conj(lr, lc);
+      m.x -= p.x;
+      m.y -= p.y;
+    }
+  }
+  return fail;
+}
+
+__device__ __forceinline__ void bf_forward(const double2& m, double2& rhs, int D, int r, int c, bool in) {      // L y = rhs
+  for (int k = 0; k < D; ++k) {
+    const double l = sqrt(__shfl(m.x, 9 * k, 64));
+    if (r == k) {
+      rhs.x /= l;
+      rhs.y /= l;
+    }
+    const double2 yk = bf_shfl(rhs, 8 * k + c), lrk = bf_shfl(m, 8 * r + k);
+    if (in && r > k) {
+      const double2 p = bf_mul(lrk, yk);
+      rhs.x -= p.x;
+      rhs.y -= p.y;
+    }
+  }
+}
+
+__device__ __forceinline__ void bf_backward(const double2& m, double2& rhs, int D, int r, int c) {             // L^H z = y
+  for (int k = D - 1; k >= 0; --k) {
+    const double l = sqrt(__shfl(m.x, 9 * k, 64));
+    if (r == k) {
+      rhs.x /= l;
+      rhs.y /= l;
+    }
+    const double2 zk = bf_shfl(rhs, 8 * k + c), lkr = bf_shfl(m, 8 * k + r);
+    if (r < k) {
+      const double2 p = bf_conj_mul(lkr, zk);
+      rhs.x -= p.x;
+      rhs.y -= p.y;
+    }
+  }
+}
+
 __global__ __launch_bounds__(BF_THREADS) void bf_mvdr_kernel(BfWeightArgs a) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int D = a.D, r = lane >> 3, c = lane & 7;
@@ -264,48 +324,9 @@ __global__ __launch_bounds__(BF_THREADS) void bf_mvdr_kernel(BfWeightArgs a) {
   if (in && r == c) m.x += load;
 
   // every lane sees the same pivots and the same denominator, so `fail` is the same in the whole wave
-  int fail = 0;
-  for (int k = 0; k < D; ++k) {                      // column k of L replaces column k of m; the pivot stays on the diagonal
-    const double piv = __shfl(m.x, 9 * k, 64);
-    if (!(piv > 0.0 && piv <= DBL_MAX)) fail = BF_BAD_SOLVE;
-    const double l = sqrt(piv);
-    if (in && c == k && r > k) {
-      m.x /= l;
-      m.y /= l;
-    }
-    const double2 lr = bf_shfl(m, 8 * r + k), lc = bf_shfl(m, 8 * c + k);
-    if (in && c > k && r >= c) {
-      const double2 p = bf_mul_conj(lr, lc);
-      m.x -= p.x;
-      m.y -= p.y;
-    }
-  }
-  for (int k = 0; k < D; ++k) {                      // L y = rhs
-    const double l = sqrt(__shfl(m.x, 9 * k, 64));
-    if (r == k) {
-      rhs.x /= l;
-      rhs.y /= l;
-    }
-    const double2 yk = bf_shfl(rhs, 8 * k + c), lrk = bf_shfl(m, 8 * r + k);
-    if (in && r > k) {
-      const double2 p = bf_mul(lrk, yk);
-      rhs.x -= p.x;
-      rhs.y -= p.y;
-    }
-  }
-  for (int k = D - 1; k >= 0; --k) {                 // L^H z = y
-    const double l = sqrt(__shfl(m.x, 9 * k, 64));
-    if (r == k) {
-      rhs.x /= l;
-      rhs.y /= l;
-    }
-    const double2 zk = bf_shfl(rhs, 8 * k + c), lkr = bf_shfl(m, 8 * k + r);
-    if (r < k) {
-      const double2 p = bf_conj_mul(lkr, zk);
-      rhs.x -= p.x;
-      rhs.y -= p.y;
-    }
-  }
+  int fail = bf_cholesky(m, D, r, c, in);
+  bf_forward(m, rhs, D, r, c, in);                   // L y = rhs
+  bf_backward(m, rhs, D, r, c);                      // L^H z = y
 
   double den = 0.0;
   if (a.mode == BF_MVDR) {
@@ -323,6 +344,85 @@ __global__ __launch_bounds__(BF_THREADS) void bf_mvdr_kernel(BfWeightArgs a) {
     a.W[bin * D + r] = w;
   }
   if (lane == 0) a.status[bin] = fail;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- GEV
+struct BfGevArgs {
+  const double2* Phi_n;
+  const double2* Phi_s;
+  double2* W;
+  double2* RTF;
+  double* gain;
+  int* status;
+  long nbins;
+  int D, ref;
+  double loading;
+};
+
+__global__ __launch_bounds__(BF_THREADS) void bf_gev_kernel(BfGevArgs a) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int D = a.D, r = lane >> 3, c = lane & 7;
+  const bool in = r < D && c < D;
+  for (long bin = (long)blockIdx.x * BF_WAVES + wv; bin < a.nbins; bin += (long)gridDim.x * BF_WAVES) {
+  const double2 zero = make_double2(0.0, 0.0);
+  double2 m = in ? a.Phi_n[bin * (D * D) + r * D + c] : zero;
+  double2 rhs = in ? a.Phi_s[bin * (D * D) + r * D + c] : zero;
+
+  double tr = 0.0;
+  for (int i = 0; i < D; ++i) tr += __shfl(m.x, 9 * i, 64);
+  const double load = a.loading * (tr / (double)D);
+  if (in && r == c) m.x += load;
+
+  // every lane sees the same pivots, eigenvalues and a_ref, so `fail` is the same in the whole wave
+  int fail = bf_cholesky(m, D, r, c, in);
+  bf_forward(m, rhs, D, r, c, in);                   // Y = L^-1 Phi_s
+  const double2 yt = bf_shfl(rhs, 8 * c + r);
+  rhs = in ? make_double2(yt.x, -yt.y) : zero;       // Y^H
+  bf_forward(m, rhs, D, r, c, in);                   // L^-1 Y^H = C: Hermitian but for rounding; its lower triangle counts
+  const double2 low = bf_shfl(rhs, 8 * c + r);
+  double2 cm = zero;
+  if (in) cm = r > c ? rhs : (r == c ? make_double2(rhs.x, 0.0) : make_double2(low.x, -low.y));
+
+  double2 v;
+  const HermEig e = herm_eig(cm, v, D, lane);
+  if (e.status) fail = BF_BAD_SOLVE;
+  const unsigned long long tops = __ballot(r == 0 && c < D && e.rank == D - 1);
+  const int top = tops ? __ffsll((long long)tops) - 1 : 0;                 // the column of the largest eigenvalue
+  const double lmax = __shfl(e.lam, top, 64);
+  if (!(lmax > 0.0 && lmax <= DBL_MAX)) fail = BF_BAD_SOLVE;
+
+  // a = L u, k rising from the first term; the diagonal of L is the pivot's square root
+  double2 av = zero;
+  for (int k = 0; k < D; ++k) {
+    const double l = sqrt(__shfl(m.x, 9 * k, 64));
+    const double2 lrk = bf_shfl(m, 8 * r + k), uk = bf_shfl(v, 8 * k + top);
+    if (k <= r) {
+      const double2 p = k < r ? bf_mul(lrk, uk) : make_double2(l * uk.x, l * uk.y);
+      av = k == 0 ? p : make_double2(av.x + p.x, av.y + p.y);
+    }
+  }
+  const double2 u = bf_shfl(v, 8 * r + top);
+  rhs = (r < D && c == 0) ? u : zero;
+  bf_backward(m, rhs, D, r, c);                      // v = L^-H u in the lanes (r, 0)
+
+  const double2 aref = bf_shfl(av, 8 * a.ref);
+  const double den = aref.x * aref.x + aref.y * aref.y;
+  if (!(den > 0.0 && den <= DBL_MAX)) fail = BF_BAD_SOLVE;
+
+  if (r < D && c == 0) {
+    const double2 num = bf_mul_conj(av, aref);
+    double2 rtf = make_double2(num.x / den, num.y / den);
+    double2 w = bf_mul_conj(rhs, aref);
+    if (D == 1) w = rtf = make_double2(1.0, 0.0);
+    if (fail) w = rtf = make_double2(r == a.ref ? 1.0 : 0.0, 0.0);
+    a.W[bin * D + r] = w;
+    a.RTF[bin * D + r] = rtf;
+  }
+  if (lane == 0) {
+    a.gain[bin] = fail ? 0.0 : lmax;
+    a.status[bin] = fail;
+  }
   }
 }
 
@@ -459,6 +559,20 @@ extern "C" int alvq_beamform_weights_f64(const double* Phi_n, const double* Phi_
   else
     hipLaunchKernelGGL(bf_mvdr_kernel, bf_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream,
                        args);
+  return check_launch(who);
+}
+
+extern "C" int alvq_beamform_gev_f64(const double* Phi_n, const double* Phi_s, double* W, double* RTF, double* gain, int* status,
+                                     int B, int D, int F, int ref, double loading, void* stream) {
+  const char* who = "alvq_beamform_gev_f64";
+  ALVQ_REQUIRE(Phi_n && Phi_s && W && RTF && gain && status, ALVQ_EINVAL, "%s: null pointer", who);
+  const int rc = bf_check_dims(who, B, D, F);
+  if (rc != ALVQ_OK) return rc;
+  ALVQ_REQUIRE(ref >= 0 && ref < D, ALVQ_EINVAL, "%s: ref=%d (need 0 <= ref < D = %d)", who, ref, D);
+  ALVQ_REQUIRE(std::isfinite(loading) && loading >= 0.0, ALVQ_EINVAL, "%s: loading=%g must be finite and >= 0", who, loading);
+  const long nbins = (long)B * F;
+  const BfGevArgs args{(const double2*)Phi_n, (const double2*)Phi_s, (double2*)W, (double2*)RTF, gain, status, nbins, D, ref, loading};
+  hipLaunchKernelGGL(bf_gev_kernel, bf_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream, args);
   return check_launch(who);
 }
 

@@ -147,6 +147,9 @@ _SIGNATURES = {
     "alvq_beamform_weights_f64": (_i32, [_c_void_p] * 5 + [_i32] * 5 + [ctypes.c_double, _c_void_p]),
     "alvq_beamform_apply_f32": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
     "alvq_beamform_apply_f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_beamform_gev_f64": (_i32, [_c_void_p] * 6 + [_i32] * 4 + [ctypes.c_double, _c_void_p]),
+    "alvq_eigh_f64": (_i32, [_c_void_p] * 4 + [_i64, _i32, _c_void_p]),
+    "alvq_music_f64": (_i32, [_c_void_p] * 7 + [_i32] * 5 + [ctypes.c_double, _i32, ctypes.c_double] + [_i32] * 4 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1165,6 +1168,68 @@ def beamform_apply(spec4d, w):
     out = torch.empty((B, F, T, 2), device=spec4d.device, dtype=real)
     _call_real("beamform_apply", real, _ptr(xr, real, "spec"), _ptr(wr, torch.float64, "w"), _ptr(out, real), B, D, F, T)
     return torch.view_as_complex(out)
+
+
+def beamform_gev(phi_n, phi_s, ref=0, loading=0.0):
+    """GEV weights and the covariance-whitening steering estimate (alvq_beamform_gev_f64): phi_n, phi_s (B, F, D, D) complex128
+    on the GPU -> (W (B, F, D) complex128, RTF (B, F, D) complex128, gain (B, F) float64, status (B, F) int32)."""
+    who = "beamform_gev"
+    if phi_n.dim() != 4 or phi_n.shape[-1] != phi_n.shape[-2]:
+        raise RuntimeError("%s: phi_n must be (B, F, D, D) (got %s)" % (who, tuple(phi_n.shape)))
+    B, F, D, _ = phi_n.shape
+    pn, ps = _c128(phi_n, (B, F, D, D), who, "phi_n"), _c128(phi_s, (B, F, D, D), who, "phi_s")
+    W = torch.empty((B, F, D, 2), device=phi_n.device, dtype=torch.float64)
+    rtf = torch.empty((B, F, D, 2), device=phi_n.device, dtype=torch.float64)
+    gain = torch.empty((B, F), device=phi_n.device, dtype=torch.float64)
+    status = torch.empty((B, F), device=phi_n.device, dtype=torch.int32)
+    _check(lib().alvq_beamform_gev_f64(_ptr(pn, torch.float64, "phi_n"), _ptr(ps, torch.float64, "phi_s"), _ptr(W, torch.float64),
+                                       _ptr(rtf, torch.float64), _ptr(gain, torch.float64), _ptr(status, torch.int32), B, D, F,
+                                       int(ref), float(loading), _stream()), "alvq_beamform_gev_f64")
+    return torch.view_as_complex(W), torch.view_as_complex(rtf), gain, status
+
+
+# ----------------------------------------------------------------------------------------------- subspace methods
+def eigh(cov):
+    """Hermitian eigendecomposition (alvq_eigh_f64): cov (n, D, D) complex128 on the GPU, 1 <= D <= 8 -> (values (n, D) float64
+    ascending, vectors (n, D, D) complex128, status (n,) int32).  status is the kernel's per-matrix flag (include/alvq.h) and
+    is not read here."""
+    if cov.dim() != 3 or cov.shape[1] != cov.shape[2]:
+        raise RuntimeError("eigh: cov must be (n, D, D) (got %s)" % (tuple(cov.shape),))
+    n, D, _ = cov.shape
+    ar = _c128(cov, (n, D, D), "eigh", "cov")
+    lam = torch.empty((n, D), device=cov.device, dtype=torch.float64)
+    V = torch.empty((n, D, D, 2), device=cov.device, dtype=torch.float64)
+    status = torch.empty((n,), device=cov.device, dtype=torch.int32)
+    _check(lib().alvq_eigh_f64(_ptr(ar, torch.float64, "cov"), _ptr(lam, torch.float64), _ptr(V, torch.float64),
+                               _ptr(status, torch.int32), n, D, _stream()), "alvq_eigh_f64")
+    return lam, torch.view_as_complex(V), status
+
+
+def music(vectors, values, mics, cand, n_sources, fs, n_fft, c, f_lo, f_hi):
+    """The MUSIC null spectrum (alvq_music_f64): vectors (B, F, D, D) complex128 and values (B, F, D) float64 as ``eigh``
+    returns them, microphones mics (D, 3) or (B, D, 3) and candidates cand (G, 3) or (B, G, 3), float64, all on the GPU ->
+    (null (B, G) float64, best (B,) int32, status (B,) int32).  A two-dimensional mics / cand serves every item."""
+    if vectors.dim() != 4 or vectors.shape[-1] != vectors.shape[-2]:
+        raise RuntimeError("music: vectors must be (B, F, D, D) (got %s)" % (tuple(vectors.shape),))
+    B, F, D, _ = vectors.shape
+    vr = _c128(vectors, (B, F, D, D), "music", "vectors")
+    if values.dtype != torch.float64 or tuple(values.shape) != (B, F, D):
+        raise RuntimeError("music: values must be float64 %s (got %s %s)" % ((B, F, D), values.dtype, tuple(values.shape)))
+    if mics.dim() not in (2, 3) or tuple(mics.shape[-2:]) != (D, 3) or (mics.dim() == 3 and mics.shape[0] != B):
+        raise RuntimeError("music: mics must be (%d, 3) or (%d, %d, 3) (got %s)" % (D, B, D, tuple(mics.shape)))
+    if cand.dim() not in (2, 3) or cand.shape[-1] != 3 or (cand.dim() == 3 and cand.shape[0] != B):
+        raise RuntimeError("music: cand must be (G, 3) or (%d, G, 3) (got %s)" % (B, tuple(cand.shape)))
+    values, mics, cand = values.contiguous(), mics.contiguous(), cand.contiguous()
+    G = cand.shape[-2]
+    out = torch.empty((B, G), device=vectors.device, dtype=torch.float64)
+    best = torch.empty((B,), device=vectors.device, dtype=torch.int32)
+    status = torch.empty((B,), device=vectors.device, dtype=torch.int32)
+    _check(lib().alvq_music_f64(_ptr(vr, torch.float64, "vectors"), _ptr(values, torch.float64, "values"),
+                                _ptr(mics, torch.float64, "mics"), _ptr(cand, torch.float64, "cand"), _ptr(out, torch.float64),
+                                _ptr(best, torch.int32), _ptr(status, torch.int32), B, D, F, G, int(n_sources), float(fs), int(n_fft),
+                                float(c), int(f_lo), int(f_hi), 1 if mics.dim() == 3 else 0, 1 if cand.dim() == 3 else 0, _stream()),
+           "alvq_music_f64")
+    return out, best, status
 
 
 def tsne_code_sqdist(codes):

@@ -11,6 +11,8 @@ as speech and which as noise.  Float64 arithmetic, fixed-order sums, no host syn
     BF.mvdr(spec, mics, src).spec                                 # MPDR: the mixture's own covariance
     BF.mvdr(spec, mics, src, noise_mask=m_noise).spec             # MVDR: the covariance of the frames a mask calls noise
     BF.mvdr(spec, noise_mask=m_noise, speech_mask=m_speech).spec  # Souden: two masks (B, F, T), no geometry
+    BF.gev(spec, m_noise, m_speech).spec                          # GEV / max-SNR: the same two masks, an eigenvector
+    BF.gev_weights(cov_n, cov_s).rtf                              # ... and the steering vector (RTF) the masks imply
     beam, srp = BF.locate_and_beamform(spec, mics, grid)          # SRP-PHAT's arg-max over a (G, 3) grid, then MPDR at it
     FE.istft(beam.spec, length=S)                                 # (B, S): speech_metrics.stoi and si_sdr apply directly
 
@@ -37,6 +39,7 @@ from .localization import _int_in, _on_gpu, _positive
 Cov = collections.namedtuple("Cov", "cov status")
 Weights = collections.namedtuple("Weights", "w status")
 Beam = collections.namedtuple("Beam", "spec weights status")
+Gev = collections.namedtuple("Gev", "w rtf gain status")
 
 MAX_MICROPHONES = 8
 MAX_FRAMES = 65535
@@ -276,6 +279,57 @@ def mvdr(spec, mics=None, source=None, noise_mask=None, speech_mask=None, ref=0,
                                                     n_fft, c)
     _all_on_gpu(who, spec=x, mics=mics, source=source, noise_mask=noise_mask, speech_mask=speech_mask)
     return _unbatch(_mvdr(x, geometry, mics, source, noise_mask, speech_mask, ref, loading, fs, n_fft, c), batched)
+
+
+def gev_weights(noise_cov, speech_cov, ref=0, loading=1e-6):
+    """The GEV (max-SNR) beamformer of two covariances (Warsitz and Haeb-Umbach 2007) and the steering vector they imply
+    (covariance whitening, Markovich-Golan and Gannot 2015): noise_cov, speech_cov (F, D, D) or (B, F, D, D) complex128 on the
+    GPU -> ``Gev(w, rtf, gain, status)``.  With Phi' = noise_cov + loading tr(noise_cov) / D I = L L^H and (lambda_max, u) the
+    top eigenpair of L^-1 speech_cov L^-H (``subspace.eigh``'s solver, inside the kernel): v = L^-H u maximises
+    v^H speech_cov v / v^H Phi' v, a = Phi' v is the steering vector up to scale, rtf = a / a_ref the relative transfer
+    function and w = v conj(a_ref) the weights normalised to w^H rtf = 1 (the MVDR towards rtf where speech_cov has rank
+    1); gain = lambda_max.  w, rtf (B, F, D) complex128, gain (B, F) float64, status (B, F) int32: 0, or 2 = a pivot or
+    lambda_max <= 0 or not finite, a_ref = 0 or the eigensolver did not converge; such a bin gets w = rtf = e_ref and gain
+    0."""
+    who = "gev_weights"
+    _cplx(who, "noise_cov", noise_cov, (3, 4))
+    _cplx(who, "speech_cov", speech_cov, (3, 4))
+    if noise_cov.dim() != speech_cov.dim():
+        raise ValueError("%s: noise_cov and speech_cov must both have a batch dimension or neither" % who)
+    batched = noise_cov.dim() == 4
+    pn, ps = (noise_cov, speech_cov) if batched else (noise_cov[None], speech_cov[None])
+    B, F, D = pn.shape[:3]
+    for name, t in (("noise_cov", pn), ("speech_cov", ps)):
+        if tuple(t.shape) != (B, F, D, D):
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, (B, F, D, D) if batched else (F, D, D),
+                                                           tuple(t.shape) if batched else tuple(t.shape[1:])))
+    if D < 1 or D > MAX_MICROPHONES:
+        raise ValueError("%s: need 1 <= D <= 8 microphones, got D = %d" % (who, D))
+    _bins(who, "B = %d, F = %d" % (B, F), B, F)
+    _int_in(who, "ref", ref, 0, D - 1)
+    _nonneg(who, "loading", loading)
+    _on_gpu(who, pn, "noise_cov")
+    _on_gpu(who, ps, "speech_cov")
+    out = Gev(*N.beamform_gev(pn, ps, ref, float(loading)))
+    return out if batched else Gev(*(t[0] for t in out))
+
+
+def gev(spec, noise_mask, speech_mask, ref=0, loading=1e-6):
+    """The GEV beamformer from two masks: ``apply(spec, gev_weights(spatial_covariance(spec, noise_mask).cov,
+    spatial_covariance(spec, speech_mask).cov, ref, loading).w)`` -> ``Beam(spec, weights, status)`` as ``mvdr`` returns it,
+    status the covariances' OR the weights'."""
+    who = "gev"
+    x, batched = _spec4(who, spec)
+    if noise_mask is None or speech_mask is None:
+        raise ValueError("%s: both noise_mask and speech_mask are needed" % who)
+    noise_mask = _mask3(who, "noise_mask", noise_mask, x.shape, batched)
+    speech_mask = _mask3(who, "speech_mask", speech_mask, x.shape, batched)
+    _int_in(who, "ref", ref, 0, x.shape[1] - 1)
+    _nonneg(who, "loading", loading)
+    _all_on_gpu(who, spec=x, noise_mask=noise_mask, speech_mask=speech_mask)
+    noise, speech = spatial_covariance(x, noise_mask), spatial_covariance(x, speech_mask)
+    w = gev_weights(noise.cov, speech.cov, ref=ref, loading=loading)
+    return _unbatch(Beam(apply(x, w.w), w.w, noise.status | speech.status | w.status), batched)
 
 
 def locate_and_beamform(spec, mics, candidates, ref=0, loading=1e-6, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=None):

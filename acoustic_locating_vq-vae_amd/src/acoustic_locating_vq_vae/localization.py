@@ -9,6 +9,7 @@ cross-correlation (GCC-PHAT, Knapp and Carter 1976) with its time differences of
     ring = LOC.locate_on_ring(spec, mics, receiver, room, R=1, z=1)   # theta (B,): the label ``LocationModule`` regresses
     LOC.srp_phat(spec, mics, grid).best                                # (B,) the arg-max over any (G, 3) grid of positions
     LOC.tdoa(spec, max_lag=8)                                          # (B, P) seconds, pair (i, j): arrival at i minus at j
+    LOC.music(spec, mics, grid, n_sources=2).null                      # (B, G) the MUSIC null spectrum: sources are its minima
 
 Definitions (in full: include/alvq.h).  The pairs p = (i, j), i < j, run in lexicographic order, P = D (D - 1) / 2.  With
 u(z) = z / |z| (0 for z = 0) taken per microphone, psi[p, f] = mean_t u(X_i[f, t]) conj(u(X_j[f, t])) inside the band and 0
@@ -33,6 +34,7 @@ from .front_end import N_FFT, SOUND_SPEED
 GCC = collections.namedtuple("GCC", "corr lags")
 SRP = collections.namedtuple("SRP", "map best status")
 Ring = collections.namedtuple("Ring", "theta source map status")
+Music = collections.namedtuple("Music", "null best status values")
 
 MAX_MICROPHONES = 8
 MAX_FRAMES = 65535
@@ -161,6 +163,82 @@ def srp_phat(spec, mics, candidates, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=
     return SRP(out, best, status) if batched else SRP(out[0], best[0], status[0])
 
 
+def _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band):
+    """The rules ``music`` and ``music_from_covariance`` share, ValueErrors only -> the band in bins."""
+    _int_in(who, "n_sources", n_sources, 1, D - 1)
+    _positive(who, "fs", fs)
+    _positive(who, "c", c)
+    lo, hi = _band(who, band, F)
+    _geometry(who, "mics", mics, B, D)
+    _geometry(who, "candidates", candidates, B)
+    if B * candidates.shape[-2] > 2 ** 31 - 1:
+        raise ValueError("%s: need B G <= 2^31 - 1, got B = %d, G = %d" % (who, B, candidates.shape[-2]))
+    return lo, hi
+
+
+def _music(cov, cov_status, mics, candidates, n_sources, fs, n_fft, c, lo, hi):
+    """Checked arguments, cov (B, F, D, D) -> a batched Music."""
+    B, F, D, _ = cov.shape
+    values, vectors, eig_status = N.eigh(cov.reshape(B * F, D, D))
+    values, vectors, eig_status = values.view(B, F, D), vectors.view(B, F, D, D), eig_status.view(B, F)
+    null, best, status = N.music(vectors, values, mics, candidates, n_sources, fs, n_fft, c, lo, hi)
+    bins = eig_status if cov_status is None else (eig_status | cov_status)
+    flagged = (bins[:, lo:hi + 1] != 0).any(dim=1)
+    status = status | flagged.to(torch.int32)
+    null = torch.where(flagged[:, None], torch.full_like(null, float("nan")), null)
+    best = torch.where(flagged, torch.full_like(best, -1), best)
+    return Music(null, best, status, values)
+
+
+def music(spec, mics, candidates, n_sources=1, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=None):
+    """MUSIC (Schmidt 1986), the subspace locator: spec (D, F, T) or (B, D, F, T) complex64 / complex128, mics (D, 3) or
+    (B, D, 3) and candidates (G, 3) or (B, G, 3), float64, all on the GPU; 1 <= n_sources <= D - 1 is the dimension K of the
+    signal subspace -> ``Music(null, best, status, values)``.  The spatial covariance of every bin (no mask), its
+    eigendecomposition (``subspace.eigh``), then with e_k the eigenvectors of the K largest eigenvalues and a_d =
+    e^{-j 2 pi f (fs / n_fft) tau_d(q)} (``beamforming.steering_vectors``' sign), null[g] = the mean over the band's counted
+    bins of 1 - (1 / D) sum_k |e_k^H a(q_g)|^2: 0 where the steering vector lies in the signal subspace, so sources are its
+    minima.  A bin whose eigenvalues are all 0 is not counted.  null (B, G) float64; best (B,) int32 the arg-min (the lowest
+    index on ties); status (B,) int32 bits: 1 = a non-finite value, or a covariance / eigensolver status, inside the band (the
+    row is NaN), 4 = a non-finite coordinate (NaN), 2 = no counted bin (the row is 1); best is -1 with any; values
+    (B, F, D) float64, the eigenvalues ascending: their profile tells how many sources there are -- (G,), two scalars and
+    (F, D) for a (D, F, T) spec."""
+    who = "music"
+    x, batched = _spec4(who, spec, n_fft)
+    B, D, F = x.shape[0], x.shape[1], x.shape[2]
+    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band)
+    _on_gpu(who, x)
+    _on_gpu(who, mics, "mics")
+    _on_gpu(who, candidates, "candidates")
+    cov, cov_status = N.spatial_covariance(x, None)
+    out = _music(cov, cov_status, mics, candidates, n_sources, fs, n_fft, c, lo, hi)
+    return out if batched else Music(out.null[0], out.best[0], out.status[0], out.values[0])
+
+
+def music_from_covariance(cov, mics, candidates, n_sources=1, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=None):
+    """``music`` on spatial covariances the caller has formed -- ``beamforming.spatial_covariance(spec, mask).cov`` with the
+    mask of a model, say: cov (F, D, D) or (B, F, D, D) complex128 on the GPU, Hermitian (the lower triangle is read),
+    F = n_fft / 2 + 1, 2 <= D <= 8.  The covariances' own status is the caller's."""
+    who = "music_from_covariance"
+    if not isinstance(cov, torch.Tensor) or cov.dim() not in (3, 4) or cov.dtype != torch.complex128:
+        raise ValueError("%s: cov must be a complex128 (F, D, D) or (B, F, D, D) tensor" % who)
+    batched = cov.dim() == 4
+    y = cov if batched else cov[None]
+    B, F, D = y.shape[0], y.shape[1], y.shape[2]
+    if y.shape[3] != D or D < 2 or D > MAX_MICROPHONES:
+        raise ValueError("%s: need square covariances of 2 <= D <= 8 microphones, got shape %s" % (who, tuple(cov.shape)))
+    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1:
+        raise ValueError("%s: need 1 <= B <= 65535, F >= 1 and B F <= 2^31 - 1, got shape %s" % (who, tuple(cov.shape)))
+    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
+    if F != n_fft // 2 + 1:
+        raise ValueError("%s: %d frequency bins, n_fft=%d has %d" % (who, F, n_fft, n_fft // 2 + 1))
+    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band)
+    _on_gpu(who, y, "cov")
+    _on_gpu(who, mics, "mics")
+    _on_gpu(who, candidates, "candidates")
+    out = _music(y, None, mics, candidates, n_sources, fs, n_fft, c, lo, hi)
+    return out if batched else Music(out.null[0], out.best[0], out.status[0], out.values[0])
+
+
 def ring_candidates(n_angles, receiver, room, R, z, device="cuda"):
     """The positions the dataset generator can produce, as candidates: ``(theta_grid (n,), points (n, 3))`` float64 on the GPU
     with theta_k = -pi + 2 pi k / n and points = min(receiver + (R cos theta, R sin theta, z), room)
@@ -174,14 +252,23 @@ def ring_candidates(n_angles, receiver, room, R, z, device="cuda"):
     return theta, points
 
 
-def locate_on_ring(spec, mics, receiver, room, R, z, n_angles=360, **srp_kwargs):
+def locate_on_ring(spec, mics, receiver, room, R, z, n_angles=360, method="srp", n_sources=1, **srp_kwargs):
     """The classical estimate of the label ``LocationModule`` is trained on: SRP-PHAT over ``ring_candidates`` ->
     ``Ring(theta (B,), source (B, 3), map (B, n_angles), status (B,))``, theta and source those of the arg-max (of candidate
-    0 where status is not 0: read status)."""
+    0 where status is not 0: read status).  method "music" runs ``music(spec, mics, points, n_sources, ...)`` in its place:
+    map is then the null spectrum and the pick its arg-min."""
     if not isinstance(spec, torch.Tensor):
         raise ValueError("locate_on_ring: spec must be a (D, F, T) or (B, D, F, T) tensor")
+    if method not in ("srp", "music"):
+        raise ValueError("locate_on_ring: method must be 'srp' or 'music', got %r" % (method,))
+    if method == "srp" and n_sources != 1:
+        raise ValueError("locate_on_ring: n_sources goes with method 'music', got %r" % (n_sources,))
     _on_gpu("locate_on_ring", spec)
     theta, points = ring_candidates(n_angles, receiver, room, R, z, spec.device)
+    if method == "music":
+        found = music(spec, mics, points, n_sources, **srp_kwargs)
+        pick = found.best.clamp_min(0).to(torch.int64)
+        return Ring(theta[pick], points[pick], found.null, found.status)
     srp = srp_phat(spec, mics, points, **srp_kwargs)
     pick = srp.best.clamp_min(0).to(torch.int64)
     return Ring(theta[pick], points[pick], srp.map, srp.status)

@@ -539,6 +539,65 @@ int alvq_beamform_weights_f64(const double* Phi_n, const double* Phi_s, const do
 int alvq_beamform_apply_f32(const float* X, const double* W, float* Y, int B, int D, int F, int T, void* stream);
 int alvq_beamform_apply_f64(const double* X, const double* W, double* Y, int B, int D, int F, int T, void* stream);
 
+/* The GEV (max-SNR) beamformer and the covariance-whitening steering estimate from two covariances (Warsitz, Haeb-Umbach
+ * 2007; Markovich-Golan, Gannot 2015).  Phi_n, Phi_s as above (of Phi_n the lower triangle and the real part of its diagonal
+ * are read, Phi_s whole).  Per bin:
+ *   Phi' = Phi_n + loading (tr Phi_n / D) I = L L^H            (the factorisation of alvq_beamform_weights_f64)
+ *   C    = L^-1 Phi_s L^-H: Y = L^-1 Phi_s and then L^-1 Y^H by the same forward substitution; of the result the lower
+ *          triangle and the real part of the diagonal count
+ *   (lambda_max, u) = the top eigenpair of C as alvq_eigh_f64 defines it (its last column, phase rule included)
+ *   v = L^-H u (back substitution),  a = L u = Phi' v (k rising from the first term)
+ *   RTF = a / a_ref (as a conj(a_ref) / |a_ref|^2),  W = v conj(a_ref), so that W^H RTF = 1;  gain = lambda_max, the
+ *   generalised Rayleigh quotient w^H Phi_s w / w^H Phi' w at its maximum.
+ * D = 1: W = RTF = 1.  W, RTF: device (B, F, D) complex128; gain: device (B, F) float64.  status: device (B, F) int32: 0, or
+ * 2 = a pivot <= 0 or not finite, lambda_max <= 0 or not finite, |a_ref|^2 = 0 or not finite, or an eigensolver status other
+ * than 0; such a bin gets W = RTF = e_ref and gain = 0.  Limits as above; loading finite and >= 0; 0 <= ref < D.  One launch,
+ * a wave a bin. */
+int alvq_beamform_gev_f64(const double* Phi_n, const double* Phi_s, double* W, double* RTF, double* gain, int* status, int B,
+                          int D, int F, int ref, double loading, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Subspace methods (csrc/subspace.hip, csrc/herm_eig.h).  Float64 throughout, no atomics, no host sync, graph-capturable.
+ *
+ * Eigendecomposition of n_matrices complex Hermitian matrices of order D, 1 <= D <= 8.  A: device (n, D, D) complex128, of
+ * which the lower triangle (i >= j) and the real part of the diagonal are read.  Cyclic Jacobi in round-robin order: with
+ * m = D rounded up to even, step s = 0 .. m - 2 of a sweep pairs index m - 1 with s and every other index i with
+ * (2 s - i) mod (m - 1); a pair with an index >= D is a bye; the pairs of a step are disjoint and rotate together.  With
+ * nf = ||A||_F (taken as mx sqrt(sum |a / mx|^2), mx the largest |re| or |im|), u = 2^-53, the pair p < q is rotated while
+ * |a_pq| > 0.5 u nf / D:  zeta = (a_qq - a_pp) / (2 |a_pq|), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (sign(0) = 1),
+ * cs = 1 / sqrt(1 + t^2), sn = cs t a_pq / |a_pq|, J = [[cs, sn], [-conj(sn), cs]] on (p, q); A <- J^H A J with a_pq = 0,
+ * a_pp - t |a_pq| and a_qq + t |a_pq| set outright, V <- V J from V = I.  A sweep with no rotation ends the run; at most 16
+ * sweeps.  lam: device (n, D) float64, ascending (equal values in the order of their Jacobi columns); V: device (n, D, D)
+ * complex128, column k the eigenvector of lam[k], each multiplied by the unit phasor that makes its component of the
+ * largest re^2 + im^2 (the lowest index on ties) real and positive.  A = 0 gives lam = 0 and V = I.
+ * status: device (n,) int32: 0 converged; 1 a non-finite entry was read: lam and V are NaN; 2 the 16th sweep still
+ * rotated: lam and V as they stand.  One launch: a wave a matrix (lane 8 r + c holds entry (r, c) of A and of V; rows and
+ * columns travel by shuffles), four matrices a workgroup, the grid capped at 65536 workgroups with waves striding over the
+ * matrices beyond.  A matrix shares nothing with its neighbours: the same bits alone, in any batch and on any run.
+ * 1 <= n_matrices <= 2^31 - 1. */
+int alvq_eigh_f64(const double* A, double* lam, double* V, int* status, int64_t n_matrices, int D, void* stream);
+
+/* The MUSIC null spectrum over candidate positions.  V: device (B, F, D, D) complex128 and lam: device (B, F, D) float64 as
+ * alvq_eigh_f64 writes them for the (B F) spatial covariances (ascending); mics: device float64 (D, 3), or (B, D, 3) with
+ * mics_batched != 0; cand: (G, 3), or (B, G, 3) with cand_batched != 0.  With
+ *   tau_d(q) = |q - m_d| / c,   a_d = e^{-j 2 pi f (fs / n_fft) tau_d}   (alvq_steering_vectors_f64's sign)
+ * and e_k the K last columns of V[b, f] (the K largest eigenvalues: the signal subspace),
+ *   null[b, g] = mean over the counted bins f in [f_lo, f_hi] of  1 - (1 / D) sum_k |sum_d conj(e_k[d]) a_d|^2
+ * which is 0 where the steering vector lies in the signal subspace.  Sums run with the index rising (d from the first term,
+ * k over the columns D - K .. D - 1, f over the band); the result is not clamped.  A bin whose D eigenvalues are all 0 (a
+ * silent bin) is not counted.  The phasors come from alvq_srp_phat_f64's rotation recurrence, anchors at f_lo + 8 n included.
+ * null: device (B, G) float64; best: device (B,) int32, the arg-min of the item's row, the lowest index on ties;
+ * status: device (B,) int32 bit flags:
+ *   1  a non-finite eigenvector entry or eigenvalue inside the band      null row all NaN, best -1
+ *   2  no counted bin                                                   null row all 1,   best -1
+ *   4  a non-finite microphone or candidate coordinate of the item       null row all NaN, best -1
+ * Three launches: status, map (a thread a candidate, tiles of 256), arg-min.  Limits: 1 <= B <= 65535, 1 <= F <= 2^24,
+ * B F <= 2^31 - 1 (F need not be n_fft / 2 + 1); 2 <= D <= 8; 1 <= K <= D - 1; G >= 1, B G <= 2^31 - 1; 2 <= n_fft <= 2^24;
+ * 0 <= f_lo <= f_hi < F; fs, c > 0 and finite. */
+int alvq_music_f64(const double* V, const double* lam, const double* mics, const double* cand, double* null, int* best,
+                   int* status, int B, int D, int F, int G, int K, double fs, int n_fft, double c, int f_lo, int f_hi,
+                   int mics_batched, int cand_batched, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
