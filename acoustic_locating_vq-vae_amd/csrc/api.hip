@@ -24,6 +24,7 @@ static const OptionSpec kSpecs[OPT_COUNT] = {
     {"wide_min_tiles", "ALVQ_WIDE_MIN_TILES", 192},   // bf16: 256 x 256-tile kernels only from this many tiles (about one per CU)
     {"fx_rows", "ALVQ_FX_ROWS", 0},                   // f16mx conv row tile: 0 automatic, 128 / 256 forced
     {"fx_narrow", "ALVQ_FX_NARROW", 1},               // f16mx: 128-channel m-tile for fp32-NCL outputs of <= 128 channels
+    {"fx_epi", "ALVQ_FX_EPI", 1},                     // f16mx conv: kernels compiled for one epilogue operand set (0: the general one)
     {"conv_v2", "ALVQ_CONV_V2", 1},                   // bf16: the 256 x 256-tile kernels at all
     {"conv_k3", "ALVQ_CONV_K3", 1},                   // bf16: the shared-slab width-3 kernel (0: the generic 256 x 256 one)
     {"wgrad_v3", "ALVQ_WGRAD_V3", 3},                 // bf16 weight gradient without bias: v3 kernels for width 1 (1) / width 3 (2)

@@ -53,6 +53,13 @@ __device__ __forceinline__ void fx_load_add16(const u16* ph, const unsigned char
 
 // Store 16 consecutive channels of one row (H: 32 bytes, hi8 / lo8: 16 bytes each) and return the packed H words (the
 // sign bits of a ReLU'd output are derived from them, fx_sign_bits_of_h).
+__device__ __forceinline__ void fx_put16(u16* ph, unsigned char* pq, const unsigned (&h)[8], const unsigned (&qh)[4],
+                                         const unsigned (&ql)[4]) {
+  *(u32x4*)ph = u32x4{h[0], h[1], h[2], h[3]};
+  *(u32x4*)(ph + 8) = u32x4{h[4], h[5], h[6], h[7]};
+  *(u32x4*)pq = u32x4{qh[0], qh[1], qh[2], qh[3]};
+  *(u32x4*)(pq + 32) = u32x4{ql[0], ql[1], ql[2], ql[3]};
+}
 template <bool NOSTORE = false>
 __device__ __forceinline__ void fx_store16(u16* ph, unsigned char* pq, float s_hi, float s_lo, const float (&v)[16], unsigned (&h)[8]) {
   unsigned qh[4], ql[4];
@@ -62,10 +69,26 @@ __device__ __forceinline__ void fx_store16(u16* ph, unsigned char* pq, float s_h
     for (int e = 0; e < 4; ++e) asm volatile("" ::"v"(h[e]), "v"(h[4 + e]), "v"(qh[e]), "v"(ql[e]));
     return;
   }
-  *(u32x4*)ph = u32x4{h[0], h[1], h[2], h[3]};
-  *(u32x4*)(ph + 8) = u32x4{h[4], h[5], h[6], h[7]};
-  *(u32x4*)pq = u32x4{qh[0], qh[1], qh[2], qh[3]};
-  *(u32x4*)(pq + 32) = u32x4{ql[0], ql[1], ql[2], ql[3]};
+  fx_put16(ph, pq, h, qh, ql);
+}
+
+// A 32 x 32 accumulator fragment (lane (j, h): row j, channels (q & 3) + 8 (q >> 2) + 4 h) -> 16 consecutive channels
+// 16 h .. 16 h + 15 of row j, by one lane swap per register pair.
+__device__ __forceinline__ void fx_frag_to_row16(const f32x16& c, float (&v)[16]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const u32x2 ra = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[e]), __float_as_uint(c[8 + e]), false, false);
+    const u32x2 rb = __builtin_amdgcn_permlane32_swap(__float_as_uint(c[4 + e]), __float_as_uint(c[12 + e]), false, false);
+    v[e] = __uint_as_float(ra[0]);
+    v[4 + e] = __uint_as_float(ra[1]);
+    v[8 + e] = __uint_as_float(rb[0]);
+    v[12 + e] = __uint_as_float(rb[1]);
+  }
+}
+// one v_max_f32 per value (fmaxf costs a second one: the compiler canonicalises its operand first)
+__device__ __forceinline__ void fx_relu16(float (&v)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) asm("v_max_f32 %0, 0, %1" : "=v"(v[e]) : "v"(v[e]));
 }
 
 // Operand loads come FIRST and in bulk: one load -> use -> store chain per 32-channel tile made the epilogue a string of
@@ -132,15 +155,7 @@ __device__ __forceinline__ void wave_epilogue_fx(const ConvFxArgs& ax, const f32
     const long hoff = ro + cb0 + mi * 32;                 // elements from a plane's start to this lane's 16 channels
     const long qoff = ro * 2 + qo0 + mi * 64;             // bytes into the Q plane
     float v[16];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const u32x2 ra = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][e]), __float_as_uint(acc[mi][ni][8 + e]), false, false);
-      const u32x2 rb = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][4 + e]), __float_as_uint(acc[mi][ni][12 + e]), false, false);
-      v[e] = __uint_as_float(ra[0]);
-      v[4 + e] = __uint_as_float(ra[1]);
-      v[8 + e] = __uint_as_float(rb[0]);
-      v[12 + e] = __uint_as_float(rb[1]);
-    }
+    fx_frag_to_row16(acc[mi][ni], v);
     if (a.bias) {
       const int cb = cb0 + mi * 32;
       if (m0 + wm0 + mi * 32 + 32 <= a.M) {              // the whole 32-channel tile is real channels: four 16-byte loads
@@ -157,10 +172,7 @@ __device__ __forceinline__ void wave_epilogue_fx(const ConvFxArgs& ax, const f32
     }
     if (a.skip1) fx_join16(ld[ni].h0[mi], ld[ni].h1[mi], ld[ni].ql[mi], s_lo, v);
     if (a.skip2) fx_load_add16(a.skip2 + hoff, (const unsigned char*)(a.skip2 + ax.y_plane) + qoff, s_lo, v);
-    if (a.relu & 1) {      // one v_max_f32 per value (fmaxf costs a second one: the compiler canonicalises its operand first)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) asm("v_max_f32 %0, 0, %1" : "=v"(v[e]) : "v"(v[e]));
-    }
+    if (a.relu & 1) fx_relu16(v);
     if (a.mask_bits) {     // sign-extend bit e to a word (v_bfe_i32) and AND: two VALU instructions per element; written
                            // as asm because the compiler turns the C form into and + compare + select with wait states
       const unsigned bt = ld[ni].mb[mi];
@@ -218,13 +230,128 @@ __device__ __forceinline__ void wave_epilogue_fx(const ConvFxArgs& ax, const f32
   fp16_report(watch, ax.range_flag);
 }
 
+// wave_epilogue_fx for the operand sets the forward launches of a train step are made of, on an m-tile that lies inside
+// Mop: EPI == 1 no operand, 2 bias alone, 3 skip1 alone (ReLU and the sign bits of the output either way, at run time: they
+// load nothing).  The other operands do not exist here -- no register is held for them and no branch tests them.  Same values
+// combined in the same order and stored to the same addresses as the general body; what differs is that no load is
+// issued behind one of the wave's own stores (conv1d_bf16x3.hip, wave_epilogue_x3_ordered, says why that matters):
+//  * the bias is added into the accumulators in front of everything.  Lane (j, h) of fragment mi holds channels
+//    (q & 3) + 8 (q >> 2) + 4 h of both row blocks, so a fragment's bias is four 16-byte loads, and acc + bias is the same
+//    float on either side of the lane swap.  The tiles then load nothing.
+//  * skip1 goes one row block ahead through ONE 48-register buffer: the second block is requested after the first has
+//    been converted (64 registers of H / hi8 / lo8 words, while its 64 accumulators die) and before it is stored.
+template <int NIN, int EPI>
+__device__ __forceinline__ void wave_epilogue_fx_set(const ConvFxArgs& ax, f32x16 (&acc)[4][2], int m0, int r0, int lane, int wm0,
+                                                     int wn0) {
+  static_assert(EPI >= 1 && EPI <= 3, "1 no operand, 2 bias, 3 skip1");
+  const ConvBArgs& a = ax.b;
+  const int j = lane & 31, h = lane >> 5;
+  const int Lp1 = a.L + 1, ndata = a.B * Lp1;
+  const float s_lo = fx_pow2(ax.eb - FX_LO_SHIFT), s_hi = fx_pow2(ax.eb);
+  fx_saturating_conversions();
+  const int cb0 = m0 + wm0 + 16 * h;
+  const long qo0 = fx_q_off(cb0);
+  unsigned watch = 0;
+  bool okr[NIN], gapsr[NIN];
+#pragma unroll
+  for (int ni = 0; ni < NIN; ++ni) {
+    int b, l;
+    okr[ni] = row_valid(r0 + wn0 + ni * 32 + j, Lp1, ndata, &b, &l);
+    gapsr[ni] = !__all(okr[ni]);
+  }
+  u32x4 s1h0[4], s1h1[4], s1ql[4];   // skip1: H (2 x 16 B) and lo8 of 16 channels, per 32-channel tile
+  auto request = [&](int ni) {
+    const long ro = (long)(r0 + wn0 + ni * 32 + j) * a.Mop;
+    const u16* s1h = a.skip1 + ro + cb0;
+    const unsigned char* s1q = (const unsigned char*)(a.skip1 + ax.y_plane) + ro * 2 + qo0 + 32;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      s1h0[mi] = *(const u32x4*)(s1h + mi * 32);
+      s1h1[mi] = *(const u32x4*)(s1h + mi * 32 + 8);
+      s1ql[mi] = *(const u32x4*)(s1q + mi * 64);
+    }
+  };
+  // one tile up to its stored words; skip1 of row block ni is in the buffer
+  auto convert = [&](int ni, int mi, unsigned (&hw)[8], unsigned (&qh)[4], unsigned (&ql)[4]) {
+    float v[16];
+    fx_frag_to_row16(acc[mi][ni], v);
+    if (EPI == 3) fx_join16(s1h0[mi], s1h1[mi], s1ql[mi], s_lo, v);
+    if (a.relu & 1) fx_relu16(v);
+    if (gapsr[ni]) {                       // one 32-row block in sixteen holds a gap row: gap / tail rows stay zero
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = okr[ni] ? v[e] : 0.f;
+    }
+    fx_split<16>(v, s_hi, s_lo, hw, qh, ql);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) fp16_watch(watch, hw[e]);
+  };
+  auto store = [&](int ni, int mi, const unsigned (&hw)[8], const unsigned (&qh)[4], const unsigned (&ql)[4]) {
+    const long ro = (long)(r0 + wn0 + ni * 32 + j) * a.Mop;
+    const long hoff = ro + cb0 + mi * 32;                 // elements from a plane's start to this lane's 16 channels
+    const long qoff = ro * 2 + qo0 + mi * 64;             // bytes into the Q plane
+    fx_put16(a.y + hoff, (unsigned char*)(a.y + ax.y_plane) + qoff, hw, qh, ql);
+    if (a.bits_out) *(unsigned short*)(a.bits_out + (hoff >> 3)) = (unsigned short)fx_sign_bits_of_h(hw);
+  };
+  auto tile = [&](int ni, int mi) {
+    unsigned hw[8], qh[4], ql[4];
+    convert(ni, mi, hw, qh, ql);
+    store(ni, mi, hw, qh, ql);
+  };
+
+  if (EPI == 3) request(0);
+  if (EPI == 2) {
+    f32x4 bq[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const int c0 = m0 + wm0 + mi * 32;
+      if (c0 + 32 <= a.M) {                               // the whole 32-channel tile is real channels
+#pragma unroll
+        for (int k = 0; k < 4; ++k) bq[mi][k] = *(const f32x4*)(a.bias + c0 + 8 * k + 4 * h);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bq[mi][k][e] = (c0 + 8 * k + 4 * h + e < a.M) ? a.bias[c0 + 8 * k + 4 * h + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NIN; ++ni)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[mi][ni][q] += bq[mi][q >> 2][q & 3];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if (EPI == 3 && NIN > 1) {
+    unsigned hw[4][8], qh[4][4], ql[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) convert(0, mi, hw[mi], qh[mi], ql[mi]);
+    __builtin_amdgcn_sched_barrier(0);
+    request(NIN - 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) store(0, mi, hw[mi], qh[mi], ql[mi]);
+  } else {
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) tile(0, mi);
+  }
+  if (NIN > 1) {
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) tile(NIN - 1, mi);
+  }
+  fp16_report(watch, ax.range_flag);
+}
+
 // DBG: 1 run-time ablation switches, 2 also no fp16 MFMAs, 3 also no fp8 MFMAs (timing experiments, tools/ablate_f16mx.sh).
 // NIN: 32-row blocks per wave.  2 = the 256-row tile; 1 = a 128-row tile (a wave owns 128 x 32) for launches whose 256-row
 // grid would leave CUs idle (one m-tile: M <= 256, or few rows) -- twice the workgroups at 5/4 instead of 6/8 fragment
 // reads per MFMA.
 // MIN: 32-channel blocks per wave.  4 = the 256-channel m-tile; 2 = a 128-channel m-tile (a wave owns 64 x 32, with
 // NIN = 1) for layers of at most 128 output channels, whose 256-wide tile would spend half of its MFMAs on padding.
-template <int OUT, int KW, int DBG = 0, int NIN = 2, int MIN = 4>
+// EPI: operand set of the f16mx output's epilogue.  0 = any (wave_epilogue_fx tests every operand at run time); 1 / 2 / 3 =
+// none / bias alone / skip1 alone (wave_epilogue_fx_set).  A parameter of the KERNEL: with the general body in the same
+// kernel the register allocator sized the whole kernel for it (255 VGPRs and 288 bytes of scratch against 68).
+template <int OUT, int KW, int DBG = 0, int NIN = 2, int MIN = 4, int EPI = 0>
 __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
   typedef ConvRings G;
   constexpr int RT = 128 * NIN;          // rows per workgroup
@@ -389,7 +516,8 @@ __global__ __launch_bounds__(512, 2) void conv1d_f16mx_kernel(ConvFxArgs ax) {
     return;
   }
   if (OUT == 0) {
-    wave_epilogue_fx<NIN, DBG>(ax, acc, m0, r0, lane, wm0, wn0);
+    if constexpr (EPI != 0) wave_epilogue_fx_set<NIN, EPI>(ax, acc, m0, r0, lane, wm0, wn0);
+    else wave_epilogue_fx<NIN, DBG>(ax, acc, m0, r0, lane, wm0, wn0);
     if (DBG && (dbg & (256 | 512))) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stores have left
       __syncthreads();
@@ -653,10 +781,13 @@ extern "C" int alvq_grad_scale_f32(const float* x, int64_t n, float* state, void
   return check_launch("alvq_grad_scale_f32");
 }
 
-// conv1d_f16mx_kernel<OUT, KW, 0, NIN, MIN> sits at fx_slot(OUT, KW, NIN, MIN); (NIN, MIN) = (2, 4), (1, 4), (1, 2) -- the
-// 256-row tile, the 128-row tile, the 128-row x 128-channel tile -> 0, 1, 2.  The last exists for the fp32-NCL output only.
-static constexpr int fx_slot(int OUT, int KW, int NIN, int MIN) { return (((NIN == 1) + (MIN == 2)) * 2 + OUT) * 2 + (KW == 3); }
-typedef KernelTable<void (*)(ConvFxArgs), 12> FxTable;
+// conv1d_f16mx_kernel<OUT, KW, 0, NIN, MIN, EPI> sits at fx_slot(OUT, KW, NIN, MIN, EPI); (NIN, MIN) = (2, 4), (1, 4), (1, 2)
+// -- the 256-row tile, the 128-row tile, the 128-row x 128-channel tile -> 0, 1, 2.  The last exists for the fp32-NCL output
+// only, and EPI != 0 for the f16mx output only: the fp32-NCL store (conv_store_ncl) is not this file's and has one operand.
+static constexpr int fx_slot(int OUT, int KW, int NIN, int MIN, int EPI = 0) {
+  return ((((NIN == 1) + (MIN == 2)) * 2 + OUT) * 2 + (KW == 3)) * 4 + EPI;
+}
+typedef KernelTable<void (*)(ConvFxArgs), 48> FxTable;
 static FxTable fx_table() {
   FxTable t;
   for_values<1, 3>([&](auto kw) {
@@ -664,6 +795,9 @@ static FxTable fx_table() {
       t.put(fx_slot(out, kw, nin, 4), conv1d_f16mx_kernel<out, kw, 0, nin, 4>, ConvRings::LDS);
     }); });
     t.put(fx_slot(1, kw, 1, 2), conv1d_f16mx_kernel<1, kw, 0, 1, 2>, ConvRings::LDS);
+    for_values<2, 1>([&](auto nin) { for_values<1, 2, 3>([&](auto epi) {
+      t.put(fx_slot(0, kw, nin, 4, epi), conv1d_f16mx_kernel<0, kw, 0, nin, 4, epi>, ConvRings::LDS);
+    }); });
   });
   return t;
 }
@@ -739,5 +873,10 @@ extern "C" int alvq_conv1d_f16mx(const void* x, const void* wp, const float* bia
     return check_launch("alvq_conv1d_f16mx(dbg)");
   }
 #endif
-  return table.launch(fx_slot(y ? 0 : 1, KW, half ? 1 : 2, narrow ? 2 : 4), grid, block, s, "alvq_conv1d_f16mx", a);
+  // one of the three operand sets of a train step's forward launches, on whole m-tiles: the kernel compiled for that set
+  // (option "fx_epi" = 0 sends every launch to the general epilogue)
+  int epi = 0;
+  if (y && !skip2 && !mask && !mask_bits && !post && a.b.Mop % ConvRings::M == 0 && option(OPT_FX_EPI) != 0)
+    epi = bias ? (skip1 ? 0 : 2) : (skip1 ? 3 : 1);
+  return table.launch(fx_slot(y ? 0 : 1, KW, half ? 1 : 2, narrow ? 2 : 4, epi), grid, block, s, "alvq_conv1d_f16mx", a);
 }

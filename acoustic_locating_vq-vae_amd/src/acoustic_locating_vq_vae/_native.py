@@ -1285,7 +1285,9 @@ def tsne_descend(P, Y, update, gains, grad, stats, n_iter, exaggeration, momentu
 # KernelTimer names follow rocprofv3's kernel names -- function plus its leading template arguments -- so that bench.py's
 # per-kernel figures can be laid beside `rocprofv3 --kernel-trace --stats` line by line: conv1d_f16mx_kernel<OUT, KW, ...>,
 # conv1d_bf16x3_kernel<OUT, KW, ...>, conv1d_bf16_k3_kernel<OUT, F16>, conv1d_bf16_v2_kernel<OUT, F16>,
-# conv1d_bf16_kernel<KW, OUT, F16> (OUT: 0 = NLC output, 1 = fp32 NCL; F16: the fp16 opcodes of the bf16 kernels)
+# conv1d_bf16_kernel<KW, OUT, F16> (OUT: 0 = NLC output, 1 = fp32 NCL; F16: the fp16 opcodes of the bf16 kernels).  The "..."
+# of the f16mx name stands for <DBG, NIN, MIN, EPI>: rocprofv3 prints e.g. conv1d_f16mx_kernel<0, 3, 0, 2, 4, 2> for the
+# bias-alone epilogue (EPI = 1 / 2 / 3: no operand / bias / skip1, 0 the general one), all under the one <OUT, KW, ...> name here.
 def _conv16_name(f16, out, KW, M, rows):
     """Mirrors the dispatch in csrc/conv1d_bf16.hip: wide layers go to the 256x256-tile kernels (k3 for width 3)."""
     min_tiles = get_option("wide_min_tiles")

@@ -52,6 +52,8 @@ const char* alvq_last_error(void);
  *   fx_rows 0            f16mx / bf16x3 conv row tile: 0 automatic, 128 or 256 forced
  *   fx_narrow 1          f16mx: 128-channel m-tile for fp32-NCL outputs of <= 128 channels; bf16x3: the 128-channel m-tiles
  *                        (outputs of <= 128 channels, problems with fewer than 192 tiles of 256 x 256)
+ *   fx_epi 1             f16mx conv, f16mx output with no operand / bias alone / skip1 alone on whole 256-channel m-tiles:
+ *                        the kernel compiled for that operand set (0: the general epilogue; bit-identical results)
  *   vq_reg 1             quantiser argmin, D <= 256: x rows in registers + double-buffered codebook tile (0: the
  *                        LDS-stationary kernel; bit-identical results)
  *   phat_lds 1           PHAT cross-spectra / SRP-PHAT: a bin's normalised rows / an item's psi band in LDS where they fit

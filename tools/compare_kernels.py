@@ -10,7 +10,11 @@ two builds of the same source (the per-build unit id) and whenever the host code
 literal of the s_add_u32 behind an s_getpc_b64 (the distance from there to a __device__ variable) is blanked: it moves with the
 size of every kernel that lies between, so an untouched kernel of an object whose other kernels changed would differ by it alone.
 Code and metadata are reported separately ("code of", "metadata of", "code and metadata of"), the changed metadata lines with
-their values.  Prints one line per object and a total; exit status 1 if anything differs."""
+their values.  Prints one line per object and a total; exit status 1 if anything differs.
+
+    python tools/compare_kernels.py --stats BUILD_DIR REGEX
+
+lists instead the kernels of one build whose symbol matches REGEX: instructions, registers, spilled VGPRs, scratch, static LDS."""
 import os
 import re
 import subprocess
@@ -98,7 +102,25 @@ def compare(old_dir, new_dir, tmp):
     return nobj, nker, ndiff
 
 
+def stats(build_dir, pattern, tmp):
+    """One line per kernel of build_dir whose (mangled) symbol matches the regular expression: instructions, registers, spilled
+    VGPRs, scratch and static LDS bytes, from the disassembly and the metadata entry."""
+    keys = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+    print("%-72s %6s %5s %5s %5s %7s %8s %6s" % ("kernel", "instr", "vgpr", "agpr", "sgpr", "spilled", "scratch", "lds"))
+    for f in sorted(f for f in os.listdir(build_dir) if f.endswith(".o")):
+        co = code_object(os.path.join(build_dir, f), tmp)
+        for k, (code, meta) in sorted((kernels(co) if co else {}).items()):
+            if re.search(pattern, k):
+                val = {ln.split(":")[0].strip(" -"): ln.split(":")[1].strip() for ln in meta.splitlines() if ":" in ln}
+                print("%-72s %6d " % (k, len([ln for ln in code.splitlines() if not ln.endswith(":")])) +
+                      "%5s %5s %5s %7s %8s %6s" % tuple(val.get(key, "-") for key in keys))
+
+
 def main(argv):
+    if len(argv) == 3 and argv[0] == "--stats":               # python tools/compare_kernels.py --stats BUILD_DIR REGEX
+        with tempfile.TemporaryDirectory() as tmp:
+            stats(argv[1], argv[2], tmp)
+        return 0
     if len(argv) < 2 or len(argv) % 2:
         sys.exit(__doc__)
     tot = [0, 0, 0]
