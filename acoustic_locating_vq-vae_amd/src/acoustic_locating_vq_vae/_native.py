@@ -150,6 +150,11 @@ _SIGNATURES = {
     "alvq_beamform_gev_f64": (_i32, [_c_void_p] * 6 + [_i32] * 4 + [ctypes.c_double, _c_void_p]),
     "alvq_eigh_f64": (_i32, [_c_void_p] * 4 + [_i64, _i32, _c_void_p]),
     "alvq_music_f64": (_i32, [_c_void_p] * 7 + [_i32] * 5 + [ctypes.c_double, _i32, ctypes.c_double] + [_i32] * 4 + [_c_void_p]),
+    "alvq_auxiva_workspace_bytes": (_i64, [_i32] * 4),
+    "alvq_auxiva_f32": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
+    "alvq_auxiva_f64": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
+    "alvq_separation_masks_f32": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
+    "alvq_separation_masks_f64": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1186,6 +1191,38 @@ def beamform_gev(phi_n, phi_s, ref=0, loading=0.0):
                                        _ptr(rtf, torch.float64), _ptr(gain, torch.float64), _ptr(status, torch.int32), B, D, F,
                                        int(ref), float(loading), _stream()), "alvq_beamform_gev_f64")
     return torch.view_as_complex(W), torch.view_as_complex(rtf), gain, status
+
+
+# ----------------------------------------------------------------------------------------------- source separation
+IVA_LAPLACE, IVA_GAUSS = 0, 1
+
+
+def auxiva(spec4d, iterations, model, ref, eps, w0=None):
+    """AuxIVA (alvq_auxiva_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 and w0 (B, F, D, D) complex128 or None on the
+    GPU -> (Y of spec4d's shape and dtype, W (B, F, D, D) complex128, status (B, F) int32).  status is the kernels' per-bin
+    flag (include/alvq.h) and is not read here."""
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "auxiva")
+    nbytes = lib().alvq_auxiva_workspace_bytes(B, D, F, T)
+    if nbytes < 0:
+        raise RuntimeError("auxiva: bad dims (B=%d D=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, "
+                           "1 <= T <= 65535)" % (B, D, F, T))
+    w0r = None if w0 is None else _c128(w0, (B, F, D, D), "auxiva", "w0")
+    out = torch.empty_like(xr)
+    W = torch.empty((B, F, D, D, 2), device=spec4d.device, dtype=torch.float64)
+    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=spec4d.device, dtype=torch.uint8)
+    _call_real("auxiva", real, _ptr(xr, real, "spec"), _ptr(w0r, torch.float64, "w0"), _ptr(W, torch.float64), _ptr(out, real),
+               _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T, int(model), int(iterations), int(ref), float(eps))
+    return torch.view_as_complex(out), torch.view_as_complex(W), status
+
+
+def separation_masks(spec4d):
+    """Ratio masks (alvq_separation_masks_f32 / _f64): spec4d (B, K, F, T) complex64 / complex128 on the GPU -> (B, K, F, T)
+    float64."""
+    real, (B, K, F, T), yr = _spec4_real(spec4d, "separation_masks")
+    M = torch.empty((B, K, F, T), device=spec4d.device, dtype=torch.float64)
+    _call_real("separation_masks", real, _ptr(yr, real, "spec"), _ptr(M, torch.float64), B, K, F, T)
+    return M
 
 
 # ----------------------------------------------------------------------------------------------- subspace methods

@@ -601,6 +601,70 @@ int alvq_music_f64(const double* V, const double* lam, const double* mics, const
                    int mics_batched, int cand_batched, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * AuxIVA blind source separation of a microphone array's complex spectrograms (csrc/iva.hip): auxiliary-function independent
+ * vector analysis with iterative projection (Ono, WASPAA 2011), the determined case K = D sources, and the ratio masks of
+ * its output.  It needs no geometry and no masks, starts from W = I and is deterministic.  All arithmetic is float64 (a
+ * complex64 value is widened first); only Y is rounded.  No atomics, no host sync, graph-capturable; every sum runs in one
+ * order that depends on sizes alone: an item has the same bits alone, in any batch and on any run.
+ * Limits: 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 1 <= D <= 8; 1 <= T <= 65535; 0 <= iterations <= 256; 0 <= ref < D; eps
+ * finite and >= 0; model 0 ("laplace") or 1 ("gauss").
+ *   X, Y   device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128 ("_f64"); they must not
+ *          overlap.  X[b, d, f, t]: microphone d; Y[b, k, f, t]: source k.
+ *   W      device (B, F, D, D) complex128, the demixing matrix of every bin.  Row k extracts source k:
+ *          y_k[t] = sum_d W[k][d] x_d[t], d rising, the sum starting from the first product (a complex product is
+ *          (a.re b.re - a.im b.im, a.re b.im + a.im b.re), each part two rounded products and one sum).
+ *   W0     device (B, F, D, D) complex128 or NULL (may be W itself).  status: device (B, F) int32.
+ *
+ * Start.  W = I, or W0.
+ * Bin status before the first iteration.  A bin that holds a non-finite value, or nothing but zeros, gets status 1.  Such a bin
+ * keeps W = I (whatever W0 holds) and Y = X bit for bit, and contributes nothing to p below.
+ * One iteration:
+ *   1. Source activity.  p[b, k, t] = sum_f |y_k[f, t]|^2 over the item's bins whose status is not 1, f rising, as
+ *      p = fma(y.im, y.im, fma(y.re, y.re, p));  r = sqrt(p).
+ *   2. Weights.  model 0 (Laplace):                 phi[k, t] = 1 / max(r, eps max_t r)        (max_t r = sqrt(max_t p))
+ *                model 1 (time-varying Gaussian):   phi[k, t] = F / max(p, eps max_t p)        (F: every bin of the item)
+ *      Where a source's max_t p is 0 or a p of the source is not finite, phi = 1 for that source.  eps has WPE's meaning.
+ *   3. Update.  For each bin of status 0, for k = 0 .. D - 1 in this order, row k replaced before row k + 1 is computed:
+ *        V_k = (1 / T) sum_t phi[k, t] x_t x_t^H.  Only i >= j is computed, above the diagonal stands the exact conjugate, and
+ *              the diagonal's imaginary part is exactly +0.  A frame's term c = x_i conj(x_j) is
+ *              re = fma(x_i.im, x_j.im, x_i.re x_j.re), im = x_i.im x_j.re - x_i.re x_j.im (two rounded products, so that two
+ *              identical microphones give exactly 0), and it enters as acc = fma(phi, c, acc), on the diagonal the real
+ *              part alone.  All D matrices V_k of an iteration depend on X and phi only, not on W.
+ *        M   = W V_k, entry (r, c) = sum_j W[r][j] V_k[j][c], j rising from the first product.
+ *        Solve M w = e_k by Gaussian elimination with partial pivoting: in column j = 0 .. D - 1 the pivot is the entry of
+ *              the largest |z|^2 = re^2 + im^2 among the rows i >= j, the lowest row winning ties; the two rows are exchanged;
+ *              row r > j loses l = M[r][j] / pivot times row j (a / p is taken as a conj(p) / |p|^2).  Back substitution
+ *              j = D - 1 .. 0.
+ *        q   = Re(w^H V_k w) = sum_r (w_r.re u_r.re + w_r.im u_r.im), u = V_k w with c rising, both sums from their first term.
+ *        w  <- w / sqrt(q), part by part; then W[k][:] <- conj(w).
+ *      A pivot whose |z|^2 is 0 or not finite gives the bin status 2, and so does a q that is <= 0 or not finite.  The bin
+ *      goes back to W = I and is not updated again; it goes on contributing y = x to p.
+ * After `iterations` iterations, project back (the minimal distortion principle) onto microphone ref: A = W^-1 by the same
+ * elimination with the D columns of I as right-hand sides; a singular W (a pivot as above) gives status 2, W = I and Y = X.
+ *   Y[b, k, f, t] = A[ref][k] y_k[f, t], the image of source k at microphone ref; sum_k Y_k = x_ref up to rounding.
+ * A bin of status 1 or 2 is copied from X, bit for bit.  W is the only state carried from one iteration to the next:
+ * a + b iterations give the bits of b iterations started from the W of a (where no bin has left with status 2).
+ *
+ * Sum orders.  p: a thread owns a frame and walks f rising.  V_k: lane l of a wave adds the frames t = l, l + 64, ... rising,
+ * the 64 lane sums meet in wave_sum's butterfly, and the total is divided by T: an order that depends on T alone.
+ * 1 + 4 iterations + 1 launches on the stream (status and start; activity, weights, covariances, solves; projection); status
+ * is read on the device.  workspace: device, alvq_auxiva_workspace_bytes(B, D, F, T) = 8 B D T rounded up to 16, plus
+ * 16 B F D^3 bytes (p, then phi over it; the D matrices V_k of every bin); -1 for sizes out of range. */
+int64_t alvq_auxiva_workspace_bytes(int B, int D, int F, int T);
+int alvq_auxiva_f32(const float* X, const double* W0, double* W, float* Y, int* status, void* workspace, int B, int D, int F,
+                    int T, int model, int iterations, int ref, double eps, void* stream);
+int alvq_auxiva_f64(const double* X, const double* W0, double* W, double* Y, int* status, void* workspace, int B, int D, int F,
+                    int T, int model, int iterations, int ref, double eps, void* stream);
+
+/* Ratio masks of K separated spectrograms.  Y: device (B, K, F, T) as above, 1 <= K <= 8.
+ *   M[b, k, f, t] = |Y_k|^2 / sum_j |Y_j|^2 in float64, |z|^2 = re^2 + im^2, j rising from the first term;
+ *   1 / K where the sum is 0, and 0 where the sum is not finite.
+ * M: device (B, K, F, T) float64.  One elementwise launch.  M[:, k] and 1 - M[:, k] are the speech and noise masks of
+ * alvq_spatial_covariance_*. */
+int alvq_separation_masks_f32(const float* Y, double* M, int B, int K, int F, int T, void* stream);
+int alvq_separation_masks_f64(const double* Y, double* M, int B, int K, int F, int T, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
