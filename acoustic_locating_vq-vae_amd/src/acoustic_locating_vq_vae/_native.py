@@ -155,6 +155,9 @@ _SIGNATURES = {
     "alvq_auxiva_f64": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
     "alvq_separation_masks_f32": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
     "alvq_separation_masks_f64": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
+    "alvq_cacgmm_workspace_bytes": (_i64, [_i32] * 5),
+    "alvq_cacgmm_f32": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_cacgmm_f64": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1223,6 +1226,36 @@ def separation_masks(spec4d):
     M = torch.empty((B, K, F, T), device=spec4d.device, dtype=torch.float64)
     _call_real("separation_masks", real, _ptr(yr, real, "spec"), _ptr(M, torch.float64), B, K, F, T)
     return M
+
+
+def cacgmm(spec4d, init, iterations, floor, quadratic0=None):
+    """cACGMM mask estimation (alvq_cacgmm_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128, init and quadratic0 (or
+    None) (B, K, F, T) float64 on the GPU -> (masks (B, K, F, T), prior (B, K, T), cov (B, F, K, D, D) complex128, quadratic
+    (B, K, F, T), status (B, F) int32).  status is the kernels' per-bin flag (include/alvq.h) and is not read here."""
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "cacgmm")
+    if init.dim() != 4 or init.dtype != torch.float64 or tuple(init.shape) != (B, init.shape[1], F, T):
+        raise RuntimeError("cacgmm: init must be float64 (%d, K, %d, %d) (got %s %s)" % (B, F, T, init.dtype, tuple(init.shape)))
+    K = init.shape[1]
+    if quadratic0 is not None and (quadratic0.dtype != torch.float64 or quadratic0.shape != init.shape):
+        raise RuntimeError("cacgmm: quadratic0 must be float64 %s (got %s %s)" % (tuple(init.shape), quadratic0.dtype,
+                                                                                 tuple(quadratic0.shape)))
+    nbytes = lib().alvq_cacgmm_workspace_bytes(B, D, K, F, T)
+    if nbytes < 0:
+        raise RuntimeError("cacgmm: bad dims (B=%d D=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 2 <= D <= 8, "
+                           "1 <= K <= 8, 1 <= T <= 65535)" % (B, D, K, F, T))
+    dev = spec4d.device
+    masks = torch.empty((B, K, F, T), device=dev, dtype=torch.float64)
+    quadratic = torch.empty((B, K, F, T), device=dev, dtype=torch.float64)
+    prior = torch.empty((B, K, T), device=dev, dtype=torch.float64)
+    cov = torch.empty((B, F, K, D, D, 2), device=dev, dtype=torch.float64)
+    status = torch.empty((B, F), device=dev, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    g0, q0 = init.contiguous(), None if quadratic0 is None else quadratic0.contiguous()
+    _call_real("cacgmm", real, _ptr(xr, real, "spec"), _ptr(g0, torch.float64, "init"),
+               _ptr(q0, torch.float64, "quadratic0"), _ptr(masks, torch.float64), _ptr(prior, torch.float64),
+               _ptr(cov, torch.float64), _ptr(quadratic, torch.float64), _ptr(status, torch.int32), _ptr(ws, torch.uint8),
+               B, D, K, F, T, int(iterations), float(floor))
+    return masks, prior, torch.view_as_complex(cov), quadratic, status
 
 
 # ----------------------------------------------------------------------------------------------- subspace methods

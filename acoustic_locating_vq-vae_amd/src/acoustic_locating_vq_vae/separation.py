@@ -29,6 +29,16 @@ microphone ``ref`` (the minimal distortion principle): A = W^-1 by the same elim
 Y[b, k, f, t] = A[ref, k] y_k[f, t], the image of source k at microphone ref, in the input's dtype.  Ratio masks:
 M[b, k, f, t] = |Y_k|^2 / sum_j |Y_j|^2 in float64, j rising; 1 / K where the sum is 0 and 0 where it is not finite.
 Nothing here reads a status: the caller does, when it can sync.
+
+AuxIVA is a determined method: exactly D sources for D microphones and no class for diffuse noise.  For one or two talkers on a
+larger array the classical mask estimator is cACGMM spatial clustering (csrc/cacgmm.hip), K classes on D microphones:
+
+    init = SEP.time_masks(B, K, F, T, generator=g)                # (B, K, F, T) float64, constant over frequency
+    r = SEP.cacgmm(spec, init, iterations=20)                     # CACGMM(masks, prior, cov, quadratic, status)
+    BF.gev(spec, 1 - r.masks[:, k], r.masks[:, k])                # class k against the rest
+    SEP.cacgmm(spec, r.masks, 10, quadratic0=r.quadratic)         # ten more iterations, bit for bit
+
+Its definitions are ``cacgmm``'s docstring and, in full, include/alvq.h.
 """
 import collections
 
@@ -41,9 +51,11 @@ from .front_end import HOP, N_FFT
 from .localization import _int_in, _on_gpu
 
 IVA = collections.namedtuple("IVA", "spec w status")
+CACGMM = collections.namedtuple("CACGMM", "masks prior cov quadratic status")
 
 MAX_ITERATIONS = 256
 MODELS = {"laplace": N.IVA_LAPLACE, "gauss": N.IVA_GAUSS}
+MAX_CLASSES = 8
 
 
 def _iva_rules(who, D, iterations, model, ref, eps):
@@ -109,3 +121,67 @@ def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, ho
     spec = N.stft_complex(waves.reshape(B * D, S).contiguous(), n_fft, hop).view(B, D, F, T)
     sep = auxiva(spec, iterations, model, ref)
     return N.istft(sep.spec.reshape(B * D, F, T), n_fft, hop, S).view(B, D, S)
+
+
+def _class_array(who, name, a, B, F, T, batched, K=None):
+    """a as float64 (B, K, F, T) for a spectrogram of (B, D, F, T): (K, F, T) without the batch, and F may be 1 (every bin the
+    same), which is expanded here."""
+    lead = (B,) if batched else ()
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.dim() != len(lead) + 3:
+        raise ValueError("%s: %s must be a float64 %s tensor" % (who, name, lead + ("K", F, T)))
+    a = a if batched else a[None]
+    if a.shape[0] != B or a.shape[2] not in (1, F) or a.shape[3] != T or (K is not None and a.shape[1] != K):
+        raise ValueError("%s: %s must be %s (or with 1 in place of F), got %s"
+                         % (who, name, lead + ("K" if K is None else K, F, T), tuple(a.shape[0 if batched else 1:])))
+    if a.shape[1] < 1 or a.shape[1] > MAX_CLASSES:
+        raise ValueError("%s: need 1 <= K <= 8 classes, got K = %d" % (who, a.shape[1]))
+    return a.expand(B, a.shape[1], F, T)
+
+
+def cacgmm(spec, init, iterations=20, quadratic0=None, floor=1e-10):
+    """cACGMM spatial clustering (Ito, Araki, Nakatani, EUSIPCO 2016; csrc/cacgmm.hip): the masks of K classes -- talkers and
+    diffuse noise alike -- on D microphones, K and D independent, which is what ``auxiva`` cannot give.  spec (D, F, T) or
+    (B, D, F, T), complex64 or complex128 on the GPU, 2 <= D <= 8; init (B, K, F, T) float64 (``time_masks``), 1 <= K <= 8, or
+    (B, K, 1, T), expanded over the bins here; quadratic0 None or like init -> ``CACGMM(masks (B, K, F, T) float64 summing to 1
+    over k, prior (B, K, T), cov (B, F, K, D, D) complex128, the normalised class matrices, quadratic (B, K, F, T), status
+    (B, F) int32)``, without B for a (D, F, T) spec.  ``masks[:, k]`` and ``1 - masks[:, k]`` are the speech and noise masks of
+    ``beamforming.mvdr`` and ``gev``.  ``cacgmm(X, init, a + b)`` equals ``cacgmm(X, r.masks, b, quadratic0=r.quadratic)`` with
+    ``r = cacgmm(X, init, a)`` bit for bit.
+
+    Definitions (in full: include/alvq.h).  z[f, t] = x / |x|; gamma = init as it is, q = quadratic0 or 1.  A bin with a
+    non-finite value, a negative or non-finite init or a quadratic0 that is not > 0 gets status 1, emits masks = 1 / K, cov = I,
+    quadratic = 1 and stays out of the priors; a frame of zeros is silent: weight 0 in the M-step, gamma = prior and q = 1 after
+    the E-step.  One iteration: (1) prior[b, k, t] = the mean of gamma over the item's bins of status 0, f rising.  (2) per bin
+    and class B_k = D sum_t (gamma / q) z z^H / sum_t gamma (I for a class without weight), eigendecomposed; lambda_i <-
+    max(lambda_i, floor lambda_max), then scaled to sum to D; a failure gives status 2.  (3) per frame
+    q_k = sum_i |v_i^H z|^2 / lambda_i, l_k = log prior - log det B_k - D log q_k, gamma = softmax_k l_k.  There is no frequency
+    permutation alignment: the priors shared over frequency stand in for it, which is why the init should be constant over
+    frequency.  Nothing here reads a status: the caller does, when it can sync."""
+    who = "cacgmm"
+    x, batched = _spec4(who, spec)
+    B, D, F, T = x.shape
+    if D < 2:
+        raise ValueError("%s: need 2 <= D <= 8 microphones, got D = %d" % (who, D))
+    g0 = _class_array(who, "init", init, B, F, T, batched)
+    q0 = None if quadratic0 is None else _class_array(who, "quadratic0", quadratic0, B, F, T, batched, g0.shape[1])
+    _int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
+    _nonneg(who, "floor", floor)
+    if floor > 1:
+        raise ValueError("%s: floor must be in [0, 1], got %r" % (who, floor))
+    _on_gpu(who, x, "spec")
+    _on_gpu(who, g0, "init")
+    if q0 is not None:
+        _on_gpu(who, q0, "quadratic0")
+    out = CACGMM(*N.cacgmm(x, g0, int(iterations), float(floor), q0))
+    return out if batched else CACGMM(*(t[0] for t in out))
+
+
+def time_masks(B, K, F, T, generator=None, device="cuda"):
+    """An init for ``cacgmm`` that is constant over frequency: uniform(0, 1) + 1e-3 per (b, k, t) from ``generator``, normalised
+    over k and repeated over f -> (B, K, F, T) float64 on ``device``.  With an independent init per bin the classes of different
+    bins come out in different orders, and the masks near chance across bins."""
+    who = "time_masks"
+    for name, v, hi in (("B", B, 65535), ("K", K, MAX_CLASSES), ("F", F, 2 ** 31 - 1), ("T", T, MAX_FRAMES)):
+        _int_in(who, name, v, 1, hi)
+    m = torch.rand((B, K, 1, T), dtype=torch.float64, generator=generator, device=device) + 1e-3
+    return (m / m.sum(dim=1, keepdim=True)).expand(B, K, F, T).contiguous()

@@ -665,6 +665,70 @@ int alvq_separation_masks_f32(const float* Y, double* M, int B, int K, int F, in
 int alvq_separation_masks_f64(const double* Y, double* M, int B, int K, int F, int T, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * cACGMM spatial clustering of a microphone array's complex spectrograms (csrc/cacgmm.hip): the complex angular central
+ * Gaussian mixture model (Ito, Araki, Nakatani, EUSIPCO 2016), fitted by EM.  It gives the time-frequency masks of K classes --
+ * talkers and diffuse noise alike -- from D microphones, K and D independent: what the mask-driven beamformers take where AuxIVA
+ * (K = D, no noise class) does not apply.  All arithmetic is float64 (a complex64 value is widened first).  No atomics, no host
+ * sync, graph-capturable; every sum runs in one order that depends on sizes alone: an item has the same bits alone, in any batch
+ * and on any run.  There is no frequency permutation alignment: the priors are shared over frequency and stand in for it.
+ * Limits: 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 2 <= D <= 8; 1 <= K <= 8; 1 <= T <= 65535; 1 <= iterations <= 256;
+ * 0 <= floor <= 1.
+ *   X          device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128 ("_f64").
+ *   init       device (B, K, F, T) float64: gamma at the start (may be masks itself).
+ *   quadratic0 device (B, K, F, T) float64 or NULL: q at the start (may be quadratic itself); NULL: q = 1.
+ *   masks      device (B, K, F, T) float64: gamma after the last iteration; it sums to 1 over k up to rounding.
+ *   prior      device (B, K, T) float64: the priors of the last iteration.
+ *   cov        device (B, F, K, D, D) complex128: the normalised class matrices of the last iteration.
+ *   quadratic  device (B, K, F, T) float64: q after the last iteration.  status: device (B, F) int32.
+ *
+ * Start.  A bin (b, f) gets status 1 if it holds a value of X that is not finite, a frame whose n is not finite, an init value
+ * that is negative or not finite, or a quadratic0 value that is not > 0 and finite.  n[f, t] = |x|^2 = sum_d (re^2 + im^2), d
+ * rising from 0, each term two rounded products and their sum.  Such a bin emits masks = 1 / K, cov = I and quadratic = 1 and never
+ * contributes to the priors.  gamma = init as it is (no renormalisation) and q = quadratic0, or 1.
+ * The model is one of the directions z[f, t] = x / sqrt(n).  z is never formed: z z^H = x x^H / n and |v^H z|^2 = |v^H x|^2 / n.
+ * A frame with n == 0 is silent: it has weight 0 in both sums of step 2, and step 3 leaves it gamma[k] = prior[k, t], q = 1.
+ * (An n so small that x_i conj(x_j) underflows loses the frame's direction; scale such an input first.)
+ * One iteration:
+ *   1. Priors.  prior[b, k, t] = (sum_f gamma[b, k, f, t]) / F0 over the item's bins of status 0, f rising from 0.0; F0 is
+ *      their number.  1 / K where F0 = 0.
+ *   2. M-step.  For each bin of status 0 and each class k:
+ *        sg  = sum_t gamma[t] over the frames that are not silent.
+ *        S   = sum_t w[t] x_t x_t^H with w = gamma / (q n), 0 for a silent frame.  Only i >= j is computed.  A frame's term
+ *              c = x_i conj(x_j) is re = fma(x_i.im, x_j.im, x_i.re x_j.re), im = x_i.im x_j.re - x_i.re x_j.im (two rounded
+ *              products), and it enters as acc = fma(w, c, acc), on the diagonal the real part alone.
+ *        B_k = (D S) / sg, entry by entry and part by part; above the diagonal stands the exact conjugate and the diagonal's
+ *              imaginary part is +0.  Where sg is not > 0, B_k = I.
+ *        B_k = V diag(lambda) V^H by the cyclic Jacobi method of alvq_eigh_f64, lambda ascending (ties in Jacobi's column order).
+ *        lambda_i <- max(lambda_i, floor lambda_max);  s = sum_i lambda_i, i rising from the first;  lambda_i <- (lambda_i D) / s;
+ *        logdet_k = sum_i log lambda_i, i rising from the first.
+ *        cov[b, f, k][r][c] = sum_i lambda_i (V[r][i] conj(V[c][i])), i rising from the first term, the product's parts as in
+ *              c above (two rounded products each): exactly Hermitian.
+ *      The solver's status, or a lambda_max that is not > 0 and finite, gives the bin status 2 in the same iteration: from
+ *      then on it is treated like a bin of status 1 (it has contributed to the priors of this iteration, and to no later ones).
+ *   3. E-step.  For each bin of status 0 and each frame, with a_i = conj(v_i) / sqrt(lambda_i), part by part:
+ *        y_i = sum_d a_i[d] x_d, d rising from the first product (a complex product is (a.re b.re - a.im b.im,
+ *              a.re b.im + a.im b.re));  q_k = max((sum_i |y_i|^2) / n, 2^-1022), i rising from 0, |y|^2 = re^2 + im^2;
+ *        l_k = (log prior[k, t] - logdet_k) - D log q_k;  m = max_j l_j;
+ *        gamma_k = exp(l_k - m) / sum_j exp(l_j - m), j rising from 0; 1 / K where m = -inf (no class has a prior).
+ *      q = q_k is stored next to gamma.  A silent frame: gamma_k = prior[k, t], q = 1.
+ * After `iterations` iterations masks = gamma and quadratic = q; gamma and q are the only state carried from one iteration to
+ * the next, so a + b iterations give the bits of b iterations started from the masks and quadratic of a (where no bin has left
+ * with status 2).
+ *
+ * Sum orders.  Priors: a thread owns a frame and walks f rising.  S and sg: lane l of a wave adds the frames t = l, l + 64, ...
+ * rising, the 64 lane sums meet in wave_sum's butterfly: an order that depends on T alone.
+ * 1 + 4 iterations launches on the stream (status and start; priors, class matrices, decompositions, E-step); status is read
+ * on the device.  workspace: device, alvq_cacgmm_workspace_bytes(B, D, K, F, T) = 16 B F K D^2 + 8 B F K + 8 B K T bytes (B_k and
+ * then the matrix a of every class of every bin, their logdets, the logarithms of the priors); -1 for sizes out of range. */
+int64_t alvq_cacgmm_workspace_bytes(int B, int D, int K, int F, int T);
+int alvq_cacgmm_f32(const float* X, const double* init, const double* quadratic0, double* masks, double* prior, double* cov,
+                    double* quadratic, int* status, void* workspace, int B, int D, int K, int F, int T, int iterations,
+                    double floor, void* stream);
+int alvq_cacgmm_f64(const double* X, const double* init, const double* quadratic0, double* masks, double* prior, double* cov,
+                    double* quadratic, int* status, void* workspace, int B, int D, int K, int F, int T, int iterations,
+                    double floor, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
  * acoustic_locating_vq_vae/tsne.py).  2 <= N <= 65536 points, 1 <= L <= 4096 codes per point; every N x N matrix is
  * row-major fp32 with 64-bit element offsets.  Fixed-order sums, no atomics: bitwise reproducible.
