@@ -97,3 +97,51 @@ def direct_path(c, fs, r, s, nsample):
     h = 0.5 * (1.0 + np.cos(2.0 * np.pi * u / Tw)) * np.sinc(u) / (4.0 * np.pi * dist)
     h[np.abs(t - (np.floor(d) + 0.5)) > Tw / 2] = 0.0          # only the Tw taps floor(d) - Tw/2 + 1 ... floor(d) + Tw/2
     return h
+
+
+# ------------------------------------------------------------------------------------------------------- longdouble twins
+def ld_pi():
+    """pi in np.longdouble (np.pi is a float64)."""
+    return 4 * np.arctan(np.longdouble(1))
+
+
+def highpass_ld(h, fs):
+    """``highpass`` with its coefficients and its recurrence in np.longdouble; the input is taken as it is."""
+    LD = np.longdouble
+    W = 2 * ld_pi() * 100 / LD(fs)
+    R1 = np.exp(-W)
+    B1, B2, A1 = 2 * R1 * np.cos(W), -R1 * R1, -(1 + R1)
+    out = np.empty(len(h), dtype=LD)
+    y1 = y2 = LD(0)
+    for i, x in enumerate(np.asarray(h).astype(LD)):
+        y0 = B1 * y1 + B2 * y2 + x
+        out[i] = y0 + A1 * y1 + R1 * y2
+        y2, y1 = y1, y0
+    return out
+
+
+def rir_ld(c, fs, r, s, L, beta, nsample, order=-1, dim=3, hp_filter=True, chunk=1 << 12):
+    """``rir`` with every tap and every sum in np.longdouble, (nsample,): ``images``' own float64 (d, gain) in their order are
+    the twin's exact input (frac = d - floor(d) is exact), so the distance between the two is the rounding of ``rir``'s
+    per-tap arithmetic and of its sums.  sin(pi u) of the tap u = m - frac is taken as -(-1)^m sin(pi frac) with the
+    longdouble pi (np.sinc's pi is a float64), and sin(pi frac) from the smaller of frac and 1 - frac."""
+    LD = np.longdouble
+    d, gain = images(c, fs, r, s, L, beta, nsample, order, dim)
+    fd = np.floor(d).astype(np.int64)
+    frac, gain = (d - fd).astype(LD), gain.astype(LD)
+    Tw = window_length(fs)
+    pi = ld_pi()
+    h = np.zeros(nsample, dtype=LD)
+    m = np.arange(Tw) - Tw // 2 + 1
+    sign = np.where(m % 2 == 0, -1, 1).astype(LD)             # sin(pi (m - frac)) = -(-1)^m sin(pi frac)
+    for i in range(0, fd.size, chunk):
+        ff, gg = frac[i:i + chunk, None], gain[i:i + chunk, None]
+        t = fd[i:i + chunk, None] + m
+        u = m.astype(LD) - ff
+        zero = u == 0
+        sf = np.sin(pi * np.where(ff > 0.5, 1 - ff, ff))      # sin(pi frac) = sin(pi (1 - frac)): no digits lost next to 1
+        sinc = np.where(zero, LD(1), sign * sf / (pi * np.where(zero, LD(1), u)))
+        v = gg * (LD(0.5) * (1 + np.cos(2 * pi * u / Tw))) * sinc
+        ok = (t >= 0) & (t < nsample)
+        np.add.at(h, t[ok], v[ok])
+    return highpass_ld(h, fs) if hp_filter else h
