@@ -155,6 +155,9 @@ _SIGNATURES = {
     "alvq_auxiva_f64": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
     "alvq_separation_masks_f32": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
     "alvq_separation_masks_f64": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
+    "alvq_ilrma_workspace_bytes": (_i64, [_i32] * 5),
+    "alvq_ilrma_f32": (_i32, [_c_void_p] * 10 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
+    "alvq_ilrma_f64": (_i32, [_c_void_p] * 10 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
     "alvq_cacgmm_workspace_bytes": (_i64, [_i32] * 5),
     "alvq_cacgmm_f32": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_cacgmm_f64": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
@@ -1217,6 +1220,37 @@ def auxiva(spec4d, iterations, model, ref, eps, w0=None):
     _call_real("auxiva", real, _ptr(xr, real, "spec"), _ptr(w0r, torch.float64, "w0"), _ptr(W, torch.float64), _ptr(out, real),
                _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T, int(model), int(iterations), int(ref), float(eps))
     return torch.view_as_complex(out), torch.view_as_complex(W), status
+
+
+def ilrma(spec4d, basis0, activations0, iterations, ref, floor, w0=None):
+    """ILRMA (alvq_ilrma_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128, basis0 (B, D, F, L) and activations0
+    (B, D, L, T) float64 and w0 (B, F, D, D) complex128 or None on the GPU -> (Y of spec4d's shape and dtype, W (B, F, D, D)
+    complex128, basis, activations, status (B, F) int32).  status is the kernels' per-bin flag (include/alvq.h) and is not
+    read here."""
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "ilrma")
+    if basis0.dim() != 4 or basis0.dtype != torch.float64 or tuple(basis0.shape[:3]) != (B, D, F):
+        raise RuntimeError("ilrma: basis0 must be float64 (%d, %d, %d, L) (got %s %s)" % (B, D, F, basis0.dtype, tuple(basis0.shape)))
+    L = basis0.shape[3]
+    if activations0.dtype != torch.float64 or tuple(activations0.shape) != (B, D, L, T):
+        raise RuntimeError("ilrma: activations0 must be float64 (%d, %d, %d, %d) (got %s %s)"
+                           % (B, D, L, T, activations0.dtype, tuple(activations0.shape)))
+    nbytes = lib().alvq_ilrma_workspace_bytes(B, D, L, F, T)
+    if nbytes < 0:
+        raise RuntimeError("ilrma: bad dims (B=%d D=%d L=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, "
+                           "1 <= L <= 16, 1 <= T <= 65535)" % (B, D, L, F, T))
+    w0r = None if w0 is None else _c128(w0, (B, F, D, D), "ilrma", "w0")
+    dev = spec4d.device
+    b0, a0 = basis0.contiguous(), activations0.contiguous()
+    out = torch.empty_like(xr)
+    W = torch.empty((B, F, D, D, 2), device=dev, dtype=torch.float64)
+    basis, activations = torch.empty_like(b0), torch.empty_like(a0)
+    status = torch.empty((B, F), device=dev, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    _call_real("ilrma", real, _ptr(xr, real, "spec"), _ptr(w0r, torch.float64, "w0"), _ptr(b0, torch.float64, "basis0"),
+               _ptr(a0, torch.float64, "activations0"), _ptr(W, torch.float64), _ptr(basis, torch.float64),
+               _ptr(activations, torch.float64), _ptr(out, real), _ptr(status, torch.int32), _ptr(ws, torch.uint8),
+               B, D, L, F, T, int(iterations), int(ref), float(floor))
+    return torch.view_as_complex(out), torch.view_as_complex(W), basis, activations, status
 
 
 def separation_masks(spec4d):

@@ -39,6 +39,20 @@ larger array the classical mask estimator is cACGMM spatial clustering (csrc/cac
     SEP.cacgmm(spec, r.masks, 10, quadratic0=r.quadratic)         # ten more iterations, bit for bit
 
 Its definitions are ``cacgmm``'s docstring and, in full, include/alvq.h.
+
+AuxIVA's source model is one activity per frame, shared by all bins; it says nothing about which frequencies a source occupies.
+ILRMA (independent low-rank matrix analysis; Kitamura et al., IEEE/ACM TASLP 2016; csrc/ilrma.hip) keeps AuxIVA's demixing update
+and gives every source a rank-``bases`` non-negative model of its variance over (f, t), fitted by multiplicative updates:
+
+    b0, a0 = SEP.nmf_init(B, D, F, T, bases=2, generator=g)       # (B, D, F, L) and (B, D, L, T) float64, uniform(0, 1) + 1e-3
+    r = SEP.ilrma(spec, b0, a0, iterations=30)                    # ILRMA(spec, w, basis, activations, status)
+    SEP.ilrma(spec, r.basis, r.activations, 10, w0=r.w)           # ten more iterations, bit for bit
+    SEP.ilrma(spec, b0, a0, 30, w0=SEP.auxiva(spec, 10).w)        # started from AuxIVA, which has ordered the bins' sources
+    SEP.masks(r.spec)                                             # as for auxiva
+    SEP.separate_waves(waves, method="ilrma", bases=2, generator=g)
+
+A random start at few bins can lock the sources of different bins in different orders -- this is known of ILRMA -- which is what
+``w0`` is for.  Its definitions are ``ilrma``'s docstring and, in full, include/alvq.h.
 """
 import collections
 
@@ -48,14 +62,17 @@ from . import _native as N
 from .beamforming import MAX_FRAMES, MAX_MICROPHONES, _spec4
 from .dereverberation import _nonneg
 from .front_end import HOP, N_FFT
-from .localization import _int_in, _on_gpu
+from .localization import _int_in, _on_gpu, _positive
 
 IVA = collections.namedtuple("IVA", "spec w status")
+ILRMA = collections.namedtuple("ILRMA", "spec w basis activations status")
 CACGMM = collections.namedtuple("CACGMM", "masks prior cov quadratic status")
 
 MAX_ITERATIONS = 256
 MODELS = {"laplace": N.IVA_LAPLACE, "gauss": N.IVA_GAUSS}
+METHODS = ("auxiva", "ilrma")
 MAX_CLASSES = 8
+MAX_BASES = 16
 
 
 def _iva_rules(who, D, iterations, model, ref, eps):
@@ -67,6 +84,17 @@ def _iva_rules(who, D, iterations, model, ref, eps):
     _nonneg(who, "eps", eps)
 
 
+def _start_w(who, w0, spec, dims, batched):
+    """w0 as (B, F, D, D), or None: a complex128 tensor of the rank that mirrors spec's."""
+    if w0 is None:
+        return None
+    B, D, F, _ = dims
+    want = (B, F, D, D) if batched else (F, D, D)
+    if not isinstance(w0, torch.Tensor) or w0.dtype != torch.complex128 or tuple(w0.shape) != want:
+        raise ValueError("%s: w0 must be a complex128 %s tensor for spec %s" % (who, want, tuple(spec.shape)))
+    return w0 if batched else w0[None]
+
+
 def auxiva(spec, iterations=20, model="laplace", ref=0, eps=1e-10, w0=None):
     """AuxIVA of an array's spectrograms: spec (D, F, T) or (B, D, F, T), complex64 or complex128 on the GPU, and w0 None or a
     complex128 (F, D, D) / (B, F, D, D) start -> ``IVA(spec, w, status)``: the D separated spectrograms as microphone ``ref``
@@ -76,16 +104,74 @@ def auxiva(spec, iterations=20, model="laplace", ref=0, eps=1e-10, w0=None):
     x, batched = _spec4(who, spec)
     B, D, F, T = x.shape
     _iva_rules(who, D, iterations, model, ref, eps)
-    if w0 is not None:
-        want = (B, F, D, D) if batched else (F, D, D)
-        if not isinstance(w0, torch.Tensor) or w0.dtype != torch.complex128 or tuple(w0.shape) != want:
-            raise ValueError("%s: w0 must be a complex128 %s tensor for spec %s" % (who, want, tuple(spec.shape)))
-        w0 = w0 if batched else w0[None]
+    w0 = _start_w(who, w0, spec, x.shape, batched)
     _on_gpu(who, x, "spec")
     if w0 is not None:
         _on_gpu(who, w0, "w0")
     out = IVA(*N.auxiva(x, int(iterations), MODELS[model], int(ref), float(eps), w0))
     return out if batched else IVA(*(t[0] for t in out))
+
+
+def _ilrma_rules(who, D, iterations, ref, floor):
+    """The rules of ILRMA's keywords for D microphones; ValueErrors only."""
+    _int_in(who, "iterations", iterations, 0, MAX_ITERATIONS)
+    _int_in(who, "ref", ref, 0, D - 1)
+    _positive(who, "floor", floor)
+
+
+def ilrma(spec, basis0, activations0, iterations=20, ref=0, floor=1e-10, w0=None):
+    """ILRMA of an array's spectrograms: spec (D, F, T) or (B, D, F, T), complex64 or complex128 on the GPU; basis0 (B, D, F, L)
+    and activations0 (B, D, L, T) float64 (``nmf_init``), 1 <= L <= 16, without B for a (D, F, T) spec; w0 as for ``auxiva`` ->
+    ``ILRMA(spec, w, basis, activations, status)``: the D separated spectrograms as microphone ``ref`` heard them, the demixing
+    matrices w (B, F, D, D) complex128, the fitted factors and status (B, F) int32, the ranks mirroring spec's.
+    ``ilrma(X, b0, a0, m + n)`` equals ``ilrma(X, r.basis, r.activations, n, w0=r.w)`` with ``r = ilrma(X, b0, a0, m)`` bit for
+    bit.
+
+    Definitions (in full: include/alvq.h).  The variance of source k is r_k[f, t] = sum_l basis[k, f, l] activations[k, l, t].
+    A bin gets status 1 as in ``auxiva``, and also where its basis0 rows hold a value that is not finite or not > 0; every bin
+    of an item whose activations0 hold such a value gets it.  Such a bin keeps W = I and Y = X, its basis rows come back as
+    given, and it stays out of every sum over f.  One iteration: (1) P[k, f, t] = |y_k[f, t]|^2 and lam[k], its mean over the
+    bins whose status is not 1 (1 where that is not > 0 and finite); (2) W[f][k, :] /= sqrt(lam[k]), P /= lam[k], basis[k] =
+    max(basis[k] / lam[k], floor), which leaves the cost unchanged and puts the floor on a known scale; (3) with R = max(sum_l
+    basis activations, floor): basis <- max(basis sqrt(sum_t P R^-2 activations / sum_t activations / R), floor); (4) with R
+    recomputed: activations <- max(activations sqrt(sum_f P R^-2 basis / sum_f basis / R), floor); a ratio that is not finite
+    leaves the entry as it was, and max(., floor) sends a value that is not finite to floor; (5) with R recomputed, step (3)
+    of ``auxiva`` in every bin of status 0 with phi[k, t] replaced by 1 / R[k, f, t].  Then ``auxiva``'s projection onto
+    microphone ``ref``.  Nothing here reads a status: the caller does, when it can sync."""
+    who = "ilrma"
+    x, batched = _spec4(who, spec)
+    B, D, F, T = x.shape
+    lead = (B,) if batched else ()
+    if not isinstance(basis0, torch.Tensor) or basis0.dtype != torch.float64 or basis0.dim() != len(lead) + 3 \
+            or tuple(basis0.shape[:-1]) != lead + (D, F):
+        raise ValueError("%s: basis0 must be a float64 %s tensor for spec %s" % (who, lead + (D, F, "L"), tuple(spec.shape)))
+    L = basis0.shape[-1]
+    if L < 1 or L > MAX_BASES:
+        raise ValueError("%s: need 1 <= L <= 16 bases, got L = %d" % (who, L))
+    if not isinstance(activations0, torch.Tensor) or activations0.dtype != torch.float64 or tuple(activations0.shape) != lead + (D, L, T):
+        raise ValueError("%s: activations0 must be a float64 %s tensor for basis0 %s" % (who, lead + (D, L, T), tuple(basis0.shape)))
+    _ilrma_rules(who, D, iterations, ref, floor)
+    w0 = _start_w(who, w0, spec, x.shape, batched)
+    b0, a0 = (basis0, activations0) if batched else (basis0[None], activations0[None])
+    _on_gpu(who, x, "spec")
+    _on_gpu(who, b0, "basis0")
+    _on_gpu(who, a0, "activations0")
+    if w0 is not None:
+        _on_gpu(who, w0, "w0")
+    out = ILRMA(*N.ilrma(x, b0, a0, int(iterations), int(ref), float(floor), w0))
+    return out if batched else ILRMA(*(t[0] for t in out))
+
+
+def nmf_init(B, D, F, T, bases=2, generator=None, device="cuda"):
+    """A start for ``ilrma``, the companion of ``time_masks``: (basis0 (B, D, F, bases), activations0 (B, D, bases, T)) float64
+    on ``device``, uniform(0, 1) + 1e-3 from ``generator``, the basis drawn first."""
+    who = "nmf_init"
+    for name, v, hi in (("B", B, 65535), ("D", D, MAX_MICROPHONES), ("F", F, 2 ** 31 - 1), ("T", T, MAX_FRAMES),
+                        ("bases", bases, MAX_BASES)):
+        _int_in(who, name, v, 1, hi)
+    basis0 = torch.rand((B, D, F, bases), dtype=torch.float64, generator=generator, device=device) + 1e-3
+    activations0 = torch.rand((B, D, bases, T), dtype=torch.float64, generator=generator, device=device) + 1e-3
+    return basis0, activations0
 
 
 def masks(sep_spec):
@@ -99,11 +185,16 @@ def masks(sep_spec):
     return m if batched else m[0]
 
 
-def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, hop=HOP):
+def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, hop=HOP, method="auxiva", bases=2, generator=None):
     """Waveforms in, waveforms out: waves (B, D, S), float32 or float64 on the GPU -> (B, D, S) of the same dtype, row k
     ``front_end.istft`` of source k of ``auxiva`` on spec = ``N.stft_complex`` of the B D rows, which has F = n_fft / 2 + 1 bins
-    and T = 1 + S / hop frames, as ``beamforming.beamform_waves`` goes."""
+    and T = 1 + S / hop frames, as ``beamforming.beamform_waves`` goes.  method "ilrma": ``ilrma`` in its place, started from
+    ``nmf_init(B, D, F, T, bases, generator)``; ``model`` is AuxIVA's and must then be left at its default."""
     who = "separate_waves"
+    if not isinstance(method, str) or method not in METHODS:
+        raise ValueError("%s: method must be one of 'auxiva', 'ilrma', got %r" % (who, method))
+    if method == "ilrma" and model != "laplace":
+        raise ValueError("%s: model belongs to method 'auxiva'; with method 'ilrma' leave it at its default, got %r" % (who, model))
     if not isinstance(waves, torch.Tensor) or waves.dim() != 3:
         raise ValueError("%s: waves must be a (B, D, S) tensor" % who)
     if waves.dtype not in (torch.float32, torch.float64):
@@ -117,9 +208,15 @@ def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, ho
     if T > MAX_FRAMES or B * F > 2 ** 31 - 1:
         raise ValueError("%s: need B F <= 2^31 - 1 and T = 1 + S / hop <= 65535, got F = %d, T = %d" % (who, F, T))
     _iva_rules(who, D, iterations, model, ref, 0.0)
+    _int_in(who, "bases", bases, 1, MAX_BASES)
+    if generator is not None and not isinstance(generator, torch.Generator):
+        raise ValueError("%s: generator must be a torch.Generator or None, got %r" % (who, generator))
     _on_gpu(who, waves, "waves")
     spec = N.stft_complex(waves.reshape(B * D, S).contiguous(), n_fft, hop).view(B, D, F, T)
-    sep = auxiva(spec, iterations, model, ref)
+    if method == "ilrma":
+        sep = ilrma(spec, *nmf_init(B, D, F, T, bases, generator, waves.device), iterations=iterations, ref=ref)
+    else:
+        sep = auxiva(spec, iterations, model, ref)
     return N.istft(sep.spec.reshape(B * D, F, T), n_fft, hop, S).view(B, D, S)
 
 

@@ -665,6 +665,65 @@ int alvq_separation_masks_f32(const float* Y, double* M, int B, int K, int F, in
 int alvq_separation_masks_f64(const double* Y, double* M, int B, int K, int F, int T, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ILRMA blind source separation of a microphone array's complex spectrograms (csrc/ilrma.hip): independent low-rank matrix
+ * analysis (Kitamura, Ono, Sawada, Kameoka, Saruwatari, IEEE/ACM TASLP 2016), the determined case K = D sources.  The demixing
+ * update is AuxIVA's iterative projection (above, and the same kernels: csrc/iva_kernels.h); the source model is not one
+ * activity per frame but, per source, a non-negative matrix of rank L over (f, t),
+ *   r_k[f, t] = sum_l basis[k, f, l] activations[k, l, t],
+ * fitted by multiplicative updates between the demixing updates.  All arithmetic is float64 (a complex64 value is widened
+ * first); only Y is rounded.  No atomics, no host sync, graph-capturable; every sum runs in one order that depends on sizes
+ * alone: an item has the same bits alone, in any batch and on any run.
+ * Limits: AuxIVA's for B, D, F, T, iterations and ref; 1 <= L <= 16; floor finite and > 0.
+ *   X, Y, W, W0, status   as for alvq_auxiva_*.
+ *   basis0, basis               device (B, D, F, L) float64 (basis0 may be basis itself).
+ *   activations0, activations   device (B, D, L, T) float64 (activations0 may be activations itself).
+ * Below, floor(v) = v where v > floor and v is finite, and floor otherwise (a NaN and an infinity included); it stands where
+ * the literature writes max(v, floor).
+ *
+ * Start.  W = I, or W0; basis = basis0 and activations = activations0, copied as they are.  There is no canonical start of the
+ * model: the caller owns the randomness.
+ * Bin status before the first iteration.  AuxIVA's status 1; bin f of item b also gets status 1 when basis0[b, :, f, :] holds a
+ * value that is not finite or not > 0, and every bin of item b gets it when activations0[b] holds such a value.  A bin of
+ * status 1 keeps W = I (whatever W0 holds) and Y = X bit for bit, its rows basis[b, :, f, :] come back as they were given, on
+ * whichever account the bin was refused and after any number of iterations, and it stays out of every sum over f below.
+ * One iteration:
+ *   1. Power.  In every bin whose status is not 1 (a bin of status 2 has W = I), y = W x as AuxIVA's activity pass takes it and
+ *      P[k, f, t] = fma(y.im, y.im, y.re y.re).  s[k, f] = sum_t P; lam[k] = (sum_f s[k, f]) / (F' T) over those bins, f rising
+ *      from 0.0, F' their number, the divisor the rounded product of the two; lam[k] = 1 where that is not finite or not > 0.
+ *   2. Normalise, so that floor is on a known scale.  In the bins of status 0, W[k][d] <- W[k][d] / sqrt(lam[k]), part by
+ *      part; in the bins whose status is not 1, P <- P / lam[k] and basis[k, f, l] <- floor(basis[k, f, l] / lam[k]).  The cost
+ *      sum_{f, t, k} (P / R + log R) - 2 T sum_f log |det W_f| does not change under this step where the floor is not active.
+ *   3. Basis.  In the bins whose status is not 1: R[k, f, t] = floor(sum_l basis[k, f, l] activations[k, l, t]), l rising from
+ *      the first product, every product rounded; i = 1 / R; g = (P i) i;
+ *        num[l] = sum_t g activations[k, l, t],  den[l] = sum_t i activations[k, l, t],  each term entering by fma;
+ *        basis[k, f, l] <- floor(basis[k, f, l] sqrt(num[l] / den[l])); where the ratio is not finite, floor(basis[k, f, l]).
+ *   4. Activations.  For every (k, t), R, i and g recomputed from the new basis:
+ *        num[l] = sum_f g basis[k, f, l],  den[l] = sum_f i basis[k, f, l] over the bins whose status is not 1, f rising;
+ *        activations[k, l, t] <- floor(activations[k, l, t] sqrt(num[l] / den[l])); where the ratio is not finite (an item
+ *        without such a bin has 0 / 0), floor(activations[k, l, t]).  So no value that is not finite stays in the activations
+ *        after an iteration, nor in the basis rows of a bin whose status is not 1.
+ *   5. Demixing matrices.  R recomputed from the new factors.  Each bin of status 0 gets step 3 of AuxIVA to the letter with
+ *      phi[k, t] replaced by 1 / R[k, f, t]: V_k, the elimination, q, the normalisation, the rows replaced in the order
+ *      k = 0 .. D - 1, and the same rule for status 2.
+ * After `iterations` iterations the projection onto microphone ref is AuxIVA's.  iterations = 0 returns the start -- W = I in a
+ * bin of status 1 -- and its projection.  (W, basis, activations) is the only state carried from one iteration to the next:
+ * a + b iterations give the bits of b iterations started from the W, basis and activations of a.
+ *
+ * Sum orders.  s, and num and den of step 3: lane l of a wave adds the frames t = l, l + 64, ... rising and the 64 lane sums
+ * meet in wave_sum's butterfly: an order that depends on T alone.  lam, and num and den of step 4: one thread walks f rising.
+ * 3 + 7 iterations + 1 launches on the stream (status and start of W, of the activations, of the basis; power, lam, basis,
+ * activations, weights, covariances, solves; projection); status is read on the device.  workspace: device,
+ * alvq_ilrma_workspace_bytes(B, D, L, F, T) = 8 B D F T + 16 B F D^3 + 8 B D F + 8 B D + 4 B bytes, each term rounded up to 16
+ * (P, then 1 / R over it; the matrices V_k; s; lam; the items' flags); -1 for sizes out of range. */
+int64_t alvq_ilrma_workspace_bytes(int B, int D, int L, int F, int T);
+int alvq_ilrma_f32(const float* X, const double* W0, const double* basis0, const double* activations0, double* W, double* basis,
+                   double* activations, float* Y, int* status, void* workspace, int B, int D, int L, int F, int T, int iterations,
+                   int ref, double floor, void* stream);
+int alvq_ilrma_f64(const double* X, const double* W0, const double* basis0, const double* activations0, double* W, double* basis,
+                   double* activations, double* Y, int* status, void* workspace, int B, int D, int L, int F, int T, int iterations,
+                   int ref, double floor, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * cACGMM spatial clustering of a microphone array's complex spectrograms (csrc/cacgmm.hip): the complex angular central
  * Gaussian mixture model (Ito, Araki, Nakatani, EUSIPCO 2016), fitted by EM.  It gives the time-frequency masks of K classes --
  * talkers and diffuse noise alike -- from D microphones, K and D independent: what the mask-driven beamformers take where AuxIVA
