@@ -133,6 +133,11 @@ _SIGNATURES = {
     "alvq_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
     "alvq_lsd_f32": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
     "alvq_lsd_f64": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
+    "alvq_pairwise_si_sdr_f32": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_pairwise_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_assign_f64": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
+    "alvq_si_bss_eval_f32": (_i32, [_c_void_p] * 7 + [_i32] * 4 + [_c_void_p]),
+    "alvq_si_bss_eval_f64": (_i32, [_c_void_p] * 7 + [_i32] * 4 + [_c_void_p]),
     "alvq_wpe_workspace_bytes": (_i64, [_i32] * 5),
     "alvq_wpe_f32": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
     "alvq_wpe_f64": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
@@ -1008,6 +1013,56 @@ def lsd(p, q, eps):
     out = torch.empty((B,), device=p.device, dtype=torch.float64)
     _call_real("lsd", p.dtype, _ptr(p, p.dtype, "p"), _ptr(q, p.dtype, "q"), _ptr(out, torch.float64), B, F, T, float(eps))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- separation scores
+def _source_rows(references, estimates, who):
+    if references.dim() != 3 or estimates.dim() != 3 or references.dtype not in (torch.float32, torch.float64) \
+            or estimates.dtype != references.dtype or estimates.shape[0] != references.shape[0] \
+            or estimates.shape[2] != references.shape[2]:
+        raise RuntimeError("%s: expected float32 or float64 (B, K, n) references and (B, J, n) estimates of one dtype (got %s %s "
+                           "and %s %s)" % (who, references.dtype, tuple(references.shape), estimates.dtype, tuple(estimates.shape)))
+    return references.shape[0], references.shape[1], estimates.shape[1], references.shape[2]
+
+
+def pairwise_si_sdr(references, estimates):
+    """The SI-SDR of every pair (alvq_pairwise_si_sdr_f32 / _f64): references (B, K, n) and estimates (B, J, n) of one real
+    dtype on the GPU -> (B, K, J) float64 dB."""
+    B, K, J, n = _source_rows(references, estimates, "pairwise_si_sdr")
+    table = torch.empty((B, K, J), device=references.device, dtype=torch.float64)
+    _call_real("pairwise_si_sdr", references.dtype, _ptr(references, references.dtype, "references"),
+               _ptr(estimates, references.dtype, "estimates"), _ptr(table, torch.float64), B, K, J, n)
+    return table
+
+
+def assign(table, maximize):
+    """The best assignment of columns to rows (alvq_assign_f64): table (B, K, J) float64 on the GPU, K <= J -> (perm (B, K)
+    int32, total (B,) float64, status (B,) int32).  status is the kernel's per-item flag (include/alvq.h) and is not read
+    here."""
+    if table.dim() != 3 or table.dtype != torch.float64:
+        raise RuntimeError("assign: expected a float64 (B, K, J) table (got %s %s)" % (table.dtype, tuple(table.shape)))
+    B, K, J = table.shape
+    perm = torch.empty((B, K), device=table.device, dtype=torch.int32)
+    total = torch.empty((B,), device=table.device, dtype=torch.float64)
+    status = torch.empty((B,), device=table.device, dtype=torch.int32)
+    _check(lib().alvq_assign_f64(_ptr(table, torch.float64, "table"), _ptr(perm, torch.int32), _ptr(total, torch.float64),
+                                 _ptr(status, torch.int32), B, K, J, 1 if maximize else 0, _stream()), "alvq_assign_f64")
+    return perm, total, status
+
+
+def si_bss_eval(references, estimates, perm):
+    """Scale-invariant SDR, SIR and SAR (alvq_si_bss_eval_f32 / _f64): references (B, K, n), estimates (B, J, n) of one real
+    dtype and perm (B, K) int32 on the GPU -> (sdr, sir, sar (B, K) float64, status (B,) int32)."""
+    B, K, J, n = _source_rows(references, estimates, "si_bss_eval")
+    if perm.dtype != torch.int32 or tuple(perm.shape) != (B, K):
+        raise RuntimeError("si_bss_eval: expected an int32 (%d, %d) perm (got %s %s)" % (B, K, perm.dtype, tuple(perm.shape)))
+    dev = references.device
+    sdr, sir, sar = (torch.empty((B, K), device=dev, dtype=torch.float64) for _ in range(3))
+    status = torch.empty((B,), device=dev, dtype=torch.int32)
+    _call_real("si_bss_eval", references.dtype, _ptr(references, references.dtype, "references"),
+               _ptr(estimates, references.dtype, "estimates"), _ptr(perm, torch.int32, "perm"), _ptr(sdr, torch.float64),
+               _ptr(sir, torch.float64), _ptr(sar, torch.float64), _ptr(status, torch.int32), B, K, J, n)
+    return sdr, sir, sar, status
 
 
 # ----------------------------------------------------------------------------------------------- t-SNE

@@ -53,6 +53,15 @@ and gives every source a rank-``bases`` non-negative model of its variance over 
 
 A random start at few bins can lock the sources of different bins in different orders -- this is known of ILRMA -- which is what
 ``w0`` is for.  Its definitions are ``ilrma``'s docstring and, in full, include/alvq.h.
+
+All three return their sources in an order nobody chose.  ``speech_metrics`` scores the outputs against the clean talkers on
+the device (csrc/separation_metrics.hip) and says which is which; ``reorder`` applies that:
+
+    from acoustic_locating_vq_vae import speech_metrics as SM
+    waves = FE.istft(sep.spec.reshape(B * D, F, T), length=S).view(B, D, S)
+    pit = SM.pit_si_sdr(clean, waves)                             # PIT(value (B, K) dB, perm (B, K), status (B,))
+    SEP.reorder(sep.spec, SM.pit_si_sdr(clean, waves).perm)       # (B, K, F, T): output perm[b, k] is talker k
+    SM.si_bss_eval(clean, waves)                                  # sir: crosstalk left (demixing); sar: artefacts (masking)
 """
 import collections
 
@@ -183,6 +192,27 @@ def masks(sep_spec):
     _on_gpu(who, y, "sep_spec")
     m = N.separation_masks(y)
     return m if batched else m[0]
+
+
+def reorder(x, perm):
+    """The sources of x in the order perm gives: x (B, J, ...) with perm (B, K), or x (J, ...) with perm (K,), on the GPU --
+    spectrograms, waveforms or masks, any dtype; perm int32 or int64 as ``speech_metrics.pit_si_sdr`` and ``assign`` return
+    it -> (B, K, ...), out[b, k] = x[b, perm[b, k]], by torch indexing on the device.  The entries of perm must lie in
+    0..J-1 (``assign``'s always do); they are not read here."""
+    who = "reorder"
+    if not isinstance(perm, torch.Tensor) or perm.dtype not in (torch.int32, torch.int64) or perm.dim() not in (1, 2):
+        raise ValueError("%s: perm must be an int32 or int64 (K,) or (B, K) tensor" % who)
+    batched = perm.dim() == 2
+    if not isinstance(x, torch.Tensor) or x.dim() < perm.dim():
+        raise ValueError("%s: x must be a tensor of at least %d dimensions for a perm of %d" % (who, perm.dim(), perm.dim()))
+    if perm.shape[-1] < 1 or x.shape[perm.dim() - 1] < 1 or (batched and (x.shape[0] != perm.shape[0] or x.shape[0] < 1)):
+        raise ValueError("%s: x %s and perm %s do not go together" % (who, tuple(x.shape), tuple(perm.shape)))
+    _on_gpu(who, x, "x")
+    _on_gpu(who, perm, "perm")
+    index = perm.long()
+    if not batched:
+        return x[index]
+    return x[torch.arange(x.shape[0], device=x.device)[:, None], index]
 
 
 def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, hop=HOP, method="auxiva", bases=2, generator=None):

@@ -26,6 +26,30 @@ values differ from theirs at about the third decimal (unmeasured here: neither i
 fewer than 30 frames kept (value NaN).  Nothing here reads it: the caller does, when it can sync.  STOI compares frame
 against frame, so the pair must be lined up: the dataset's 'same' convolution leaves the echoed signal (Nh - 1) // 2 samples
 ahead of the clean one.
+
+Separated sources come back in an order nobody chose (``separation.auxiva``, ``ilrma``, ``cacgmm``); the scores that say which
+output is which talker, and what is left in it, are here too (csrc/separation_metrics.hip), with the same guarantees and
+graph-capturable:
+
+    from acoustic_locating_vq_vae.speech_metrics import pairwise_si_sdr, assign, pit_si_sdr, si_bss_eval, si_sdr_improvement
+    pairwise_si_sdr(clean, waves)                # (B, K, J) dB: every estimate against every reference, si_sdr's bits
+    pit = pit_si_sdr(clean, waves)               # PIT(value (B, K), perm (B, K), status (B,)): the permutation-invariant SI-SDR
+    separation.reorder(sep.spec, pit.perm)       # the separated spectrograms in the talkers' order
+    si_bss_eval(clean, waves)                    # SIBSS(sdr, sir, sar, perm, status): crosstalk (sir) or artefacts (sar)?
+    si_sdr_improvement(clean, waves, mixture)    # (B, K) dB gained over the mixture
+    assign(table, maximize=False)                # ASSIGN(perm, total, status) of any (B, K, J) cost table, K <= J <= 8
+
+``pairwise_si_sdr``'s entry [b, i, j] is ``si_sdr(references[b, i], estimates[b, j])`` bit for bit.  ``assign`` searches all
+injections pi of the K rows into the J columns in lexicographic order of (pi(0), ..., pi(K-1)); the score of pi is
+table[0, pi(0)] + table[1, pi(1)] + ..., k rising; a NaN score is skipped, ties go to the first injection; status 1 where
+every score is NaN (perm the identity, total NaN).  ``si_bss_eval`` is the scale-invariant split of Le Roux, Wisdom, Erdogan and
+Hershey ("SDR -- half-baked or well done?", 2019): with s_p the item's centred references, e the centred estimate
+perm[b, i] selects, G = [<s_p, s_q>] and g = [<s_p, e>]: target = (g[i] / G[i, i]) s_i, proj = sum_p c_p s_p with G c = g
+(Gaussian elimination, partial pivoting), interf = proj - target, artif = e - proj; sdr = |target|^2 / |target - e|^2, sir =
+|target|^2 / |interf|^2, sar = |proj|^2 / |artif|^2 in dB, the energies summed sample by sample, +inf where a denominator is
+0.  Its status per item: 0; 1 = a reference of zero or non-finite centred energy or a non-finite sample in a selected estimate
+(sir, sar NaN); 2 = a pivot that is 0 or not finite, as two identical references give (sir, sar NaN); 3 = a perm row that is
+not an injection into 0..J-1 (all NaN; found on the device).  In full: include/alvq.h.
 """
 import collections
 import functools
@@ -164,3 +188,121 @@ def log_spectral_distance(p, q, eps=1e-10):
     _on_gpu("log_spectral_distance", ps, qs)
     out = N.lsd(ps.contiguous(), qs.contiguous(), float(eps))
     return out[0] if single else out
+
+
+# ------------------------------------------------------------------------------------------------------ separation scores
+ASSIGN = collections.namedtuple("ASSIGN", "perm total status")
+PIT = collections.namedtuple("PIT", "value perm status")
+SIBSS = collections.namedtuple("SIBSS", "sdr sir sar perm status")
+
+MAX_SOURCES = 8
+
+
+def _sources(references, estimates, who, square=False):
+    """references as contiguous (B, K, n) and estimates as (B, J, n), and whether they came without B.  square: K <= J is
+    required (every reference takes an estimate of its own).  The device is checked by the caller, last."""
+    for t, name in ((references, "references"), (estimates, "estimates")):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3):
+            raise ValueError("%s: %s must be a (sources, n) or (B, sources, n) tensor" % (who, name))
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: %s must be float32 or float64, got %s" % (who, name, t.dtype))
+    if references.dim() != estimates.dim() or references.dtype != estimates.dtype:
+        raise ValueError("%s: references %s %s and estimates %s %s differ in rank or dtype"
+                         % (who, references.dtype, tuple(references.shape), estimates.dtype, tuple(estimates.shape)))
+    single = references.dim() == 2
+    s, e = (references[None], estimates[None]) if single else (references, estimates)
+    (B, K, n), J = s.shape, e.shape[1]
+    if e.shape[0] != B or e.shape[2] != n:
+        raise ValueError("%s: references %s and estimates %s differ in B or n" % (who, tuple(references.shape), tuple(estimates.shape)))
+    if B < 1 or B > 65535 or K < 1 or K > MAX_SOURCES or J < 1 or J > MAX_SOURCES or n < 2 or n > 1 << 24:
+        raise ValueError("%s: need 1 <= B <= 65535, 1 <= K, J <= 8 and 2 <= n <= 2^24, got references %s and estimates %s"
+                         % (who, tuple(references.shape), tuple(estimates.shape)))
+    if square and K > J:
+        raise ValueError("%s: %d references need at least as many estimates, got %d" % (who, K, J))
+    return s.contiguous(), e.contiguous(), single
+
+
+def pairwise_si_sdr(references, estimates):
+    """The SI-SDR of every estimate against every reference: (B, K, n) and (B, J, n), or (K, n) and (J, n), float32 or float64
+    on the GPU, 1 <= K, J <= 8 -> (B, K, J) float64 dB ((K, J) without B).  Entry [b, i, j] has the bits of
+    ``si_sdr(references[b, i], estimates[b, j])``; the reference row is streamed once per pass for all J estimates."""
+    s, e, single = _sources(references, estimates, "pairwise_si_sdr")
+    _on_gpu("pairwise_si_sdr", s, e)
+    table = N.pairwise_si_sdr(s, e)
+    return table[0] if single else table
+
+
+def assign(table, maximize=True):
+    """The assignment of J columns to K <= J rows with the largest (``maximize=False``: smallest) sum of entries: table
+    (B, K, J) or (K, J), float64 on the GPU, J <= 8 -> ``ASSIGN(perm (B, K) int32, total (B,) float64, status (B,) int32)``,
+    without B for a (K, J) table.  Exhaustive and exact: the rule is the module's docstring."""
+    who = "assign"
+    if not isinstance(table, torch.Tensor) or table.dim() not in (2, 3):
+        raise ValueError("%s: table must be a (K, J) or (B, K, J) tensor" % who)
+    if table.dtype != torch.float64:
+        raise ValueError("%s: table must be float64, got %s" % (who, table.dtype))
+    if not isinstance(maximize, bool):
+        raise ValueError("%s: maximize must be True or False, got %r" % (who, maximize))
+    single = table.dim() == 2
+    t = table[None] if single else table
+    B, K, J = t.shape
+    if B < 1 or B > 65535 or K < 1 or K > J or J > MAX_SOURCES:
+        raise ValueError("%s: need 1 <= B <= 65535 and 1 <= K <= J <= 8, got shape %s" % (who, tuple(table.shape)))
+    _on_gpu(who, t)
+    out = ASSIGN(*N.assign(t.contiguous(), maximize))
+    return ASSIGN(*(v[0] for v in out)) if single else out
+
+
+def _pit(s, e):
+    table = N.pairwise_si_sdr(s, e)
+    perm, _, status = N.assign(table, True)
+    return table, PIT(torch.gather(table, 2, perm.long()[:, :, None])[:, :, 0], perm, status)
+
+
+def pit_si_sdr(references, estimates):
+    """The permutation-invariant SI-SDR: ``assign(pairwise_si_sdr(references, estimates))`` -> ``PIT(value (B, K) float64 dB,
+    perm (B, K) int32, status (B,) int32)``, value[b, k] = table[b, k, perm[b, k]] gathered on the device; K <= J, so K talkers
+    can be scored against, say, ``cacgmm``'s K + 1 classes.  Without B for (K, n) input."""
+    s, e, single = _sources(references, estimates, "pit_si_sdr", square=True)
+    _on_gpu("pit_si_sdr", s, e)
+    out = _pit(s, e)[1]
+    return PIT(*(v[0] for v in out)) if single else out
+
+
+def si_bss_eval(references, estimates, perm=None):
+    """Scale-invariant SDR, SIR and SAR of estimates[b, perm[b, i]] against references[b, i] among the item's K references:
+    shapes as ``pit_si_sdr``; perm None (``pit_si_sdr``'s) or int32 (B, K) on the GPU ((K,) without B) ->
+    ``SIBSS(sdr, sir, sar (B, K) float64 dB, perm (B, K) int32, status (B,) int32)``.  sdr[b, i] has the bits of
+    ``pairwise_si_sdr``'s [b, i, perm[b, i]]; a low sir says crosstalk was left, a low sar says the target was distorted.  The
+    definitions and the status values are the module's docstring."""
+    who = "si_bss_eval"
+    s, e, single = _sources(references, estimates, who, square=True)
+    if perm is not None:
+        want = tuple(s.shape[1:2]) if single else tuple(s.shape[:2])
+        if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or tuple(perm.shape) != want:
+            raise ValueError("%s: perm must be None or an int32 %s tensor for references %s" % (who, want, tuple(references.shape)))
+    _on_gpu(who, s, e)
+    if perm is None:
+        p = _pit(s, e)[1].perm
+    else:
+        _on_gpu(who, perm)
+        p = (perm[None] if single else perm).contiguous()
+    sdr, sir, sar, status = N.si_bss_eval(s, e, p)
+    out = SIBSS(sdr, sir, sar, p, status)
+    return SIBSS(*(v[0] for v in out)) if single else out
+
+
+def si_sdr_improvement(references, estimates, mixture):
+    """What a separator gained: ``pit_si_sdr(references, estimates).value[b, k]`` minus the SI-SDR of the mixture against
+    references[b, k] (``pairwise_si_sdr`` with the mixture as the one estimate).  mixture: (B, n), or (n,) for (K, n) sources,
+    of the sources' dtype -> (B, K) float64 dB."""
+    who = "si_sdr_improvement"
+    s, e, single = _sources(references, estimates, who, square=True)
+    if not isinstance(mixture, torch.Tensor) or mixture.dtype != s.dtype \
+            or tuple(mixture.shape) != ((s.shape[2],) if single else (s.shape[0], s.shape[2])):
+        raise ValueError("%s: mixture must be a %s %s tensor for references %s"
+                         % (who, s.dtype, (s.shape[2],) if single else (s.shape[0], s.shape[2]), tuple(references.shape)))
+    _on_gpu(who, s, e, mixture)
+    m = (mixture[None] if single else mixture)[:, None].contiguous()
+    gain = _pit(s, e)[1].value - N.pairwise_si_sdr(s, m)[:, :, 0]
+    return gain[0] if single else gain

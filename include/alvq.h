@@ -396,6 +396,55 @@ int alvq_lsd_f32(const float* p, const float* q, double* out, int B, int F, int 
 int alvq_lsd_f64(const double* p, const double* q, double* out, int B, int F, int T, double eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scores of separated sources (csrc/separation_metrics.hip): the SI-SDR of every (reference, estimate) pair, the best
+ * assignment of estimates to references, and the scale-invariant SDR / SIR / SAR split (Le Roux, Wisdom, Erdogan, Hershey,
+ * "SDR -- half-baked or well done?", ICASSP 2019).  references: device (B, K, n), estimates: device (B, J, n), n contiguous,
+ * float32 ("_f32") or float64 ("_f64"), every sample widened on load; 1 <= K, J <= 8, 2 <= n <= 2^24, 1 <= B <= 65535.
+ * Float64 arithmetic, every sum in a fixed order, no atomics, no workspace, one launch each.
+ *
+ * alvq_pairwise_si_sdr_*: table[b, i, j] (device (B, K, J) float64) = the SI-SDR of estimates[b, j] against references[b, i]
+ * as alvq_si_sdr_* defines it, with the bits alvq_si_sdr_* gives that pair.  One workgroup per (b, i) streams the reference
+ * row once per pass against all J estimates: three passes (means; <s, s> and <e_j, s>; the energies), each sum over the
+ * samples t = thread, thread + 256, ... per thread, then the butterfly over the wave and the waves in order. */
+int alvq_pairwise_si_sdr_f32(const float* references, const float* estimates, double* table, int B, int K, int J, int n,
+                             void* stream);
+int alvq_pairwise_si_sdr_f64(const double* references, const double* estimates, double* table, int B, int K, int J, int n,
+                             void* stream);
+
+/* The best assignment of J columns to K <= J rows of table (device (B, K, J) float64), by exhaustive search.  The injections
+ * pi of {0..K-1} into {0..J-1} are ranked in lexicographic order of (pi(0), ..., pi(K-1)); the score of pi is
+ * table[0, pi(0)] + table[1, pi(1)] + ..., k rising, starting from the first term; an injection whose score is NaN is
+ * skipped.  The winner has the largest score (maximize != 0) or the smallest (maximize == 0), the lowest rank among equal
+ * scores.  perm: device (B, K) int32 = pi; total: device (B,) float64 = its score; status: device (B,) int32 = 0, or 1 where
+ * every injection was skipped (perm = the identity, total = NaN).  One workgroup an item: its threads stride over the ranks
+ * (at most 8! = 40320), each keeps its best (score, rank), and an arg-reduction over (score, rank) under the same rule picks
+ * the winner, so the result does not depend on which thread saw which rank. */
+int alvq_assign_f64(const double* table, int* perm, double* total, int* status, int B, int K, int J, int maximize,
+                    void* stream);
+
+/* Scale-invariant SDR, SIR and SAR of estimates[b, perm[b, i]] against references[b, i]; perm: device (B, K) int32.  With
+ * s_p the references of the item less their means, e the chosen estimate less its mean, G[p, q] = <s_p, s_q> and
+ * g[p] = <s_p, e> (the sums in the order of alvq_pairwise_si_sdr_*, so G[i, i] and g[i] have the bits of its <s, s> and
+ * <e, s>):  a = g[i] / G[i, i];  c solves G c = g by Gaussian elimination with partial pivoting (column j = 0 .. K - 1: the
+ * pivot of the largest |.| among the rows r >= j, the lowest row winning ties; rows exchanged; row r > j loses
+ * l = G[r][j] / pivot times row j; back substitution j = K - 1 .. 0);  target = a s_i;  proj = sum_p c_p s_p, p rising from
+ * the first product;  interf = proj - target;  artif = e - proj.  The energies |target|^2, |target - e|^2, |interf|^2,
+ * |artif|^2 and |proj|^2 are summed sample by sample in a third pass.
+ *   sdr[b, i] = 10 log10(|target|^2 / |target - e|^2), with the bits of table[b, i, perm[b, i]] of alvq_pairwise_si_sdr_*;
+ *   sir[b, i] = 10 log10(|target|^2 / |interf|^2);   sar[b, i] = 10 log10(|proj|^2 / |artif|^2);
+ * +inf where the denominator is 0, NaN where either energy is NaN.  For K = 1, c and a are one quotient and sir = +inf.
+ * sdr, sir, sar: device (B, K) float64.  status: device (B,) int32, the same in every row of the item:
+ *   3  perm[b] is not an injection into 0..J-1 (checked on the device before any estimate is read): sdr, sir, sar NaN;
+ *   1  else, a G[p, p] that is 0 or not finite, or a non-finite sample in an estimate perm[b] selects: sir, sar NaN;
+ *   2  else, a pivot that is 0 or not finite (two identical references): sir, sar NaN;
+ *   0  otherwise.  Under 1 and 2 sdr is what alvq_pairwise_si_sdr_* gives.
+ * One workgroup per (b, i); each reads the item's K references and works out G and the item's status for itself. */
+int alvq_si_bss_eval_f32(const float* references, const float* estimates, const int* perm, double* sdr, double* sir,
+                         double* sar, int* status, int B, int K, int J, int n, void* stream);
+int alvq_si_bss_eval_f64(const double* references, const double* estimates, const int* perm, double* sdr, double* sir,
+                         double* sar, int* status, int B, int K, int J, int n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Weighted prediction error (WPE) dereverberation of complex spectrograms (csrc/wpe.hip; Nakatani, Yoshioka, Kinoshita,
  * Miyoshi, Juang 2010).  X, Y: device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128
  * ("_f64"); D microphones; X and Y must not overlap.  status: device (B, F) int32.  All arithmetic is float64 (a complex64
