@@ -32,7 +32,7 @@
 //   onehot_to_index_kernel (location.hip): three interleaved butterflies; as wave_sum / wave_or / wave_max calls the kernel
 //                   takes 15 VGPRs instead of 12, in every order of the calls.
 //   the arg-reductions that carry an index with their own tie rule (vq.hip's argmin kernels, relocate_kernel,
-//                   room_acoustics.hip, assign_kernel of separation_metrics.hip), the __shfl_down suffix scan of room_acoustics.hip, the ballot compaction of
+//                   room_acoustics.hip, pm_search of assign_search.h), the __shfl_down suffix scan of room_acoustics.hip, the ballot compaction of
 //                   stoi_mask_kernel, and everything in conv_tile.h / wgrad_*.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -9,9 +9,10 @@
 //                           reference row is read once per pass for all J estimates; 1 + J, 1 + J and 2 J running sums a
 //                           thread.  Each sum is si_sdr_kernel's own (the samples t = thread, thread + 256, ..., then
 //                           block_sum<kSequential, true>, three passes), so an entry has the bits si_sdr_kernel gives the pair.
-//   assign_kernel           a workgroup per item: the threads stride over the ranks of the injections, unrank each through the
-//                           factorial number system and keep their best (score, rank); an arg-reduction over (score, rank) with
-//                           the same rule (ties to the lowest rank) picks the winner, which thread 0 unranks once more.
+//   assign_kernel           a workgroup per item: pm_search (assign_search.h, shared with permutation_align.hip) -- the threads
+//                           stride over the ranks of the injections, unrank each through the factorial number system and keep
+//                           their best (score, rank); an arg-reduction over (score, rank) with the same rule (ties to the
+//                           lowest rank) picks the winner -- which thread 0 unranks once more.
 //   si_bss_eval_kernel      a workgroup per (item, reference i): pass 1, the means of the K references and of the chosen
 //                           estimate, and a count of the non-finite samples of the K estimates the item's perm row selects (so
 //                           that every workgroup of an item arrives at the same status); pass 2, the upper triangle of the Gram
@@ -21,6 +22,7 @@
 #include <cmath>
 
 #include "alvq_common.h"
+#include "assign_search.h"
 
 namespace alvq {
 
@@ -28,7 +30,6 @@ constexpr int PM_THREADS = 256;
 constexpr int PM_WAVES = PM_THREADS / kWave;
 constexpr int PM_MAX_N = 1 << 24;
 constexpr int PM_MAX_ITEMS = 65535;        // items ride on gridDim.y
-constexpr int PM_MAX_K = 8;
 
 constexpr int PM_BAD_INPUT = 1;            // a reference of zero or non-finite centred energy, or a non-finite estimate sample
 constexpr int PM_BAD_SOLVE = 2;            // a pivot that is 0 or not finite
@@ -108,76 +109,20 @@ __global__ __launch_bounds__(PM_THREADS) void pairwise_si_sdr_kernel(const T* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------- assignment
-struct PmBest {
-  double score;
-  int rank;                                // -1: nothing yet
-};
-
-// whether candidate (s, r) beats `best` under the rule: a valid one beats none; the larger (smaller) score; then the lower rank
-__device__ __forceinline__ bool pm_beats(double s, int r, const PmBest& best, bool maximize) {
-  if (r < 0) return false;
-  if (best.rank < 0) return true;
-  if (s != best.score) return maximize ? s > best.score : s < best.score;
-  return r < best.rank;
-}
-
-// the injection of rank `rank` in lexicographic order: position k takes the digit-th smallest column not yet taken, the digits
-// those of rank in the mixed radix (J, J - 1, ..., J - K + 1); weight[k] = (J - k - 1)(J - k - 2) ... (J - K + 1)
-__device__ __forceinline__ void pm_unrank(int rank, int K, int J, const int* weight, int* pi) {
-  unsigned taken = 0u;
-  for (int k = 0; k < K; ++k) {
-    int digit = rank / weight[k];
-    rank -= digit * weight[k];
-    int col = 0;
-    for (;; ++col) {                       // digit < J - k columns are free: col stays below J
-      if (taken & (1u << col)) continue;
-      if (digit == 0) break;
-      --digit;
-    }
-    taken |= 1u << col;
-    pi[k] = col;
-  }
-}
-
 __global__ __launch_bounds__(PM_THREADS) void assign_kernel(const double* __restrict__ table, int* __restrict__ perm,
                                                             double* __restrict__ total, int* __restrict__ status, int K, int J,
                                                             int maximize) {
   __shared__ double s_table[PM_MAX_K * PM_MAX_K], s_score[PM_WAVES];
   __shared__ int s_rank[PM_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
+  const int tid = threadIdx.x, b = blockIdx.x;
   const bool up = maximize != 0;
   if (tid < K * J) s_table[tid] = table[(long)b * K * J + tid];
   __syncthreads();
   int weight[PM_MAX_K];
-  int count = 1;
-  for (int k = K - 1; k >= 0; --k) {
-    weight[k] = count;
-    count *= J - k;
-  }
-
-  PmBest best = {0.0, -1};
-  int pi[PM_MAX_K];
-  for (int rank = tid; rank < count; rank += PM_THREADS) {
-    pm_unrank(rank, K, J, weight, pi);
-    double s = s_table[pi[0]];
-    for (int k = 1; k < K; ++k) s += s_table[k * J + pi[k]];
-    if (s != s) continue;
-    if (pm_beats(s, rank, best, up)) best = PmBest{s, rank};   // the ranks of a thread rise: an equal score never replaces
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double s = __shfl_xor(best.score, o, 64);
-    const int r = __shfl_xor(best.rank, o, 64);
-    if (pm_beats(s, r, best, up)) best = PmBest{s, r};
-  }
-  if (lane == 0) {
-    s_score[tid >> 6] = best.score;
-    s_rank[tid >> 6] = best.rank;
-  }
-  __syncthreads();
+  const int count = pm_weights(K, J, weight);
+  const PmBest best = pm_search<PM_THREADS>(s_table, K, J, up, weight, count, s_score, s_rank);   // assign_search.h
   if (tid != 0) return;
-  for (int w = 1; w < PM_WAVES; ++w)
-    if (pm_beats(s_score[w], s_rank[w], best, up)) best = PmBest{s_score[w], s_rank[w]};
+  int pi[PM_MAX_K];
   if (best.rank < 0) {
     for (int k = 0; k < K; ++k) perm[(long)b * K + k] = k;
     total[b] = NAN;

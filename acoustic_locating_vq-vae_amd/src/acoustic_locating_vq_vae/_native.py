@@ -166,6 +166,9 @@ _SIGNATURES = {
     "alvq_cacgmm_workspace_bytes": (_i64, [_i32] * 5),
     "alvq_cacgmm_f32": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_cacgmm_f64": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_align_workspace_bytes": (_i64, [_i32] * 4),
+    "alvq_align_permutations_f64": (_i32, [_c_void_p] * 7 + [_i32] * 5 + [_c_void_p]),
+    "alvq_permute_bins": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
     "alvq_tsne_code_sqdist_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
     "alvq_tsne_affinities_workspace_bytes": (_i64, [_i32]),
     "alvq_tsne_affinities_f32": (_i32, [_c_void_p] * 4 + [_i32, ctypes.c_double, _c_void_p]),
@@ -1345,6 +1348,49 @@ def cacgmm(spec4d, init, iterations, floor, quadratic0=None):
                _ptr(cov, torch.float64), _ptr(quadratic, torch.float64), _ptr(status, torch.int32), _ptr(ws, torch.uint8),
                B, D, K, F, T, int(iterations), float(floor))
     return masks, prior, torch.view_as_complex(cov), quadratic, status
+
+
+def align_permutations(profile, iterations, perm0=None):
+    """Frequency permutation alignment (alvq_align_permutations_f64): profile (B, K, F, T) float64 and perm0 None or (B, F, K)
+    int32 on the GPU -> (perm (B, F, K) int32, score (B, F) float64, changed (B,) int32, status (B, F) int32).  status is the
+    kernels' per-bin flag (include/alvq.h) and is not read here."""
+    if profile.dim() != 4 or profile.dtype != torch.float64:
+        raise RuntimeError("align_permutations: profile must be float64 (B, K, F, T) (got %s %s)" % (profile.dtype, tuple(profile.shape)))
+    B, K, F, T = profile.shape
+    if perm0 is not None and (perm0.dtype != torch.int32 or tuple(perm0.shape) != (B, F, K)):
+        raise RuntimeError("align_permutations: perm0 must be int32 %s (got %s %s)" % ((B, F, K), perm0.dtype, tuple(perm0.shape)))
+    nbytes = lib().alvq_align_workspace_bytes(B, K, F, T)
+    if nbytes < 0:
+        raise RuntimeError("align_permutations: bad dims (B=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, "
+                           "1 <= K <= 8, 2 <= T <= 65535)" % (B, K, F, T))
+    dev = profile.device
+    p, p0 = profile.contiguous(), None if perm0 is None else perm0.contiguous()
+    perm = torch.empty((B, F, K), device=dev, dtype=torch.int32)
+    score = torch.empty((B, F), device=dev, dtype=torch.float64)
+    changed = torch.empty((B,), device=dev, dtype=torch.int32)
+    status = torch.empty((B, F), device=dev, dtype=torch.int32)
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    _check(lib().alvq_align_permutations_f64(_ptr(p, torch.float64, "profile"), _ptr(p0, torch.int32, "perm0"),
+                                             _ptr(perm, torch.int32), _ptr(score, torch.float64), _ptr(changed, torch.int32),
+                                             _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, K, F, T, int(iterations),
+                                             _stream()), "alvq_align_permutations_f64")
+    return perm, score, changed, status
+
+
+def permute_bins(x, perm):
+    """out[b, k, f, t] = x[b, perm[b, f, k], f, t] (alvq_permute_bins): x (B, K, F, T) float32, float64, complex64 or complex128
+    and perm (B, F, K) int32 on the GPU -> a new tensor of x's shape and dtype."""
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+        raise RuntimeError("permute_bins: x must be a real or complex (B, K, F, T) tensor of 4, 8 or 16 byte elements (got %s %s)"
+                           % (x.dtype, tuple(x.shape)))
+    B, K, F, T = x.shape
+    if perm.dtype != torch.int32 or tuple(perm.shape) != (B, F, K):
+        raise RuntimeError("permute_bins: perm must be int32 %s (got %s %s)" % ((B, F, K), perm.dtype, tuple(perm.shape)))
+    xc, pc = x.resolve_conj().contiguous(), perm.contiguous()
+    out = torch.empty_like(xc)
+    _check(lib().alvq_permute_bins(_ptr(xc, x.dtype, "x"), _ptr(pc, torch.int32, "perm"), _ptr(out, x.dtype), B, K, F, T,
+                                   x.element_size(), _stream()), "alvq_permute_bins")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- subspace methods

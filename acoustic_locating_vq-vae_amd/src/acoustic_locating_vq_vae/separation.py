@@ -62,6 +62,21 @@ the device (csrc/separation_metrics.hip) and says which is which; ``reorder`` ap
     pit = SM.pit_si_sdr(clean, waves)                             # PIT(value (B, K) dB, perm (B, K), status (B,))
     SEP.reorder(sep.spec, SM.pit_si_sdr(clean, waves).perm)       # (B, K, F, T): output perm[b, k] is talker k
     SM.si_bss_eval(clean, waves)                                  # sir: crosstalk left (demixing); sar: artefacts (masking)
+
+That is ONE order per item.  A separation that is right inside every bin but orders its sources differently from bin to bin --
+what any estimator that works per bin gives, a learned one included -- is repaired by ``align_permutations``
+(csrc/permutation_align.hip): Sawada's correlation of the classes' time profiles against per-source centroids.  ``permute_bins``
+applies its result to (B, K, F, T) arrays, ``permute_rows`` to the small per-bin ones (w, cov):
+
+    r = SEP.cacgmm(spec, init_drawn_per_bin, 10)
+    a = SEP.align_permutations(r.masks)                           # ALIGN(perm (B, F, K), score (B, F), changed (B,), status (B, F))
+    SEP.cacgmm(spec, SEP.permute_bins(r.masks, a.perm), 10, quadratic0=SEP.permute_bins(r.quadratic, a.perm))
+
+    a = SEP.align_permutations(SEP.masks(r.spec))                 # r: an auxiva / ilrma result whose bins disagree
+    SEP.permute_bins(r.spec, a.perm)                              # then istft, pit_si_sdr
+    SEP.auxiva(spec, 10, w0=SEP.permute_rows(r.w, a.perm))        # ... or go on from the aligned demixing matrices
+
+Its definitions are ``align_permutations``' docstring and, in full, include/alvq.h.
 """
 import collections
 
@@ -76,6 +91,7 @@ from .localization import _int_in, _on_gpu, _positive
 IVA = collections.namedtuple("IVA", "spec w status")
 ILRMA = collections.namedtuple("ILRMA", "spec w basis activations status")
 CACGMM = collections.namedtuple("CACGMM", "masks prior cov quadratic status")
+ALIGN = collections.namedtuple("ALIGN", "perm score changed status")
 
 MAX_ITERATIONS = 256
 MODELS = {"laplace": N.IVA_LAPLACE, "gauss": N.IVA_GAUSS}
@@ -282,8 +298,9 @@ def cacgmm(spec, init, iterations=20, quadratic0=None, floor=1e-10):
     and class B_k = D sum_t (gamma / q) z z^H / sum_t gamma (I for a class without weight), eigendecomposed; lambda_i <-
     max(lambda_i, floor lambda_max), then scaled to sum to D; a failure gives status 2.  (3) per frame
     q_k = sum_i |v_i^H z|^2 / lambda_i, l_k = log prior - log det B_k - D log q_k, gamma = softmax_k l_k.  There is no frequency
-    permutation alignment: the priors shared over frequency stand in for it, which is why the init should be constant over
-    frequency.  Nothing here reads a status: the caller does, when it can sync."""
+    permutation alignment inside: the priors shared over frequency stand in for it, which is why the init should be constant
+    over frequency; masks whose classes have come out in a different order in every bin are repaired by
+    ``align_permutations``.  Nothing here reads a status: the caller does, when it can sync."""
     who = "cacgmm"
     x, batched = _spec4(who, spec)
     B, D, F, T = x.shape
@@ -312,3 +329,87 @@ def time_masks(B, K, F, T, generator=None, device="cuda"):
         _int_in(who, name, v, 1, hi)
     m = torch.rand((B, K, 1, T), dtype=torch.float64, generator=generator, device=device) + 1e-3
     return (m / m.sum(dim=1, keepdim=True)).expand(B, K, F, T).contiguous()
+
+
+def _bin_perm(who, name, perm, B, K, F, batched):
+    """perm as int32 (B, F, K) for an array of (B, K, F, ...): (F, K) without the batch."""
+    want = (B, F, K) if batched else (F, K)
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or tuple(perm.shape) != want:
+        raise ValueError("%s: %s must be an int32 %s tensor" % (who, name, want))
+    return perm if batched else perm[None]
+
+
+def _class_rows(who, x, dtypes, what):
+    """x as (B, K, F, T), checked against the kernels' limits; whether it came with a batch dimension."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (3, 4) or x.dtype not in dtypes:
+        raise ValueError("%s: %s must be a (K, F, T) or (B, K, F, T) tensor of %s" % (who, what, " or ".join(str(d) for d in dtypes)))
+    y = x if x.dim() == 4 else x[None]
+    B, K, F, T = y.shape
+    if B < 1 or B > 65535 or K < 1 or K > MAX_CLASSES or F < 1 or B * F > 2 ** 31 - 1 or T < 1 or T > MAX_FRAMES:
+        raise ValueError("%s: need 1 <= B <= 65535, 1 <= K <= 8, F >= 1, B F <= 2^31 - 1 and 1 <= T <= 65535, got shape %s"
+                         % (who, tuple(x.shape)))
+    return y, x.dim() == 4
+
+
+def align_permutations(profile, iterations=10, perm0=None):
+    """Frequency permutation alignment (Sawada, Araki, Makino, IEEE TASLP 2011, the global stage; csrc/permutation_align.hip):
+    profile (K, F, T) or (B, K, F, T) float64 on the GPU, the time profile of class j of bin f -- ``cacgmm``'s masks, ``masks`` of
+    a separation, powers, log-powers: any finite reals, 1 <= K <= 8, 2 <= T <= 65535 -- and perm0 None (the identity) or an
+    int32 (F, K) / (B, F, K) start -> ``ALIGN(perm (B, F, K) int32, score (B, F) float64, changed (B,) int32, status (B, F)
+    int32)``, without B for a (K, F, T) profile (changed is then a scalar tensor).  perm[b, f, k] is the class of bin f that is
+    source k: ``permute_bins(x, perm)`` and ``permute_rows(a, perm)`` apply it.  changed counts the bins that the LAST iteration
+    moved: 0 at a fixed point.  ``align_permutations(P, a + b)`` equals ``align_permutations(P, b, perm0 = align_permutations(P,
+    a).perm)`` bit for bit.
+
+    Definitions (in full: include/alvq.h).  A bin with a non-finite value, or whose perm0 row is not a permutation of 0..K-1,
+    gets status 1, perm = the identity and score = NaN, and stays out of every centroid.  Every row (b, j, f) is centred and
+    scaled to unit length over t, u = (P - m) / |P - m|, a constant row to 0.  One iteration (Jacobi: all bins are scored
+    against the same centroids): (1) c[b, k, t] = sum_f u[perm[b, f, k], f, t], f rising, scaled to unit length over t;
+    (2) per bin table[k, j] = sum_t c[k, t] u[j, f, t], and the new perm[b, f, :] is the permutation of the largest total by
+    ``speech_metrics.assign``'s exhaustive rule, score its total.  Nothing here reads a status: the caller does, when it can
+    sync."""
+    who = "align_permutations"
+    p, batched = _class_rows(who, profile, (torch.float64,), "profile")
+    B, K, F, T = p.shape
+    if T < 2:
+        raise ValueError("%s: need T >= 2 frames, got T = %d" % (who, T))
+    _int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
+    p0 = None if perm0 is None else _bin_perm(who, "perm0", perm0, B, K, F, batched)
+    _on_gpu(who, p, "profile")
+    if p0 is not None:
+        _on_gpu(who, p0, "perm0")
+    out = ALIGN(*N.align_permutations(p, int(iterations), p0))
+    return out if batched else ALIGN(*(t[0] for t in out))
+
+
+def permute_bins(x, perm):
+    """The classes of every bin of x in the order perm gives (csrc/permutation_align.hip): x (K, F, T) or (B, K, F, T), float32,
+    float64, complex64 or complex128 on the GPU -- masks, quadratic, separated spectrograms -- and perm int32 (F, K) / (B, F, K)
+    as ``align_permutations`` returns it -> a new tensor of x's shape and dtype, out[b, k, f, t] = x[b, perm[b, f, k], f, t].  A
+    bin of perm with an entry outside 0..K-1 passes through unpermuted."""
+    who = "permute_bins"
+    y, batched = _class_rows(who, x, (torch.float32, torch.float64, torch.complex64, torch.complex128), "x")
+    B, K, F, _ = y.shape
+    p = _bin_perm(who, "perm", perm, B, K, F, batched)
+    _on_gpu(who, y, "x")
+    _on_gpu(who, p, "perm")
+    out = N.permute_bins(y, p)
+    return out if batched else out[0]
+
+
+def permute_rows(a, perm):
+    """The rows of the small per-bin arrays in the order perm gives: a (F, K, ...) or (B, F, K, ...) of any dtype on the GPU --
+    ``auxiva``'s and ``ilrma``'s w, whose row k extracts source k, ``cacgmm``'s cov -- and perm int32 (F, K) / (B, F, K) ->
+    out[b, f, k] = a[b, f, perm[b, f, k]], by torch indexing on the device (these arrays are small).  The entries of perm must
+    lie in 0..K-1 (``align_permutations``' always do); they are not read here.  ILRMA's basis and activations cannot be permuted
+    per bin, because an activation is shared by all bins of a source: after aligning an ILRMA result go on with
+    ``auxiva(spec, n, w0=permute_rows(r.w, perm))``, or restart ``ilrma`` from ``nmf_init`` with that w0."""
+    who = "permute_rows"
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or perm.dim() not in (2, 3):
+        raise ValueError("%s: perm must be an int32 (F, K) or (B, F, K) tensor" % who)
+    if not isinstance(a, torch.Tensor) or a.dim() < perm.dim() or tuple(a.shape[:perm.dim()]) != tuple(perm.shape) or perm.numel() < 1:
+        raise ValueError("%s: a must be a tensor of shape %s + (...) for this perm" % (who, tuple(perm.shape)))
+    _on_gpu(who, a, "a")
+    _on_gpu(who, perm, "perm")
+    index = perm.long().reshape(tuple(perm.shape) + (1,) * (a.dim() - perm.dim())).expand(a.shape)
+    return torch.gather(a, perm.dim() - 1, index)

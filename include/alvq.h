@@ -778,7 +778,8 @@ int alvq_ilrma_f64(const double* X, const double* W0, const double* basis0, cons
  * talkers and diffuse noise alike -- from D microphones, K and D independent: what the mask-driven beamformers take where AuxIVA
  * (K = D, no noise class) does not apply.  All arithmetic is float64 (a complex64 value is widened first).  No atomics, no host
  * sync, graph-capturable; every sum runs in one order that depends on sizes alone: an item has the same bits alone, in any batch
- * and on any run.  There is no frequency permutation alignment: the priors are shared over frequency and stand in for it.
+ * and on any run.  There is no frequency permutation alignment inside: the priors are shared over frequency and stand in for it
+ * (alvq_align_permutations_f64 below repairs masks whose classes come out in a different order in every bin).
  * Limits: 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 2 <= D <= 8; 1 <= K <= 8; 1 <= T <= 65535; 1 <= iterations <= 256;
  * 0 <= floor <= 1.
  *   X          device (B, D, F, T) interleaved complex, T contiguous, complex64 ("_f32") or complex128 ("_f64").
@@ -835,6 +836,57 @@ int alvq_cacgmm_f32(const float* X, const double* init, const double* quadratic0
 int alvq_cacgmm_f64(const double* X, const double* init, const double* quadratic0, double* masks, double* prior, double* cov,
                     double* quadratic, int* status, void* workspace, int B, int D, int K, int F, int T, int iterations,
                     double floor, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frequency permutation alignment of a per-bin separation (csrc/permutation_align.hip): the first, global stage of Sawada,
+ * Araki, Makino, "Underdetermined convolutive blind source separation via frequency bin-wise clustering and permutation
+ * alignment" (IEEE TASLP 2011).  A separation that is right inside every bin but orders its sources differently from bin to bin
+ * is repaired by the observation that source k has the same on/off pattern over time in every bin: the time profiles of the
+ * classes of each bin are correlated against per-source centroids, each bin takes the permutation that correlates best, and the
+ * centroids are rebuilt.  All arithmetic is float64.  No floating-point atomics, no host sync, graph-capturable; every sum runs
+ * in one order that depends on sizes alone: an item has the same bits alone, in any batch, on any run and in any replay.
+ * Limits: 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1; 1 <= K <= 8; 2 <= T <= 65535; 1 <= iterations <= 256.
+ *   profile  device (B, K, F, T) float64, T contiguous: P[b, j, f, t], the time profile of class j of bin f -- masks, powers,
+ *            log-powers: any finite reals.
+ *   perm0    device (B, F, K) int32 or NULL: the start; NULL: the identity.  It must not overlap perm.
+ *   perm     device (B, F, K) int32: perm[b, f, k] = the class of bin f that is source k.  The only state.
+ *   score    device (B, F) float64: the winner's total in the last iteration.
+ *   changed  device (B,) int32: the number of bins of status 0 whose perm differs before and after the LAST iteration; 0 at a
+ *            fixed point.  status: device (B, F) int32.
+ *
+ * Status.  A bin (b, f) with a value of P[b, :, f, :] that is not finite, or whose perm0[b, f, :] is not a permutation of
+ * 0..K-1, gets status 1: perm = the identity, score = NaN; it stays out of every centroid and is never updated.  Every other
+ * bin has status 0.
+ * Rows.  For every row (b, j, f) of a bin of status 0: m = (sum_t P) / T;  v = sum_t (P - m)^2, each term a rounded difference
+ * squared;  rn = 1 / sqrt(v) where v > 0 and finite, else 0 (a constant row carries no evidence);
+ * u[j, f, t] = (P - m) rn, a rounded difference times rn.  u is never stored: (m, rn) is, 16 bytes a row.
+ * One iteration (Jacobi: every bin is scored against the same centroids, so the order in which bins are visited is immaterial):
+ *   1. c[b, k, t] = sum_f u[perm[b, f, k], f, t] over the item's bins of status 0, f rising, the sum starting from the first
+ *      term; 0 for an item without one.
+ *   2. n_k = sqrt(sum_t c^2);  c <- c / n_k where n_k > 0 and finite, else c <- 0.
+ *   3. Per bin of status 0: table[k, j] = sum_t c[k, t] u[j, f, t], each term a rounded product.  The new perm[b, f, :] is the
+ *      winner of alvq_assign_f64's rule on that K x K table with maximize != 0 (lexicographic rank, NaN scores skipped, the
+ *      lowest rank among equal scores) and score[b, f] its total.  If every permutation was skipped the old perm stays, the
+ *      score is NaN and the bin counts as unchanged.
+ * perm is the only state, so a + b iterations give the perm, score and changed of b iterations started from the perm of a.
+ * Nothing reads a status on the host.
+ *
+ * Sum orders.  Every sum over t -- of the rows, of c^2 and of the table -- is the same: thread i of a workgroup of 256 adds the
+ * frames t = i, i + 256, ... rising from +0.0, then block_sum<kSequential, true> of csrc/block_reduce.h (wave_sum's butterfly,
+ * the four waves in order from the first): an order that depends on T alone.  The sum over f: a thread owns a frame and walks f
+ * rising, exactly as written above.
+ * 1 + 3 iterations + 1 launches on the stream (status, row statistics and start; centroids, their norms, scores; changed).
+ * workspace: device, alvq_align_workspace_bytes(B, K, F, T) = 16 B K F + 8 B K T + 4 B F bytes ((m, rn) of every row, the
+ * centroids, a changed flag a bin); -1 for sizes out of range. */
+int64_t alvq_align_workspace_bytes(int B, int K, int F, int T);
+int alvq_align_permutations_f64(const double* profile, const int* perm0, int* perm, double* score, int* changed, int* status,
+                                void* workspace, int B, int K, int F, int T, int iterations, void* stream);
+
+/* out[b, k, f, t] = x[b, perm[b, f, k], f, t] for x and out device (B, K, F, T), T contiguous, of elements of elem_bytes = 4, 8
+ * or 16 bytes (float32; float64 / complex64; complex128), and perm device (B, F, K) int32 as alvq_align_permutations_f64 gives
+ * it: a pure copy, coalesced over t, in units of the widest of 16, 8 and 4 bytes that divides a row.  An entry of perm outside
+ * 0..K-1 is not read as an index: such a bin passes through unpermuted.  out must not overlap x.  Limits as above, T >= 1. */
+int alvq_permute_bins(const void* x, const int* perm, void* out, int B, int K, int F, int T, int elem_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Exact t-SNE (sklearn.manifold.TSNE(method="exact", n_components=2) semantics; the contract in full: the docstring of
