@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import beamform_ref as R  # noqa: E402
 import srp_ref  # noqa: E402
+from parity_checks import check_cov  # noqa: E402
 from acoustic_locating_vq_vae import _native as N  # noqa: E402
 from acoustic_locating_vq_vae import beamforming as BF  # noqa: E402
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
@@ -51,17 +52,6 @@ def same_bits(a, b):
 
 def mask_of(c, kind):
     return None if kind == "ones" else dev(c.masks[kind])         # "ones": the null mask, which the restatement takes as 1
-
-
-def check_cov(got, ref_cov, scale, T, tag, skip=()):
-    err = np.abs(host(got) - ref_cov)
-    bound = 2 * R.cov_bound(T, scale)
-    keep = np.ones(err.shape[:2], bool)
-    for b, f in skip:
-        keep[b, f] = False
-    ratio = (err[keep] / bound[keep]).max()
-    print("%s: largest |Phi - Phi_ref| / bound %.3g" % (tag, ratio))
-    assert (err[keep] <= bound[keep]).all(), (tag, ratio)
 
 
 def hermitian_bits(cov):

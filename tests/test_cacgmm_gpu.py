@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import cacgmm_ref as R  # noqa: E402
+from parity_checks import check_gmm as check  # noqa: E402
 from acoustic_locating_vq_vae import beamforming as BF  # noqa: E402
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
 from acoustic_locating_vq_vae import separation as SEP  # noqa: E402
@@ -67,16 +68,6 @@ def device_run(shape, cdtype):
     assert out.quadratic.shape == (B, K, F, T) and out.quadratic.dtype == torch.float64
     assert out.status.shape == (B, F) and out.status.dtype == torch.int32
     return tuple(host(t) for t in out)
-
-
-def check(tag, got, ref, tol):
-    """masks, prior and quadratic of a device run against the restatement's."""
-    assert tol <= R.TOL_CAP, (tag, tol)                   # a condition on the case, not a measurement
-    qmax = ref.quadratic.max()
-    errs = (np.abs(got[0] - ref.masks).max(), np.abs(got[1] - ref.prior).max(), np.abs(got[3] - ref.quadratic).max() / qmax)
-    print("%s: |masks - ref| %.3g, |prior - ref| %.3g, |q - ref| / max q %.3g, tol %.3g, measured / tol %.3g"
-          % ((tag,) + errs + (tol, max(errs) / tol)))
-    assert max(errs) <= tol, (tag, errs, tol)
 
 
 # ------------------------------------------------------------------------------------------------------------------ parity

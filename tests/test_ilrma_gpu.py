@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import iva_ref as IR  # noqa: E402
 import ilrma_ref as R  # noqa: E402
+from parity_checks import check_three  # noqa: E402
 from acoustic_locating_vq_vae import beamforming as BF  # noqa: E402
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
 from acoustic_locating_vq_vae import separation as SEP  # noqa: E402
@@ -31,7 +32,6 @@ from acoustic_locating_vq_vae import separation as SEP  # noqa: E402
 U = R.U
 CDTYPES = [np.complex128, np.complex64]
 CIDS = ["complex128", "complex64"]
-NAMES = ("W", "basis", "activations")
 
 
 def dev(a):
@@ -70,19 +70,6 @@ def device_run(shape, cdtype):
     assert out.basis.dtype == out.activations.dtype == torch.float64
     assert out.status.shape == (B, F) and out.status.dtype == torch.int32
     return host(out.w), host(out.basis), host(out.activations), host(out.spec), host(out.status)
-
-
-def check_three(tag, got, want, tol, demand=True):
-    """max |dev - ref| <= tol max |ref| for each of W, basis and activations."""
-    if demand:
-        assert tol <= 1e-10, (tag, tol)                   # a condition on the case, not a measurement
-    worst = []
-    for name, g, w in zip(NAMES, got, want):
-        err = np.abs(g - w).max() / np.abs(w).max()
-        print("%s: |%s - ref| / max |ref| %.3g, tol %.3g, measured / tol %.3g" % (tag, name, err, tol, err / tol))
-        worst.append((name, err))
-    for name, err in worst:
-        assert err <= tol, (tag, name, err, tol)
 
 
 # ------------------------------------------------------------------------------------------------------------------ parity

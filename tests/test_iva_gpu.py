@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import iva_ref as R  # noqa: E402
+from parity_checks import check_w  # noqa: E402
 from acoustic_locating_vq_vae import beamforming as BF  # noqa: E402
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
 from acoustic_locating_vq_vae import separation as SEP  # noqa: E402
@@ -63,13 +64,6 @@ def device_run(shape, model, cdtype):
     assert out.w.shape == (B, F, D, D) and out.w.dtype == torch.complex128
     assert out.status.shape == (B, F) and out.status.dtype == torch.int32
     return host(out.w), host(out.spec), host(out.status)
-
-
-def check_w(tag, W, ref_W, tol):
-    assert tol <= 1e-10, (tag, tol)                       # a condition on the case, not a measurement
-    err = np.abs(W - ref_W).max() / np.abs(ref_W).max()
-    print("%s: |W - W_ref| / max |W_ref| %.3g, tol %.3g, measured / tol %.3g" % (tag, err, tol, err / tol))
-    assert err <= tol, (tag, err, tol)
 
 
 # ------------------------------------------------------------------------------------------------------------------ parity

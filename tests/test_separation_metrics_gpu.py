@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import iva_ref as IR  # noqa: E402
 import ilrma_ref as LR  # noqa: E402
+import parity_checks  # noqa: E402
 import separation_metrics_ref as R  # noqa: E402
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
 from acoustic_locating_vq_vae import separation as SEP  # noqa: E402
@@ -99,14 +100,10 @@ def test_pairwise_has_the_bits_of_si_sdr(shape, dtype):
 # ------------------------------------------------------------------------------------------------------------ the assignment
 def check_assign(table, maximize):
     got = SM.assign(dev(table), maximize=maximize)
-    want = R.assign(table, maximize)
     B, K, _ = table.shape
     assert got.perm.shape == (B, K) and got.perm.dtype == torch.int32 and got.status.dtype == torch.int32
     assert got.total.shape == (B,) and got.total.dtype == torch.float64 and got.status.shape == (B,)
-    assert np.array_equal(host(got.perm), want.perm), (table, host(got.perm), want.perm)
-    assert np.array_equal(host(got.status), want.status)
-    assert same_doubles(host(got.total), want.total)
-    return want
+    return parity_checks.check_assign("assign", (host(got.perm), host(got.total), host(got.status)), table, maximize)
 
 
 @pytest.mark.parametrize("maximize", [True, False], ids=["max", "min"])
