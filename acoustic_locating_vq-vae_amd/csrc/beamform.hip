@@ -34,7 +34,7 @@
 //                    adds conj(w_d) x_d[t] with d rising, starting from the first product.  A weight of exactly 0 is passed
 //                    over and a weight with an imaginary part of exactly 0 multiplies as a real number, so that w = e_ref
 //                    returns x_ref bit for bit whatever the bin holds, a NaN included.
-// Every grid is capped at BF_MAX_BLOCKS workgroups and strides over the bins (or outputs) beyond, whole waves or whole
+// Every grid is capped at kMaxBlocks workgroups and strides over the bins (or outputs) beyond, whole waves or whole
 // workgroups at a time.  No atomics anywhere; a bin shares nothing with its neighbours: it has the same bits alone, in any
 // batch and on any run.
 // What the launches cost: DESIGN.md.
@@ -42,17 +42,14 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 #include "herm_eig.h"
 
 namespace alvq {
 
 constexpr int BF_THREADS = 256;
 constexpr int BF_WAVES = BF_THREADS / kWave;
-constexpr int BF_MAX_D = 8;
-constexpr int BF_MAX_T = 65535;
 constexpr int BF_WAVE_T = 1024;        // rows up to this long are summed by one wave, longer ones by the workgroup
-constexpr long BF_MAX_BLOCKS = 1 << 16;   // every grid is capped here (2^24 threads, far more than the chip holds) and strides
 
 // status values of alvq_spatial_covariance_* and alvq_beamform_weights_f64, and the bit of alvq_steering_vectors_f64
 constexpr int BF_BAD_INPUT = 1;        // a non-finite X, a negative or non-finite mask value, or a mask that sums to 0
@@ -60,25 +57,6 @@ constexpr int BF_BAD_SOLVE = 2;        // a Cholesky pivot or the denominator <=
 constexpr int BF_BAD_GEOMETRY = 4;     // a non-finite coordinate (srp_phat's bit)
 
 constexpr int BF_DAS = 0, BF_MVDR = 1, BF_SOUDEN = 2;
-
-template <typename R> struct BfCplx;
-template <> struct BfCplx<float> { typedef float2 type; };
-template <> struct BfCplx<double> { typedef double2 type; };
-
-__device__ __forceinline__ bool bf_finite(double v) { return fabs(v) <= DBL_MAX; }
-
-__device__ __forceinline__ double2 bf_mul(double2 a, double2 b) {            // a b
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 bf_mul_conj(double2 a, double2 b) {       // a conj(b); imaginary part exactly 0 for a == b
-  return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
-}
-__device__ __forceinline__ double2 bf_conj_mul(double2 a, double2 b) {       // conj(a) b
-  return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
-}
-__device__ __forceinline__ double2 bf_shfl(double2 v, int src) {
-  return make_double2(__shfl(v.x, src, 64), __shfl(v.y, src, 64));
-}
 
 // ------------------------------------------------------------------------------------------------------- spatial covariance
 struct BfCovArgs {
@@ -92,7 +70,7 @@ struct BfCovArgs {
 
 template <typename R, int D, int W>
 __global__ __launch_bounds__(BF_THREADS, 2) void bf_cov_kernel(BfCovArgs a) {   // two waves a SIMD: 256 registers
-  typedef typename BfCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   constexpr int K = D * D + 1;                       // D real diagonal sums, D (D - 1) / 2 complex ones below it, the mask's sum
   __shared__ double red[W == 1 ? 1 : K][BF_WAVES];
   __shared__ int s_flag[BF_WAVES];
@@ -120,7 +98,7 @@ __global__ __launch_bounds__(BF_THREADS, 2) void bf_cov_kernel(BfCovArgs a) {   
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       x[d] = make_double2((double)v[d].x, (double)v[d].y);
-      if (!bf_finite(x[d].x) || !bf_finite(x[d].y)) bad = 1;
+      if (!is_finite(x[d].x) || !is_finite(x[d].y)) bad = 1;
     }
     int k = 0;
 #pragma unroll
@@ -200,9 +178,9 @@ __global__ __launch_bounds__(BF_THREADS) void bf_steer_kernel(const double* mics
   const double* q = src + 3L * b;
   int bad = 0;                                       // the same in every thread
   for (int e = 0; e < 3 * D; ++e)
-    if (!bf_finite(m[e])) bad = 1;
+    if (!is_finite(m[e])) bad = 1;
   const double qx = q[0], qy = q[1], qz = q[2];
-  if (!bf_finite(qx) || !bf_finite(qy) || !bf_finite(qz)) bad = 1;
+  if (!is_finite(qx) || !is_finite(qy) || !is_finite(qz)) bad = 1;
   auto tau = [&](int d) -> double {
     const double dx = qx - m[3 * d], dy = qy - m[3 * d + 1], dz = qz - m[3 * d + 2];
     return sqrt(dx * dx + dy * dy + dz * dz) / c;
@@ -258,9 +236,9 @@ __device__ __forceinline__ int bf_cholesky(double2& m, int D, int r, int c, bool
       m.x /= l;
       m.y /= l;
     }
-    const double2 lr = bf_shfl(m, 8 * r + k), lc = bf_shfl(m, 8 * c + k);
+    const double2 lr = cshfl(m, 8 * r + k), lc = cshfl(m, 8 * c + k);
     if (in && c > k && r >= c) {
-      const double2 p = bf_mul_conj(lr, lc);
+      const double2 p = cmul_conj(lr, lc);
       m.x -= p.x;
       m.y -= p.y;
     }
@@ -275,9 +253,9 @@ __device__ __forceinline__ void bf_forward(const double2& m, double2& rhs, int D
       rhs.x /= l;
       rhs.y /= l;
     }
-    const double2 yk = bf_shfl(rhs, 8 * k + c), lrk = bf_shfl(m, 8 * r + k);
+    const double2 yk = cshfl(rhs, 8 * k + c), lrk = cshfl(m, 8 * r + k);
     if (in && r > k) {
-      const double2 p = bf_mul(lrk, yk);
+      const double2 p = cmul(lrk, yk);
       rhs.x -= p.x;
       rhs.y -= p.y;
     }
@@ -291,9 +269,9 @@ __device__ __forceinline__ void bf_backward(const double2& m, double2& rhs, int 
       rhs.x /= l;
       rhs.y /= l;
     }
-    const double2 zk = bf_shfl(rhs, 8 * k + c), lkr = bf_shfl(m, 8 * k + r);
+    const double2 zk = cshfl(rhs, 8 * k + c), lkr = cshfl(m, 8 * k + r);
     if (r < k) {
-      const double2 p = bf_conj_mul(lkr, zk);
+      const double2 p = conj_cmul(lkr, zk);
       rhs.x -= p.x;
       rhs.y -= p.y;
     }
@@ -377,10 +355,10 @@ __global__ __launch_bounds__(BF_THREADS) void bf_gev_kernel(BfGevArgs a) {
   // every lane sees the same pivots, eigenvalues and a_ref, so `fail` is the same in the whole wave
   int fail = bf_cholesky(m, D, r, c, in);
   bf_forward(m, rhs, D, r, c, in);                   // Y = L^-1 Phi_s
-  const double2 yt = bf_shfl(rhs, 8 * c + r);
+  const double2 yt = cshfl(rhs, 8 * c + r);
   rhs = in ? make_double2(yt.x, -yt.y) : zero;       // Y^H
   bf_forward(m, rhs, D, r, c, in);                   // L^-1 Y^H = C: Hermitian but for rounding; its lower triangle counts
-  const double2 low = bf_shfl(rhs, 8 * c + r);
+  const double2 low = cshfl(rhs, 8 * c + r);
   double2 cm = zero;
   if (in) cm = r > c ? rhs : (r == c ? make_double2(rhs.x, 0.0) : make_double2(low.x, -low.y));
 
@@ -396,24 +374,24 @@ __global__ __launch_bounds__(BF_THREADS) void bf_gev_kernel(BfGevArgs a) {
   double2 av = zero;
   for (int k = 0; k < D; ++k) {
     const double l = sqrt(__shfl(m.x, 9 * k, 64));
-    const double2 lrk = bf_shfl(m, 8 * r + k), uk = bf_shfl(v, 8 * k + top);
+    const double2 lrk = cshfl(m, 8 * r + k), uk = cshfl(v, 8 * k + top);
     if (k <= r) {
-      const double2 p = k < r ? bf_mul(lrk, uk) : make_double2(l * uk.x, l * uk.y);
+      const double2 p = k < r ? cmul(lrk, uk) : make_double2(l * uk.x, l * uk.y);
       av = k == 0 ? p : make_double2(av.x + p.x, av.y + p.y);
     }
   }
-  const double2 u = bf_shfl(v, 8 * r + top);
+  const double2 u = cshfl(v, 8 * r + top);
   rhs = (r < D && c == 0) ? u : zero;
   bf_backward(m, rhs, D, r, c);                      // v = L^-H u in the lanes (r, 0)
 
-  const double2 aref = bf_shfl(av, 8 * a.ref);
+  const double2 aref = cshfl(av, 8 * a.ref);
   const double den = aref.x * aref.x + aref.y * aref.y;
   if (!(den > 0.0 && den <= DBL_MAX)) fail = BF_BAD_SOLVE;
 
   if (r < D && c == 0) {
-    const double2 num = bf_mul_conj(av, aref);
+    const double2 num = cmul_conj(av, aref);
     double2 rtf = make_double2(num.x / den, num.y / den);
-    double2 w = bf_mul_conj(rhs, aref);
+    double2 w = cmul_conj(rhs, aref);
     if (D == 1) w = rtf = make_double2(1.0, 0.0);
     if (fail) w = rtf = make_double2(r == a.ref ? 1.0 : 0.0, 0.0);
     a.W[bin * D + r] = w;
@@ -429,7 +407,7 @@ __global__ __launch_bounds__(BF_THREADS) void bf_gev_kernel(BfGevArgs a) {
 // -------------------------------------------------------------------------------------------------------------------- apply
 template <typename R, int D>
 __global__ __launch_bounds__(BF_THREADS) void bf_apply_kernel(const void* X, const double2* Wt, void* Y, long nbins, int F, int T) {
-  typedef typename BfCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const long total = nbins * T, chan_stride = (long)F * T;
   for (long e0 = (long)blockIdx.x * BF_THREADS; e0 < total; e0 += (long)gridDim.x * BF_THREADS) {
     const long bin0 = e0 / T;                        // the same in the whole workgroup
@@ -453,7 +431,7 @@ __global__ __launch_bounds__(BF_THREADS) void bf_apply_kernel(const void* X, con
     for (int d = 0; d < D; ++d) {
       if (w[d].x == 0.0 && w[d].y == 0.0) continue;   // a weight of exactly 0 adds nothing, whatever its x holds
       const double2 x = make_double2((double)v[d].x, (double)v[d].y);
-      const double2 p = w[d].y == 0.0 ? make_double2(w[d].x * x.x, w[d].x * x.y) : bf_conj_mul(w[d], x);
+      const double2 p = w[d].y == 0.0 ? make_double2(w[d].x * x.x, w[d].x * x.y) : conj_cmul(w[d], x);
       y = started ? make_double2(y.x + p.x, y.y + p.y) : p;
       started = true;
     }
@@ -468,46 +446,25 @@ __global__ __launch_bounds__(BF_THREADS) void bf_apply_kernel(const void* X, con
 
 using namespace alvq;
 
-static dim3 bf_grid(long blocks) { return dim3((unsigned)(blocks < BF_MAX_BLOCKS ? blocks : BF_MAX_BLOCKS)); }
-
-static int bf_check_dims(const char* who, int B, int D, int F) {
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 1 && D <= BF_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 1 <= D <= 8)", who, D);
-  return ALVQ_OK;
-}
-
-#define BF_FOR_D(D, CALL)   \
-  switch (D) {              \
-    case 1: CALL(1); break; \
-    case 2: CALL(2); break; \
-    case 3: CALL(3); break; \
-    case 4: CALL(4); break; \
-    case 5: CALL(5); break; \
-    case 6: CALL(6); break; \
-    case 7: CALL(7); break; \
-    default: CALL(8); break; \
-  }
-
 template <typename R>
 static int bf_cov_launch(const char* who, const R* X, const double* mask, double* Phi, int* status, int B, int D, int F, int T,
                          void* stream) {
   ALVQ_REQUIRE(X && Phi && status, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = bf_check_dims(who, B, D, F);
-  if (rc != ALVQ_OK) return rc;
-  ALVQ_REQUIRE(T >= 1 && T <= BF_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
+  ALVQ_TRY(check_frames(who, T));
   const long nbins = (long)B * F;
   const BfCovArgs args{X, mask, (double2*)Phi, status, nbins, F, T};
   hipStream_t s = (hipStream_t)stream;
   if (T <= BF_WAVE_T) {
-    const dim3 grid = bf_grid((nbins + BF_WAVES - 1) / BF_WAVES);
+    const dim3 grid = capped_grid((nbins + BF_WAVES - 1) / BF_WAVES);
 #define BF_CALL(N) hipLaunchKernelGGL((bf_cov_kernel<R, N, 1>), grid, dim3(BF_THREADS), 0, s, args)
-    BF_FOR_D(D, BF_CALL)
+    ALVQ_FOR_1_TO_8(D, BF_CALL)
 #undef BF_CALL
   } else {
-    const dim3 grid = bf_grid(nbins);
+    const dim3 grid = capped_grid(nbins);
 #define BF_CALL(N) hipLaunchKernelGGL((bf_cov_kernel<R, N, BF_WAVES>), grid, dim3(BF_THREADS), 0, s, args)
-    BF_FOR_D(D, BF_CALL)
+    ALVQ_FOR_1_TO_8(D, BF_CALL)
 #undef BF_CALL
   }
   return check_launch(who);
@@ -527,8 +484,8 @@ extern "C" int alvq_steering_vectors_f64(const double* mics, const double* src, 
                                          int n_fft, double c, int ref, int mics_batched, void* stream) {
   const char* who = "alvq_steering_vectors_f64";
   ALVQ_REQUIRE(mics && src && A && status, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = bf_check_dims(who, B, D, F);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
   ALVQ_REQUIRE(n_fft >= 2 && n_fft <= (1 << 24) && F <= (1 << 24), ALVQ_EINVAL, "%s: n_fft=%d F=%d (need 2 <= n_fft <= 2^24, F <= 2^24)",
                who, n_fft, F);
   ALVQ_REQUIRE(std::isfinite(fs) && fs > 0.0 && std::isfinite(c) && c > 0.0, ALVQ_EINVAL, "%s: fs=%g c=%g must be finite and > 0",
@@ -543,8 +500,8 @@ extern "C" int alvq_beamform_weights_f64(const double* Phi_n, const double* Phi_
                                          int D, int F, int mode, int ref, double loading, void* stream) {
   const char* who = "alvq_beamform_weights_f64";
   ALVQ_REQUIRE(W && status, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = bf_check_dims(who, B, D, F);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
   ALVQ_REQUIRE(mode >= BF_DAS && mode <= BF_SOUDEN, ALVQ_EINVAL, "%s: mode=%d (need 0, 1 or 2)", who, mode);
   ALVQ_REQUIRE(ref >= 0 && ref < D, ALVQ_EINVAL, "%s: ref=%d (need 0 <= ref < D = %d)", who, ref, D);
   ALVQ_REQUIRE(std::isfinite(loading) && loading >= 0.0, ALVQ_EINVAL, "%s: loading=%g must be finite and >= 0", who, loading);
@@ -554,10 +511,10 @@ extern "C" int alvq_beamform_weights_f64(const double* Phi_n, const double* Phi_
   const BfWeightArgs args{(const double2*)Phi_n, (const double2*)Phi_s, (const double2*)A, (double2*)W, status, nbins, D, F, mode, ref,
                           loading};
   if (mode == BF_DAS)
-    hipLaunchKernelGGL(bf_das_kernel, bf_grid((nbins * D + BF_THREADS - 1) / BF_THREADS), dim3(BF_THREADS), 0,
+    hipLaunchKernelGGL(bf_das_kernel, capped_grid((nbins * D + BF_THREADS - 1) / BF_THREADS), dim3(BF_THREADS), 0,
                        (hipStream_t)stream, args);
   else
-    hipLaunchKernelGGL(bf_mvdr_kernel, bf_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(bf_mvdr_kernel, capped_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream,
                        args);
   return check_launch(who);
 }
@@ -566,28 +523,28 @@ extern "C" int alvq_beamform_gev_f64(const double* Phi_n, const double* Phi_s, d
                                      int B, int D, int F, int ref, double loading, void* stream) {
   const char* who = "alvq_beamform_gev_f64";
   ALVQ_REQUIRE(Phi_n && Phi_s && W && RTF && gain && status, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = bf_check_dims(who, B, D, F);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
   ALVQ_REQUIRE(ref >= 0 && ref < D, ALVQ_EINVAL, "%s: ref=%d (need 0 <= ref < D = %d)", who, ref, D);
   ALVQ_REQUIRE(std::isfinite(loading) && loading >= 0.0, ALVQ_EINVAL, "%s: loading=%g must be finite and >= 0", who, loading);
   const long nbins = (long)B * F;
   const BfGevArgs args{(const double2*)Phi_n, (const double2*)Phi_s, (double2*)W, (double2*)RTF, gain, status, nbins, D, ref, loading};
-  hipLaunchKernelGGL(bf_gev_kernel, bf_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream, args);
+  hipLaunchKernelGGL(bf_gev_kernel, capped_grid((nbins + BF_WAVES - 1) / BF_WAVES), dim3(BF_THREADS), 0, (hipStream_t)stream, args);
   return check_launch(who);
 }
 
 template <typename R>
 static int bf_apply_launch(const char* who, const R* X, const double* W, R* Y, int B, int D, int F, int T, void* stream) {
   ALVQ_REQUIRE(X && W && Y, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = bf_check_dims(who, B, D, F);
-  if (rc != ALVQ_OK) return rc;
-  ALVQ_REQUIRE(T >= 1 && T <= BF_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
+  ALVQ_TRY(check_frames(who, T));
   const long nbins = (long)B * F, blocks = (nbins * T + BF_THREADS - 1) / BF_THREADS;
-  const dim3 grid = bf_grid(blocks);
+  const dim3 grid = capped_grid(blocks);
   hipStream_t s = (hipStream_t)stream;
 #define BF_CALL(N) \
   hipLaunchKernelGGL((bf_apply_kernel<R, N>), grid, dim3(BF_THREADS), 0, s, (const void*)X, (const double2*)W, (void*)Y, nbins, F, T)
-  BF_FOR_D(D, BF_CALL)
+  ALVQ_FOR_1_TO_8(D, BF_CALL)
 #undef BF_CALL
   return check_launch(who);
 }

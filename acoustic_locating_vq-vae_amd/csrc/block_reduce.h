@@ -93,6 +93,10 @@ struct OpMax {  // fmax / fmaxf: a NaN operand is dropped
   static __device__ __forceinline__ double f(double a, double b) { return fmax(a, b); }
   template <typename T> static __device__ __forceinline__ T wave(T v) { return wave_max(v); }
 };
+struct OpOr {  // the OR of an int of flags (phat_status_kernel, music_status_kernel): an OR has no order
+  static __device__ __forceinline__ int f(int a, int b) { return a | b; }
+  static __device__ __forceinline__ int wave(int v) { return wave_or(v); }
+};
 struct OpGreater {  // a > b ? a : b, the form of the spectrogram statistics' tree (a NaN in b is dropped, one in a is kept)
   template <typename T> static __device__ __forceinline__ T f(T a, T b) { return a > b ? a : b; }
 };

@@ -37,7 +37,7 @@
 //   and one wave a SIMD), and the decomposition is a chain of dependent shuffles, divisions and square roots that only other
 //   waves can hide: measured 0.407 ms of a 0.734 ms iteration at (B, D, K, F, T) = (64, 4, 3, 201, 500) and 0.320 ms of 0.417 ms
 //   at (8, 8, 3, 201, 500), where 4824 matrices then ran five deep on 1024 SIMDs.  The bits are the same either way.
-// Every grid but cac_prior_kernel's (at most 1024 x 65535) is capped at CAC_MAX_BLOCKS workgroups and strides over the bins
+// Every grid but cac_prior_kernel's (at most 1024 x 65535) is capped at kMaxBlocks workgroups and strides over the bins
 // (pairs) beyond, whole waves or whole workgroups at a time.  No atomics anywhere, no host-side decision between the launches: the
 // status is read on the device.  v_mfma_f64 is not used, for the reason csrc/wpe.hip gives.
 // What the launches cost: DESIGN.md.
@@ -45,7 +45,7 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 #include "herm_eig.h"
 
 namespace alvq {
@@ -53,28 +53,17 @@ namespace alvq {
 constexpr int CAC_THREADS = 256;
 constexpr int CAC_WAVES = CAC_THREADS / kWave;
 constexpr int CAC_TILE = 64;               // the frames of a workgroup of cac_prior_kernel: a lane each, in every wave
-constexpr int CAC_MAX_D = 8;
 constexpr int CAC_MAX_K = 8;
-constexpr int CAC_MAX_T = 65535;
 constexpr int CAC_MAX_ITERATIONS = 256;
-constexpr long CAC_MAX_BLOCKS = 1 << 16;
 
 constexpr int CAC_BAD_INPUT = 1;           // a non-finite X or |x|^2, a negative or non-finite init, a quadratic0 not > 0 and finite
 constexpr int CAC_BAD_EIG = 2;             // herm_eig's status, or a lambda_max that is not > 0 and finite
-
-template <typename R> struct CacCplx;
-template <> struct CacCplx<float> { typedef float2 type; };
-template <> struct CacCplx<double> { typedef double2 type; };
-
-__device__ __forceinline__ double2 cac_mul(double2 a, double2 b) {           // a b
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
 
 // -------------------------------------------------------------------------------------------------------------------- check
 template <typename R>
 __global__ __launch_bounds__(CAC_THREADS) void cac_check_kernel(const void* X, const double* init, const double* q0, double* gamma,
                                                                  double* quad, int* status, long nbins, int D, int K, int F, int T) {
-  typedef typename CacCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long chan_stride = (long)F * T;
   for (long bin = (long)blockIdx.x * CAC_WAVES + wv; bin < nbins; bin += (long)gridDim.x * CAC_WAVES) {
@@ -87,10 +76,10 @@ __global__ __launch_bounds__(CAC_THREADS) void cac_check_kernel(const void* X, c
       for (int d = 0; d < D; ++d) {
         const C v = xg[d * chan_stride + t];
         const double re = (double)v.x, im = (double)v.y;
-        if (!he_finite(re) || !he_finite(im)) bad = 1;
+        if (!is_finite(re) || !is_finite(im)) bad = 1;
         n += re * re + im * im;
       }
-      if (!he_finite(n)) bad = 1;
+      if (!is_finite(n)) bad = 1;
       for (int k = 0; k < K; ++k) {        // a thread rewrites what it read itself: init may be masks, quadratic0 quadratic
         const long i = at + k * chan_stride + t;
         const double g = init[i], q = q0 ? q0[i] : 1.0;
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(kWave * CAC_MAX_K) void cac_prior_kernel(const doub
 template <typename R, int D>
 __global__ __launch_bounds__(CAC_THREADS) void cac_cov_kernel(const void* X, const double* gamma, const double* quad,
                                                                const int* status, double2* A, long nbins, int K, int F, int T) {
-  typedef typename CacCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   constexpr int NA = D * D;                            // D real diagonal sums and D (D - 1) / 2 complex ones below it
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long chan_stride = (long)F * T;
@@ -265,7 +254,7 @@ __global__ __launch_bounds__(CAC_THREADS) void cac_eig_kernel(int* status, doubl
       double2 s = make_double2(0.0, 0.0);
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        const double2 p = he_shfl(v, 8 * r + col[j]), o = he_shfl(v, 8 * c + col[j]);
+        const double2 p = cshfl(v, 8 * r + col[j]), o = cshfl(v, 8 * c + col[j]);
         const double pr = lam[j] * (p.x * o.x + p.y * o.y), pi = lam[j] * (p.y * o.x - p.x * o.y);
         s = j == 0 ? make_double2(pr, pi) : make_double2(s.x + pr, s.y + pi);
       }
@@ -280,7 +269,7 @@ __global__ __launch_bounds__(CAC_THREADS) void cac_estep_kernel(const void* X, c
                                                                  const double2* A, const double* logdet, const int* status,
                                                                  double* gamma, double* quad, double2* cov, long nbins, int K, int F,
                                                                  int T, int last) {
-  typedef typename CacCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   __shared__ double2 As[CAC_MAX_K * D * D];
   __shared__ double lds[CAC_MAX_K];
   __shared__ double ls[CAC_MAX_K][CAC_THREADS];        // a private column a thread: the frame's l_k, then exp(l_k - max)
@@ -327,10 +316,10 @@ __global__ __launch_bounds__(CAC_THREADS) void cac_estep_kernel(const void* X, c
         double qs = 0.0;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-          double2 y = cac_mul(ak[i * D], x[0]);        // d rising from the first product
+          double2 y = cmul(ak[i * D], x[0]);        // d rising from the first product
 #pragma unroll
           for (int d = 1; d < D; ++d) {
-            const double2 p = cac_mul(ak[i * D + d], x[d]);
+            const double2 p = cmul(ak[i * D + d], x[d]);
             y.x += p.x;
             y.y += p.y;
           }
@@ -363,23 +352,10 @@ __global__ __launch_bounds__(CAC_THREADS) void cac_estep_kernel(const void* X, c
 
 using namespace alvq;
 
-static dim3 cac_grid(long blocks) { return dim3((unsigned)(blocks < CAC_MAX_BLOCKS ? blocks : CAC_MAX_BLOCKS)); }
-
 static bool cac_dims_ok(int B, int D, int K, int F, int T) {
-  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && D >= 2 && D <= CAC_MAX_D && K >= 1 && K <= CAC_MAX_K && T >= 1 &&
-         T <= CAC_MAX_T;
+  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && D >= 2 && D <= kMaxMics && K >= 1 && K <= CAC_MAX_K && T >= 1 &&
+         T <= kMaxFrames;
 }
-
-#define CAC_FOR_D(D, CALL)  \
-  switch (D) {              \
-    case 2: CALL(2); break; \
-    case 3: CALL(3); break; \
-    case 4: CALL(4); break; \
-    case 5: CALL(5); break; \
-    case 6: CALL(6); break; \
-    case 7: CALL(7); break; \
-    default: CALL(8); break; \
-  }
 
 extern "C" int64_t alvq_cacgmm_workspace_bytes(int B, int D, int K, int F, int T) {
   if (!cac_dims_ok(B, D, K, F, T)) return -1;
@@ -393,11 +369,10 @@ static int cac_launch(const char* who, const R* X, const double* init, const dou
                       double* cov, double* quadratic, int* status, void* workspace, int B, int D, int K, int F, int T, int iterations,
                       double floor, void* stream) {
   ALVQ_REQUIRE(X && init && masks && prior && cov && quadratic && status && workspace, ALVQ_EINVAL, "%s: null pointer", who);
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 2 && D <= CAC_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 2 <= D <= 8)", who, D);
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D, 2));
   ALVQ_REQUIRE(K >= 1 && K <= CAC_MAX_K, ALVQ_EINVAL, "%s: K=%d (need 1 <= K <= 8)", who, K);
-  ALVQ_REQUIRE(T >= 1 && T <= CAC_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
+  ALVQ_TRY(check_frames(who, T));
   ALVQ_REQUIRE(iterations >= 1 && iterations <= CAC_MAX_ITERATIONS, ALVQ_EINVAL, "%s: iterations=%d (need 1 <= iterations <= 256)",
                who, iterations);
   ALVQ_REQUIRE(floor >= 0.0 && floor <= 1.0, ALVQ_EINVAL, "%s: floor=%g must be in [0, 1]", who, floor);
@@ -406,10 +381,10 @@ static int cac_launch(const char* who, const R* X, const double* init, const dou
   double2* A = (double2*)workspace;
   double* logdet = (double*)((char*)workspace + (int64_t)16 * nbins * K * D * D);
   double* logprior = logdet + nbins * K;
-  hipLaunchKernelGGL((cac_check_kernel<R>), cac_grid((nbins + CAC_WAVES - 1) / CAC_WAVES), dim3(CAC_THREADS), 0, s, (const void*)X, init,
+  hipLaunchKernelGGL((cac_check_kernel<R>), capped_grid((nbins + CAC_WAVES - 1) / CAC_WAVES), dim3(CAC_THREADS), 0, s, (const void*)X, init,
                      quadratic0, masks, quadratic, status, nbins, D, K, F, T);
   const dim3 tiles((unsigned)((T + CAC_TILE - 1) / CAC_TILE), (unsigned)B);
-  const dim3 m_grid = cac_grid((nbins * K + CAC_WAVES - 1) / CAC_WAVES), e_grid = cac_grid(nbins);
+  const dim3 m_grid = capped_grid((nbins * K + CAC_WAVES - 1) / CAC_WAVES), e_grid = capped_grid(nbins);
   for (int it = 0; it < iterations; ++it) {
     const int last = it == iterations - 1;
     hipLaunchKernelGGL(cac_prior_kernel, tiles, dim3(kWave * K), 0, s, (const double*)masks, (const int*)status, prior, logprior, K, F,
@@ -417,17 +392,17 @@ static int cac_launch(const char* who, const R* X, const double* init, const dou
 #define CAC_CALL(N)                                                                                                      \
   hipLaunchKernelGGL((cac_cov_kernel<R, N>), m_grid, dim3(CAC_THREADS), 0, s, (const void*)X, (const double*)masks,     \
                      (const double*)quadratic, (const int*)status, A, nbins, K, F, T)
-    CAC_FOR_D(D, CAC_CALL)
+    ALVQ_FOR_2_TO_8(D, CAC_CALL)
 #undef CAC_CALL
 #define CAC_CALL(N) \
   hipLaunchKernelGGL((cac_eig_kernel<N>), m_grid, dim3(CAC_THREADS), 0, s, status, A, logdet, (double2*)cov, nbins, K, floor, last)
-    CAC_FOR_D(D, CAC_CALL)
+    ALVQ_FOR_2_TO_8(D, CAC_CALL)
 #undef CAC_CALL
 #define CAC_CALL(N)                                                                                                                   \
   hipLaunchKernelGGL((cac_estep_kernel<R, N>), e_grid, dim3(CAC_THREADS), 0, s, (const void*)X, (const double*)prior,               \
                      (const double*)logprior, (const double2*)A, \
                      (const double*)logdet, (const int*)status, masks, quadratic, (double2*)cov, nbins, K, F, T, last)
-    CAC_FOR_D(D, CAC_CALL)
+    ALVQ_FOR_2_TO_8(D, CAC_CALL)
 #undef CAC_CALL
   }
   return check_launch(who);

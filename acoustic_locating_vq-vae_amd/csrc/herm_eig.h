@@ -19,11 +19,10 @@
 #pragma once
 #include <cfloat>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 
 namespace alvq {
 
-constexpr int HE_MAX_D = 8;
 constexpr int HE_MAX_SWEEPS = 16;
 constexpr double HE_U = 1.1102230246251565e-16;      // 2^-53
 constexpr int HE_BAD_INPUT = 1;                      // a non-finite entry was read
@@ -34,9 +33,6 @@ struct HermEig {
   int rank;          // its place in ascending order: column c of V belongs at column `rank` of the output
   int status;        // the same in every lane
 };
-
-__device__ __forceinline__ double2 he_shfl(double2 v, int src) { return make_double2(__shfl(v.x, src, 64), __shfl(v.y, src, 64)); }
-__device__ __forceinline__ bool he_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // whom index i meets at step s of the round robin of m players (m even); an index beyond the table meets itself
 __device__ __forceinline__ int he_partner(int i, int s, int m) {
@@ -54,7 +50,7 @@ __device__ __forceinline__ HermEig herm_eig(double2 a, double2& v, int D, int la
   const bool in = r < D && c < D;
   HermEig out;
   out.status = 0;
-  if (__any(in && (!he_finite(a.x) || !he_finite(a.y)))) {
+  if (__any(in && (!is_finite(a.x) || !is_finite(a.y)))) {
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     v = make_double2(nan, nan);
     out.lam = nan;
@@ -80,7 +76,7 @@ __device__ __forceinline__ HermEig herm_eig(double2 a, double2& v, int D, int la
         const bool pair = r < D && pr < D && pr != r;
         const int lo = pair ? min(r, pr) : r, hi = pair ? max(r, pr) : r;
         const double alpha = __shfl(a.x, 9 * lo, 64), beta = __shfl(a.x, 9 * hi, 64);
-        const double2 g = he_shfl(a, 8 * hi + lo);                         // a_qp; a_pq is its conjugate
+        const double2 g = cshfl(a, 8 * hi + lo);                         // a_qp; a_pq is its conjugate
         const double absg = hypot(g.x, g.y);
         const bool rot = pair && absg > thr;
         double cs = 1.0, h = 0.0;
@@ -97,10 +93,10 @@ __device__ __forceinline__ HermEig herm_eig(double2 a, double2& v, int D, int la
         rotated = true;
         // the pair of the lane's column: what the lanes of row c have just computed
         const double ccs = __shfl(cs, 9 * c, 64);
-        const double2 csn = he_shfl(sn, 9 * c);
+        const double2 csn = cshfl(sn, 9 * c);
         const int crot = __shfl((int)rot, 9 * c, 64);
         // A <- A J, V <- V J:  col_p <- cs col_p - conj(sn) col_q,  col_q <- sn col_p + cs col_q
-        const double2 ya = he_shfl(a, 8 * r + pc), yv = he_shfl(v, 8 * r + pc);
+        const double2 ya = cshfl(a, 8 * r + pc), yv = cshfl(v, 8 * r + pc);
         if (crot) {
           if (c < pc) {
             a = make_double2(ccs * a.x - (csn.x * ya.x + csn.y * ya.y), ccs * a.y - (csn.x * ya.y - csn.y * ya.x));
@@ -111,7 +107,7 @@ __device__ __forceinline__ HermEig herm_eig(double2 a, double2& v, int D, int la
           }
         }
         // A <- J^H A:  row_p <- cs row_p - sn row_q,  row_q <- conj(sn) row_p + cs row_q
-        const double2 yr = he_shfl(a, 8 * pr + c);
+        const double2 yr = cshfl(a, 8 * pr + c);
         if (rot) {
           if (r < pr)
             a = make_double2(cs * a.x - (sn.x * yr.x - sn.y * yr.y), cs * a.y - (sn.x * yr.y + sn.y * yr.x));
@@ -141,7 +137,7 @@ __device__ __forceinline__ HermEig herm_eig(double2 a, double2& v, int D, int la
   double best = -1.0;
   double2 vm = make_double2(1.0, 0.0);
   for (int i = 0; i < D; ++i) {
-    const double2 x = he_shfl(v, 8 * i + c);
+    const double2 x = cshfl(v, 8 * i + c);
     const double m2 = x.x * x.x + x.y * x.y;
     if (m2 > best) {
       best = m2;

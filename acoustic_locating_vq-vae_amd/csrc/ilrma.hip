@@ -34,7 +34,7 @@
 // would make that kernel a template of L as well -- 2 x 8 x 16 instantiations of the largest kernel here -- and put L loads and
 // a division between the loads of a frame and its D^2 fused multiply-adds.  Nothing has been measured that says otherwise.
 // v_mfma_f64 is not used, for the reason csrc/wpe.hip gives.  No atomics, no host-side decision between the launches.
-// Every grid over rows, pairs or bins is capped at IVA_MAX_BLOCKS workgroups and strides, whole waves at a time.
+// Every grid over rows, pairs or bins is capped at kMaxBlocks workgroups and strides, whole waves at a time.
 // What the launches cost: DESIGN.md.
 #include "iva_kernels.h"
 
@@ -58,7 +58,7 @@ __device__ __forceinline__ double ilrma_model(const double (&bs)[L], const doubl
 // the multiplicative update of one entry: v sqrt(num / den) where the ratio is finite, v where it is not; floored
 __device__ __forceinline__ double ilrma_update(double v, double num, double den, double floor) {
   const double ratio = num / den;
-  return ilrma_floor(iva_finite(ratio) ? v * sqrt(ratio) : v, floor);
+  return ilrma_floor(is_finite(ratio) ? v * sqrt(ratio) : v, floor);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- start
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(IVA_THREADS) void ilrma_bin_kernel(const double* ba
 template <typename R, int D>
 __global__ __launch_bounds__(IVA_THREADS) void ilrma_power_kernel(const void* X, const double2* W, const int* status, double* P,
                                                                   double* rowsum, long nbins, int F, int T) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long chan_stride = (long)F * T;
   for (long e = (long)blockIdx.x * IVA_WAVES + wv; e < nbins * D; e += (long)gridDim.x * IVA_WAVES) {
@@ -119,10 +119,10 @@ __global__ __launch_bounds__(IVA_THREADS) void ilrma_power_kernel(const void* X,
       C v[D];
 #pragma unroll
       for (int d = 0; d < D; ++d) v[d] = xg[d * chan_stride + t];
-      double2 y = iva_mul(w[0], make_double2((double)v[0].x, (double)v[0].y));
+      double2 y = cmul(w[0], make_double2((double)v[0].x, (double)v[0].y));
 #pragma unroll
       for (int d = 1; d < D; ++d) {
-        const double2 q = iva_mul(w[d], make_double2((double)v[d].x, (double)v[d].y));
+        const double2 q = cmul(w[d], make_double2((double)v[d].x, (double)v[d].y));
         y.x += q.x;
         y.y += q.y;
       }
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(IVA_THREADS) void ilrma_basis_kernel(const double* 
 
 // -------------------------------------------------------------------------------------------------------------- activations
 template <int L>
-__global__ __launch_bounds__(kWave * IVA_MAX_D) void ilrma_act_kernel(const double* P, const double* basis, const double* lam,
+__global__ __launch_bounds__(kWave * kMaxMics) void ilrma_act_kernel(const double* P, const double* basis, const double* lam,
                                                                       const int* status, double* act, int D, int F, int T,
                                                                       double floor) {
   const int lane = threadIdx.x & 63;
@@ -298,7 +298,7 @@ using namespace alvq;
 static int64_t ilrma_round16(int64_t n) { return (n + 15) / 16 * 16; }
 
 static bool ilrma_dims_ok(int B, int D, int L, int F, int T) {
-  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && D >= 1 && D <= IVA_MAX_D && T >= 1 && T <= IVA_MAX_T && L >= 1 &&
+  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && D >= 1 && D <= kMaxMics && T >= 1 && T <= kMaxFrames && L >= 1 &&
          L <= ILRMA_MAX_L;
 }
 
@@ -327,8 +327,9 @@ static int ilrma_launch(const char* who, const R* X, const double* W0, const dou
                         int iterations, int ref, double floor, void* stream) {
   ALVQ_REQUIRE(X && basis0 && activations0 && W && basis && activations && Y && status && workspace, ALVQ_EINVAL, "%s: null pointer",
                who);
-  const int rc = iva_check_dims(who, B, D, F, T);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
+  ALVQ_TRY(check_frames(who, T));
   ALVQ_REQUIRE(L >= 1 && L <= ILRMA_MAX_L, ALVQ_EINVAL, "%s: L=%d (need 1 <= L <= 16)", who, L);
   ALVQ_REQUIRE(iterations >= 0 && iterations <= IVA_MAX_ITERATIONS, ALVQ_EINVAL, "%s: iterations=%d (need 0 <= iterations <= 256)", who,
                iterations);
@@ -345,7 +346,7 @@ static int ilrma_launch(const char* who, const R* X, const double* W0, const dou
   int* flags = (int*)(base + ws.flags);
   double2* Wd = (double2*)W;
   const dim3 threads(IVA_THREADS);
-  const dim3 bin_grid = iva_grid((nbins + IVA_WAVES - 1) / IVA_WAVES), row_grid = iva_grid((rows + IVA_WAVES - 1) / IVA_WAVES);
+  const dim3 bin_grid = capped_grid((nbins + IVA_WAVES - 1) / IVA_WAVES), row_grid = capped_grid((rows + IVA_WAVES - 1) / IVA_WAVES);
   hipLaunchKernelGGL((iva_check_kernel<R>), bin_grid, threads, 0, s, (const void*)X, (const double2*)W0, Wd, status, nbins, D, F, T);
   hipLaunchKernelGGL(ilrma_item_kernel, dim3((unsigned)B), threads, 0, s, activations0, activations, flags, (long)D * L * T);
   hipLaunchKernelGGL(ilrma_bin_kernel, bin_grid, threads, 0, s, basis0, basis, (const int*)flags, Wd, status, nbins, D, L, F);
@@ -355,7 +356,7 @@ static int ilrma_launch(const char* who, const R* X, const double* W0, const dou
 #define IVA_CALL(N)                                                                                                                 \
   hipLaunchKernelGGL((ilrma_power_kernel<R, N>), row_grid, threads, 0, s, (const void*)X, (const double2*)Wd, (const int*)status, P, \
                      rowsum, nbins, F, T)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
     hipLaunchKernelGGL(ilrma_lambda_kernel, dim3((unsigned)((pairs + IVA_WAVES - 1) / IVA_WAVES)), threads, 0, s,
                        (const double*)rowsum, (const int*)status, lam, pairs, D, F, T);
@@ -377,16 +378,16 @@ static int ilrma_launch(const char* who, const R* X, const double* W0, const dou
 #define IVA_CALL(N)                                                                                                                \
   hipLaunchKernelGGL((iva_cov_kernel<R, N>), row_grid, threads, 0, s, (const void*)X, (const double*)P, (const int*)status, V, nbins, \
                      F, T, (long)F * T, (long)T)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
 #define IVA_CALL(N) \
   hipLaunchKernelGGL((iva_solve_kernel<N, true>), bin_grid, threads, 0, s, (const double2*)V, Wd, status, nbins, (const double*)lam, F)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
   }
 #define IVA_CALL(N) \
-  hipLaunchKernelGGL((iva_project_kernel<R, N>), iva_grid(nbins), threads, 0, s, (const void*)X, Wd, (void*)Y, status, nbins, F, T, ref)
-  IVA_FOR_D(D, IVA_CALL)
+  hipLaunchKernelGGL((iva_project_kernel<R, N>), capped_grid(nbins), threads, 0, s, (const void*)X, Wd, (void*)Y, status, nbins, F, T, ref)
+  ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
   return check_launch(who);
 }

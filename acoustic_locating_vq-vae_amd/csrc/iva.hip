@@ -42,7 +42,7 @@
 //                     16 D T bytes, from cache.  A bin whose status is not 0 is copied, bit for bit.
 // iva_masks_kernel<R, K>   elementwise, a thread a (b, f, t).
 // Every grid but iva_activity_kernel's (at most 1024 x 65535) and iva_weights_kernel's (B D <= 524 280) is capped at
-// IVA_MAX_BLOCKS workgroups and strides over the bins (pairs, outputs) beyond, whole waves or whole workgroups at a time.
+// kMaxBlocks workgroups and strides over the bins (pairs, outputs) beyond, whole waves or whole workgroups at a time.
 // No atomics anywhere, no host-side decision between the launches: the status is read on the device.
 // What the launches cost: DESIGN.md.
 // iva_check_kernel, iva_cov_kernel, iva_solve (and iva_solve_kernel) and iva_project_kernel live in csrc/iva_kernels.h, which
@@ -55,7 +55,7 @@ namespace alvq {
 template <typename R, int D>
 __global__ __launch_bounds__(kWave * D) void iva_activity_kernel(const void* X, const double2* W, const int* status, double* P, int F,
                                                                 int T) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const int lane = threadIdx.x & 63;
   const int k = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));          // wave k of the workgroup owns source k
   const int b = blockIdx.y, t = blockIdx.x * IVA_TILE + lane;
@@ -74,10 +74,10 @@ __global__ __launch_bounds__(kWave * D) void iva_activity_kernel(const void* X, 
       const C v = xg[d * chan_stride + (long)f * T];
       x[d] = make_double2((double)v.x, (double)v.y);
     }
-    double2 y = iva_mul(w[0], x[0]);
+    double2 y = cmul(w[0], x[0]);
 #pragma unroll
     for (int d = 1; d < D; ++d) {
-      const double2 q = iva_mul(w[d], x[d]);
+      const double2 q = cmul(w[d], x[d]);
       y.x += q.x;
       y.y += q.y;
     }
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_weights_kernel(double* P, int
 // -------------------------------------------------------------------------------------------------------------------- masks
 template <typename R, int K>
 __global__ __launch_bounds__(IVA_THREADS) void iva_masks_kernel(const void* Y, double* M, long nbins, int F, int T) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const long total = nbins * T, chan_stride = (long)F * T;
   for (long e = (long)blockIdx.x * IVA_THREADS + threadIdx.x; e < total; e += (long)gridDim.x * IVA_THREADS) {
     const long bin = e / T;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_masks_kernel(const void* Y, d
     for (int k = 0; k < K; ++k) {
       double m = 0.0;                                  // a sum that is not finite
       if (s == 0.0) m = 1.0 / (double)K;
-      else if (iva_finite(s)) m = q[k] / s;
+      else if (is_finite(s)) m = q[k] / s;
       M[at + k * chan_stride] = m;
     }
   }
@@ -148,7 +148,7 @@ using namespace alvq;
 static int64_t iva_phi_bytes(int B, int D, int T) { return ((int64_t)8 * B * D * T + 15) / 16 * 16; }
 
 extern "C" int64_t alvq_auxiva_workspace_bytes(int B, int D, int F, int T) {
-  if (B < 1 || B > 65535 || F < 1 || (long)B * F > INT_MAX || D < 1 || D > IVA_MAX_D || T < 1 || T > IVA_MAX_T) return -1;
+  if (B < 1 || B > 65535 || F < 1 || (long)B * F > INT_MAX || D < 1 || D > kMaxMics || T < 1 || T > kMaxFrames) return -1;
   // p, then phi over it: (B, D, T) float64; the D weighted covariances of every bin: (B, F, D, D, D) complex128
   return iva_phi_bytes(B, D, T) + (int64_t)16 * B * F * D * D * D;
 }
@@ -157,8 +157,9 @@ template <typename R>
 static int iva_launch(const char* who, const R* X, const double* W0, double* W, R* Y, int* status, void* workspace, int B, int D, int F,
                       int T, int model, int iterations, int ref, double eps, void* stream) {
   ALVQ_REQUIRE(X && W && Y && status && workspace, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = iva_check_dims(who, B, D, F, T);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D));
+  ALVQ_TRY(check_frames(who, T));
   ALVQ_REQUIRE(model == IVA_LAPLACE || model == IVA_GAUSS, ALVQ_EINVAL, "%s: model=%d (need 0 = laplace or 1 = gauss)", who, model);
   ALVQ_REQUIRE(iterations >= 0 && iterations <= IVA_MAX_ITERATIONS, ALVQ_EINVAL, "%s: iterations=%d (need 0 <= iterations <= 256)", who,
                iterations);
@@ -168,29 +169,29 @@ static int iva_launch(const char* who, const R* X, const double* W0, double* W, 
   hipStream_t s = (hipStream_t)stream;
   double* P = (double*)workspace;
   double2* Wd = (double2*)W;
-  hipLaunchKernelGGL((iva_check_kernel<R>), iva_grid((nbins + IVA_WAVES - 1) / IVA_WAVES), dim3(IVA_THREADS), 0, s, (const void*)X,
+  hipLaunchKernelGGL((iva_check_kernel<R>), capped_grid((nbins + IVA_WAVES - 1) / IVA_WAVES), dim3(IVA_THREADS), 0, s, (const void*)X,
                      (const double2*)W0, Wd, status, nbins, D, F, T);
   double2* V = (double2*)((char*)workspace + iva_phi_bytes(B, D, T));
   const dim3 tiles((unsigned)((T + IVA_TILE - 1) / IVA_TILE), (unsigned)B);
-  const dim3 cov_grid = iva_grid((nbins * D + IVA_WAVES - 1) / IVA_WAVES), solve_grid = iva_grid((nbins + IVA_WAVES - 1) / IVA_WAVES);
+  const dim3 cov_grid = capped_grid((nbins * D + IVA_WAVES - 1) / IVA_WAVES), solve_grid = capped_grid((nbins + IVA_WAVES - 1) / IVA_WAVES);
   for (int it = 0; it < iterations; ++it) {
 #define IVA_CALL(N) \
   hipLaunchKernelGGL((iva_activity_kernel<R, N>), tiles, dim3(kWave * N), 0, s, (const void*)X, (const double2*)Wd, (const int*)status, P, F, T)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
     hipLaunchKernelGGL(iva_weights_kernel, dim3((unsigned)(B * D)), dim3(IVA_THREADS), 0, s, P, F, T, model, eps);
 #define IVA_CALL(N) \
   hipLaunchKernelGGL((iva_cov_kernel<R, N>), cov_grid, dim3(IVA_THREADS), 0, s, (const void*)X, (const double*)P, (const int*)status, V, nbins, F, T, (long)T, 0L)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
 #define IVA_CALL(N) \
   hipLaunchKernelGGL((iva_solve_kernel<N, false>), solve_grid, dim3(IVA_THREADS), 0, s, (const double2*)V, Wd, status, nbins, (const double*)nullptr, F)
-    IVA_FOR_D(D, IVA_CALL)
+    ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
   }
 #define IVA_CALL(N) \
-  hipLaunchKernelGGL((iva_project_kernel<R, N>), iva_grid(nbins), dim3(IVA_THREADS), 0, s, (const void*)X, Wd, (void*)Y, status, nbins, F, T, ref)
-  IVA_FOR_D(D, IVA_CALL)
+  hipLaunchKernelGGL((iva_project_kernel<R, N>), capped_grid(nbins), dim3(IVA_THREADS), 0, s, (const void*)X, Wd, (void*)Y, status, nbins, F, T, ref)
+  ALVQ_FOR_1_TO_8(D, IVA_CALL)
 #undef IVA_CALL
   return check_launch(who);
 }
@@ -208,13 +209,14 @@ extern "C" int alvq_auxiva_f64(const double* X, const double* W0, double* W, dou
 template <typename R>
 static int iva_masks_launch(const char* who, const R* Y, double* M, int B, int K, int F, int T, void* stream) {
   ALVQ_REQUIRE(Y && M, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = iva_check_dims(who, B, K, F, T);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, K));
+  ALVQ_TRY(check_frames(who, T));
   const long nbins = (long)B * F;
-  const dim3 grid = iva_grid((nbins * T + IVA_THREADS - 1) / IVA_THREADS);
+  const dim3 grid = capped_grid((nbins * T + IVA_THREADS - 1) / IVA_THREADS);
   hipStream_t s = (hipStream_t)stream;
 #define IVA_CALL(N) hipLaunchKernelGGL((iva_masks_kernel<R, N>), grid, dim3(IVA_THREADS), 0, s, (const void*)Y, M, nbins, F, T)
-  IVA_FOR_D(K, IVA_CALL)
+  ALVQ_FOR_1_TO_8(K, IVA_CALL)
 #undef IVA_CALL
   return check_launch(who);
 }

@@ -11,39 +11,19 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 
 namespace alvq {
 
 constexpr int IVA_THREADS = 256;
 constexpr int IVA_WAVES = IVA_THREADS / kWave;
 constexpr int IVA_TILE = 64;               // the frames of a workgroup of iva_activity_kernel: a lane each, in every wave
-constexpr int IVA_MAX_D = 8;
-constexpr int IVA_MAX_T = 65535;
 constexpr int IVA_MAX_ITERATIONS = 256;
-constexpr long IVA_MAX_BLOCKS = 1 << 16;
 
 constexpr int IVA_BAD_INPUT = 1;           // a non-finite value in the bin, or a bin of zeros
 constexpr int IVA_BAD_SOLVE = 2;           // a pivot or Re(w^H V w) that is 0 (<= 0) or not finite, or a singular W at the end
 
 constexpr int IVA_LAPLACE = 0, IVA_GAUSS = 1;
-
-template <typename R> struct IvaCplx;
-template <> struct IvaCplx<float> { typedef float2 type; };
-template <> struct IvaCplx<double> { typedef double2 type; };
-
-__device__ __forceinline__ bool iva_finite(double v) { return fabs(v) <= DBL_MAX; }
-
-__device__ __forceinline__ double2 iva_mul(double2 a, double2 b) {           // a b
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 iva_div(double2 a, double2 p) {           // a / p as a conj(p) / |p|^2
-  const double den = p.x * p.x + p.y * p.y;
-  return make_double2((a.x * p.x + a.y * p.y) / den, (a.y * p.x - a.x * p.y) / den);
-}
-__device__ __forceinline__ double2 iva_shfl(double2 v, int src) {
-  return make_double2(__shfl(v.x, src, 64), __shfl(v.y, src, 64));
-}
 
 // M z = rhs for every column of rhs at once, on the wave's layout: lane 8 r + c holds entry (r, c) of M and of rhs (a single
 // right-hand side is held in every column).  Gaussian elimination with partial pivoting, column j = 0 .. D - 1: the pivot is the
@@ -69,13 +49,13 @@ __device__ __forceinline__ int iva_solve(double2& m, double2& rhs, int r, int c)
     }
     if (!(best > 0.0 && best <= DBL_MAX)) fail = IVA_BAD_SOLVE;
     const int src = r == j ? p : (r == p ? j : r);
-    m = iva_shfl(m, 8 * src + c);
-    rhs = iva_shfl(rhs, 8 * src + c);
-    const double2 piv = iva_shfl(m, 9 * j), mrj = iva_shfl(m, 8 * r + j), mjc = iva_shfl(m, 8 * j + c);
-    const double2 bjc = iva_shfl(rhs, 8 * j + c);
+    m = cshfl(m, 8 * src + c);
+    rhs = cshfl(rhs, 8 * src + c);
+    const double2 piv = cshfl(m, 9 * j), mrj = cshfl(m, 8 * r + j), mjc = cshfl(m, 8 * j + c);
+    const double2 bjc = cshfl(rhs, 8 * j + c);
     if (r > j) {
-      const double2 l = iva_div(mrj, piv);
-      const double2 pm = iva_mul(l, mjc), pb = iva_mul(l, bjc);
+      const double2 l = cdiv(mrj, piv);
+      const double2 pm = cmul(l, mjc), pb = cmul(l, bjc);
       if (c > j) {
         m.x -= pm.x;
         m.y -= pm.y;
@@ -88,12 +68,12 @@ __device__ __forceinline__ int iva_solve(double2& m, double2& rhs, int r, int c)
   }
 #pragma unroll
   for (int j = D - 1; j >= 0; --j) {
-    const double2 piv = iva_shfl(m, 9 * j), bjc = iva_shfl(rhs, 8 * j + c), mrj = iva_shfl(m, 8 * r + j);
-    const double2 z = iva_div(bjc, piv);
+    const double2 piv = cshfl(m, 9 * j), bjc = cshfl(rhs, 8 * j + c), mrj = cshfl(m, 8 * r + j);
+    const double2 z = cdiv(bjc, piv);
     if (r == j) {
       rhs = z;
     } else if (r < j) {
-      const double2 pz = iva_mul(mrj, z);
+      const double2 pz = cmul(mrj, z);
       rhs.x -= pz.x;
       rhs.y -= pz.y;
     }
@@ -105,7 +85,7 @@ __device__ __forceinline__ int iva_solve(double2& m, double2& rhs, int r, int c)
 template <typename R>
 __global__ __launch_bounds__(IVA_THREADS) void iva_check_kernel(const void* X, const double2* W0, double2* W, int* status, long nbins,
                                                                  int D, int F, int T) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long chan_stride = (long)F * T;
   for (long bin = (long)blockIdx.x * IVA_WAVES + wv; bin < nbins; bin += (long)gridDim.x * IVA_WAVES) {
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_check_kernel(const void* X, c
       for (int t = lane; t < T; t += kWave) {
         const C v = xg[d * chan_stride + t];
         const double re = (double)v.x, im = (double)v.y;
-        if (!iva_finite(re) || !iva_finite(im)) bad = 1;
+        if (!is_finite(re) || !is_finite(im)) bad = 1;
         if (re != 0.0 || im != 0.0) any = 1;
       }
     bad = wave_or(bad);
@@ -136,7 +116,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_check_kernel(const void* X, c
 template <typename R, int D>
 __global__ __launch_bounds__(IVA_THREADS) void iva_cov_kernel(const void* X, const double* Phi, const int* status, double2* V,
                                                               long nbins, int F, int T, long row_stride, long bin_stride) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   constexpr int K = D * D;                             // D real diagonal sums and D (D - 1) / 2 complex ones below it
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long chan_stride = (long)F * T;
@@ -225,19 +205,19 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_solve_kernel(const double2* V
       double2 m = zero;                                // (W V_k)[r][c], j rising from the first product
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        const double2 wrj = iva_shfl(w, 8 * r + j);
-        const double2 q = iva_mul(wrj, V[in ? j * D + c : 0]);
+        const double2 wrj = cshfl(w, 8 * r + j);
+        const double2 q = cmul(wrj, V[in ? j * D + c : 0]);
         m = j == 0 ? q : make_double2(m.x + q.x, m.y + q.y);
       }
       if (!in) m = zero;
       double2 sol = make_double2(r == k ? 1.0 : 0.0, 0.0);            // e_k in every column
       fail = iva_solve<D>(m, sol, r, c);               // the lanes of row r hold w_r
-      const double2 wc = iva_shfl(sol, 8 * c);
-      const double2 term = in ? iva_mul(V[at], wc) : zero;
+      const double2 wc = cshfl(sol, 8 * c);
+      const double2 term = in ? cmul(V[at], wc) : zero;
       double2 vw = zero;                               // (V_k w)[r], c rising from the first product
 #pragma unroll
       for (int cc = 0; cc < D; ++cc) {
-        const double2 q = iva_shfl(term, 8 * r + cc);
+        const double2 q = cshfl(term, 8 * r + cc);
         vw = cc == 0 ? q : make_double2(vw.x + q.x, vw.y + q.y);
       }
       const double qr = sol.x * vw.x + sol.y * vw.y;                  // Re(conj(w_r) (V_k w)_r)
@@ -261,7 +241,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_solve_kernel(const double2* V
 template <typename R, int D>
 __global__ __launch_bounds__(IVA_THREADS) void iva_project_kernel(const void* X, double2* W, void* Y, int* status, long nbins, int F,
                                                                   int T, int ref) {
-  typedef typename IvaCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   __shared__ double2 Ws[D * D];
   __shared__ double2 As[D];
   __shared__ int s_pass;
@@ -317,14 +297,14 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_project_kernel(const void* X,
           for (int d = 0; d < D; ++d) x[d] = make_double2((double)v[d].x, (double)v[d].y);
 #pragma unroll
           for (int k = 0; k < KP; ++k) {
-            double2 y = iva_mul(wk[k][0], x[0]);
+            double2 y = cmul(wk[k][0], x[0]);
 #pragma unroll
             for (int d = 1; d < D; ++d) {
-              const double2 q = iva_mul(wk[k][d], x[d]);
+              const double2 q = cmul(wk[k][d], x[d]);
               y.x += q.x;
               y.y += q.y;
             }
-            const double2 img = iva_mul(ak[k], y);
+            const double2 img = cmul(ak[k], y);
             C out;
             out.x = (R)img.x;
             out.y = (R)img.y;
@@ -336,28 +316,5 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_project_kernel(const void* X,
     __syncthreads();                                   // Ws, As and s_pass are free for the next bin
   }
 }
-
-// ----------------------------------------------------------------------------------------------------------------- host side
-inline dim3 iva_grid(long blocks) { return dim3((unsigned)(blocks < IVA_MAX_BLOCKS ? blocks : IVA_MAX_BLOCKS)); }
-
-inline int iva_check_dims(const char* who, int B, int D, int F, int T) {
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 1 && D <= IVA_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 1 <= D <= 8)", who, D);
-  ALVQ_REQUIRE(T >= 1 && T <= IVA_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
-  return ALVQ_OK;
-}
-
-#define IVA_FOR_D(D, CALL)  \
-  switch (D) {              \
-    case 1: CALL(1); break; \
-    case 2: CALL(2); break; \
-    case 3: CALL(3); break; \
-    case 4: CALL(4); break; \
-    case 5: CALL(5); break; \
-    case 6: CALL(6); break; \
-    case 7: CALL(7); break; \
-    default: CALL(8); break; \
-  }
 
 }  // namespace alvq

@@ -25,13 +25,13 @@
 //                       (the widest that divides a row), coalesced over t.
 // Every sum over t is the same: thread i of 256 adds the frames t = i, i + 256, ... rising from +0.0, then
 // block_sum<kSequential, true> (block_reduce.h).  No atomics, no host-side decision between the launches: status is read on
-// the device.  Every grid over bins is capped at PA_MAX_BLOCKS workgroups and strides over the bins beyond, whole workgroups
+// the device.  Every grid over bins is capped at kMaxBlocks workgroups and strides over the bins beyond, whole workgroups
 // at a time.  What the launches cost: DESIGN.md.
 #include <cfloat>
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 #include "assign_search.h"
 
 namespace alvq {
@@ -41,13 +41,9 @@ constexpr int PA_WAVES = PA_THREADS / kWave;
 constexpr int PA_TILE = 64;                // the frames of a workgroup of align_centroid_kernel: a lane each, in every wave
 constexpr int PA_STEPS = 8;                // the bins align_centroid_kernel loads at a time
 constexpr int PA_MAX_K = PM_MAX_K;
-constexpr int PA_MAX_T = 65535;
 constexpr int PA_MAX_ITERATIONS = 256;
-constexpr long PA_MAX_BLOCKS = 1 << 16;
 
 constexpr int PA_BAD_INPUT = 1;            // a non-finite value in the bin, or a perm0 row that is not a permutation
-
-__device__ __forceinline__ bool pa_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // whether p[0..K-1] is a permutation of 0..K-1; an entry out of range is never used as a shift count
 __device__ __forceinline__ bool pa_is_permutation(const int* p, int K) {
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(PA_THREADS) void align_check_kernel(const double* _
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const double x = p[j * row_stride + t];
-        if (!pa_finite(x)) v[K] += 1.0;
+        if (!is_finite(x)) v[K] += 1.0;
         v[j] += x;
       }
     }
@@ -303,23 +299,9 @@ __global__ __launch_bounds__(PA_THREADS) void permute_bins_kernel(const V* __res
 
 using namespace alvq;
 
-static dim3 pa_grid(long blocks) { return dim3((unsigned)(blocks < PA_MAX_BLOCKS ? blocks : PA_MAX_BLOCKS)); }
-
 static bool pa_dims_ok(int B, int K, int F, int T, int min_T) {
-  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && K >= 1 && K <= PA_MAX_K && T >= min_T && T <= PA_MAX_T;
+  return B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX && K >= 1 && K <= PA_MAX_K && T >= min_T && T <= kMaxFrames;
 }
-
-#define PA_FOR_K(K, CALL)   \
-  switch (K) {              \
-    case 1: CALL(1); break; \
-    case 2: CALL(2); break; \
-    case 3: CALL(3); break; \
-    case 4: CALL(4); break; \
-    case 5: CALL(5); break; \
-    case 6: CALL(6); break; \
-    case 7: CALL(7); break; \
-    default: CALL(8); break; \
-  }
 
 extern "C" int64_t alvq_align_workspace_bytes(int B, int K, int F, int T) {
   if (!pa_dims_ok(B, K, F, T, 2)) return -1;
@@ -331,10 +313,9 @@ extern "C" int alvq_align_permutations_f64(const double* profile, const int* per
                                            int* status, void* workspace, int B, int K, int F, int T, int iterations, void* stream) {
   const char* who = "alvq_align_permutations_f64";
   ALVQ_REQUIRE(profile && perm && score && changed && status && workspace, ALVQ_EINVAL, "%s: null pointer", who);
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
+  ALVQ_TRY(check_bins(who, B, F));
   ALVQ_REQUIRE(K >= 1 && K <= PA_MAX_K, ALVQ_EINVAL, "%s: K=%d (need 1 <= K <= 8)", who, K);
-  ALVQ_REQUIRE(T >= 2 && T <= PA_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 2 <= T <= 65535)", who, T);
+  ALVQ_TRY(check_frames(who, T, 2));
   ALVQ_REQUIRE(iterations >= 1 && iterations <= PA_MAX_ITERATIONS, ALVQ_EINVAL, "%s: iterations=%d (need 1 <= iterations <= 256)",
                who, iterations);
   const long nbins = (long)B * F;
@@ -342,11 +323,11 @@ extern "C" int alvq_align_permutations_f64(const double* profile, const int* per
   double2* rows = (double2*)workspace;
   double* cent = (double*)((char*)workspace + (int64_t)16 * B * K * F);
   int* flags = (int*)(cent + (long)B * K * T);
-  const dim3 bins = pa_grid(nbins);
+  const dim3 bins = capped_grid(nbins);
 #define PA_CALL(N)                                                                                                           \
   hipLaunchKernelGGL((align_check_kernel<N>), bins, dim3(PA_THREADS), 0, s, profile, perm0, perm, score, status, rows, flags, \
                      nbins, F, T)
-  PA_FOR_K(K, PA_CALL)
+  ALVQ_FOR_1_TO_8(K, PA_CALL)
 #undef PA_CALL
   const dim3 tiles((unsigned)((T + PA_TILE - 1) / PA_TILE), (unsigned)B);
   for (int it = 0; it < iterations; ++it) {
@@ -356,7 +337,7 @@ extern "C" int alvq_align_permutations_f64(const double* profile, const int* per
 #define PA_CALL(N)                                                                                                        \
   hipLaunchKernelGGL((align_score_kernel<N>), bins, dim3(PA_THREADS), 0, s, profile, (const double*)cent, (const int*)status, \
                      (const double2*)rows, perm, score, flags, nbins, F, T)
-    PA_FOR_K(K, PA_CALL)
+    ALVQ_FOR_1_TO_8(K, PA_CALL)
 #undef PA_CALL
   }
   hipLaunchKernelGGL(align_changed_kernel, dim3((unsigned)B), dim3(PA_THREADS), 0, s, (const int*)flags, changed, F);
@@ -365,7 +346,7 @@ extern "C" int alvq_align_permutations_f64(const double* profile, const int* per
 
 template <typename V>
 static void permute_bins_start(const void* x, const int* perm, void* out, long nbins, int K, int F, int Tv, hipStream_t s) {
-  hipLaunchKernelGGL((permute_bins_kernel<V>), pa_grid(nbins), dim3(PA_THREADS), 0, s, (const V*)x, perm, (V*)out, nbins, K, F, Tv);
+  hipLaunchKernelGGL((permute_bins_kernel<V>), capped_grid(nbins), dim3(PA_THREADS), 0, s, (const V*)x, perm, (V*)out, nbins, K, F, Tv);
 }
 
 extern "C" int alvq_permute_bins(const void* x, const int* perm, void* out, int B, int K, int F, int T, int elem_bytes, void* stream) {

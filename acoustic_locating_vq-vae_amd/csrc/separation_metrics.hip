@@ -21,7 +21,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 #include "assign_search.h"
 
 namespace alvq {
@@ -35,8 +35,6 @@ constexpr int PM_BAD_INPUT = 1;            // a reference of zero or non-finite 
 constexpr int PM_BAD_SOLVE = 2;            // a pivot that is 0 or not finite
 constexpr int PM_BAD_PERM = 3;             // a perm row that is not an injection into 0..J-1
 constexpr int PM_NONE_VALID = 1;           // assign: every injection's score was NaN
-
-__device__ __forceinline__ bool pm_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // 10 log10(num / den) under the rules of si_sdr_kernel: NaN for a NaN energy, +inf for a denominator of 0
 __device__ __forceinline__ double pm_ratio_db(double num, double den) {
@@ -208,7 +206,7 @@ __global__ __launch_bounds__(PM_THREADS) void si_bss_eval_kernel(const T* __rest
     for (int p = 0; p < K; ++p) {
       v[p] += (double)s[(long)p * n + t];
       const double x = (double)est[(long)pi[p] * n + t];
-      if (!pm_finite(x)) v[K + 1] += 1.0;
+      if (!is_finite(x)) v[K + 1] += 1.0;
       if (p == i) v[K] += x;
     }
   }
@@ -321,11 +319,6 @@ static int pm_check_dims(const char* who, int B, int K, int J, int n) {
   return ALVQ_OK;
 }
 
-template <typename T, int J>
-static void pairwise_si_sdr_start(const T* references, const T* estimates, double* table, int B, int K, int n, hipStream_t s) {
-  hipLaunchKernelGGL((pairwise_si_sdr_kernel<T, J>), dim3(K, B), dim3(PM_THREADS), 0, s, references, estimates, table, K, n);
-}
-
 template <typename T>
 static int pairwise_si_sdr_launch(const char* who, const T* references, const T* estimates, double* table, int B, int K, int J,
                                   int n, void* stream) {
@@ -333,16 +326,10 @@ static int pairwise_si_sdr_launch(const char* who, const T* references, const T*
   const int rc = pm_check_dims(who, B, K, J, n);
   if (rc != ALVQ_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  switch (J) {
-    case 1: pairwise_si_sdr_start<T, 1>(references, estimates, table, B, K, n, s); break;
-    case 2: pairwise_si_sdr_start<T, 2>(references, estimates, table, B, K, n, s); break;
-    case 3: pairwise_si_sdr_start<T, 3>(references, estimates, table, B, K, n, s); break;
-    case 4: pairwise_si_sdr_start<T, 4>(references, estimates, table, B, K, n, s); break;
-    case 5: pairwise_si_sdr_start<T, 5>(references, estimates, table, B, K, n, s); break;
-    case 6: pairwise_si_sdr_start<T, 6>(references, estimates, table, B, K, n, s); break;
-    case 7: pairwise_si_sdr_start<T, 7>(references, estimates, table, B, K, n, s); break;
-    default: pairwise_si_sdr_start<T, 8>(references, estimates, table, B, K, n, s); break;
-  }
+#define PM_CALL(N) \
+  hipLaunchKernelGGL((pairwise_si_sdr_kernel<T, N>), dim3(K, B), dim3(PM_THREADS), 0, s, references, estimates, table, K, n)
+  ALVQ_FOR_1_TO_8(J, PM_CALL)
+#undef PM_CALL
   return check_launch(who);
 }
 
@@ -367,13 +354,6 @@ extern "C" int alvq_assign_f64(const double* table, int* perm, double* total, in
   return check_launch(who);
 }
 
-template <typename T, int K>
-static void si_bss_eval_start(const T* references, const T* estimates, const int* perm, double* sdr, double* sir, double* sar,
-                              int* status, int B, int J, int n, hipStream_t s) {
-  hipLaunchKernelGGL((si_bss_eval_kernel<T, K>), dim3(K, B), dim3(PM_THREADS), 0, s, references, estimates, perm, sdr, sir, sar,
-                     status, J, n);
-}
-
 template <typename T>
 static int si_bss_eval_launch(const char* who, const T* references, const T* estimates, const int* perm, double* sdr, double* sir,
                               double* sar, int* status, int B, int K, int J, int n, void* stream) {
@@ -382,16 +362,11 @@ static int si_bss_eval_launch(const char* who, const T* references, const T* est
   if (rc != ALVQ_OK) return rc;
   ALVQ_REQUIRE(K <= J, ALVQ_EINVAL, "%s: K=%d J=%d (need K <= J: every reference takes an estimate of its own)", who, K, J);
   hipStream_t s = (hipStream_t)stream;
-  switch (K) {
-    case 1: si_bss_eval_start<T, 1>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 2: si_bss_eval_start<T, 2>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 3: si_bss_eval_start<T, 3>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 4: si_bss_eval_start<T, 4>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 5: si_bss_eval_start<T, 5>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 6: si_bss_eval_start<T, 6>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    case 7: si_bss_eval_start<T, 7>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-    default: si_bss_eval_start<T, 8>(references, estimates, perm, sdr, sir, sar, status, B, J, n, s); break;
-  }
+#define PM_CALL(N)                                                                                                          \
+  hipLaunchKernelGGL((si_bss_eval_kernel<T, N>), dim3(N, B), dim3(PM_THREADS), 0, s, references, estimates, perm, sdr, sir, sar, \
+                     status, J, n)
+  ALVQ_FOR_1_TO_8(K, PM_CALL)
+#undef PM_CALL
   return check_launch(who);
 }
 

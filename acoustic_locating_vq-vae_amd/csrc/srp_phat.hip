@@ -34,14 +34,12 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 
 namespace alvq {
 
 constexpr int PHAT_THREADS = 256;
 constexpr int PHAT_WAVES = PHAT_THREADS / kWave;
-constexpr int PHAT_MAX_D = 8;
-constexpr int PHAT_MAX_T = 65535;
 constexpr int PHAT_MAX_NFFT = 1 << 24;
 constexpr int PHAT_LDS_LIMIT = 160 * 1024 - 256;     // dynamic LDS: the 160 KiB less the static reduction scratch
 constexpr int SRP_THREADS = 512;
@@ -51,15 +49,6 @@ constexpr int SRP_ANCHOR = 8;          // bins between two sincospi anchors of t
 constexpr int SRP_BAD_SPECTRUM = 1;    // a non-finite psi inside the band
 constexpr int SRP_SILENT = 2;          // every psi inside the band is 0
 constexpr int SRP_BAD_GEOMETRY = 4;    // a non-finite microphone or candidate coordinate
-
-struct OpOr {
-  static __device__ __forceinline__ int f(int a, int b) { return a | b; }
-  static __device__ __forceinline__ int wave(int v) { return wave_or(v); }
-};
-
-template <typename R> struct PhatCplx;
-template <> struct PhatCplx<float> { typedef float2 type; };
-template <> struct PhatCplx<double> { typedef double2 type; };
 
 __host__ __device__ inline int phat_pairs(int D) { return D * (D - 1) / 2; }
 
@@ -78,7 +67,7 @@ struct PhatArgs {
 
 template <typename R, bool ROW_LDS>
 __global__ __launch_bounds__(PHAT_THREADS) void phat_kernel(PhatArgs a) {
-  typedef typename PhatCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   extern __shared__ __attribute__((aligned(16))) unsigned char phat_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int D = a.D, T = a.T, P = phat_pairs(D);
@@ -311,9 +300,8 @@ __global__ __launch_bounds__(PHAT_THREADS) void srp_argmax_kernel(const double* 
 using namespace alvq;
 
 static int phat_check_band(const char* who, int B, int D, int F, int f_lo, int f_hi) {
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 2 && D <= PHAT_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 2 <= D <= 8)", who, D);
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_TRY(check_mics(who, D, 2));
   ALVQ_REQUIRE(f_lo >= 0 && f_lo <= f_hi && f_hi < F, ALVQ_EINVAL, "%s: band %d..%d (need 0 <= f_lo <= f_hi < F = %d)", who, f_lo,
                f_hi, F);
   return ALVQ_OK;
@@ -332,7 +320,7 @@ static int phat_launch(const char* who, const R* X, double* psi, int* status, in
   ALVQ_REQUIRE(X && psi && status, ALVQ_EINVAL, "%s: null pointer", who);
   const int rc = phat_check_band(who, B, D, F, f_lo, f_hi);
   if (rc != ALVQ_OK) return rc;
-  ALVQ_REQUIRE(T >= 1 && T <= PHAT_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
+  ALVQ_TRY(check_frames(who, T));
   const size_t row_bytes = 16 * (size_t)D * T;
   const bool row_lds = option(OPT_PHAT_LDS) != 0 && row_bytes <= (size_t)PHAT_LDS_LIMIT;
   static DeviceOnce attr;
@@ -409,15 +397,9 @@ extern "C" int alvq_srp_phat_f64(const double* psi, const double* mics, const do
   const SrpArgs args{(const double2*)psi, mics, cand, map, status, B, G, F, n_fft, f_lo, f_hi, (long)mics_stride, (long)cand_stride,
                      fs / (double)n_fft, c, (double)P * phat_band_weight(n_fft, f_lo, f_hi)};
   const dim3 grid((unsigned)(((long)G + SRP_THREADS - 1) / SRP_THREADS), (unsigned)B);
-  switch (D) {
-    case 2: srp_map_launch<2>(args, psi_lds, lds, grid, s); break;
-    case 3: srp_map_launch<3>(args, psi_lds, lds, grid, s); break;
-    case 4: srp_map_launch<4>(args, psi_lds, lds, grid, s); break;
-    case 5: srp_map_launch<5>(args, psi_lds, lds, grid, s); break;
-    case 6: srp_map_launch<6>(args, psi_lds, lds, grid, s); break;
-    case 7: srp_map_launch<7>(args, psi_lds, lds, grid, s); break;
-    default: srp_map_launch<8>(args, psi_lds, lds, grid, s); break;
-  }
+#define SRP_CALL(N) srp_map_launch<N>(args, psi_lds, lds, grid, s)
+  ALVQ_FOR_2_TO_8(D, SRP_CALL)
+#undef SRP_CALL
   hipLaunchKernelGGL(srp_argmax_kernel, dim3(B), dim3(PHAT_THREADS), 0, s, (const double*)map, (const int*)status, best, G);
   return check_launch(who);
 }

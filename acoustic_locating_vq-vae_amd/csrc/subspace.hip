@@ -6,7 +6,7 @@
 // sub_eigh_kernel      a wave a matrix, four matrices a workgroup, no LDS and no barrier: csrc/herm_eig.h does the work.  The
 //                      lane 8 r + c reads entry (max(r, c), min(r, c)) itself (the upper triangle as the conjugate of the
 //                      lower, the diagonal's real part alone) and stores entry (r, rank(c)) of V: columns land in ascending
-//                      order of their eigenvalues.  The grid is capped at SUB_MAX_BLOCKS workgroups; a wave strides over the
+//                      order of their eigenvalues.  The grid is capped at kMaxBlocks workgroups; a wave strides over the
 //                      matrices beyond, whole.
 // music_status_kernel  one workgroup an item: the OR over the item's band of V and lambda (a non-finite value; a non-zero
 //                      eigenvalue) and over its coordinates.  No atomics: wave_or, then the waves through LDS.
@@ -24,14 +24,13 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 #include "herm_eig.h"
 
 namespace alvq {
 
 constexpr int SUB_THREADS = 256;
 constexpr int SUB_WAVES = SUB_THREADS / kWave;
-constexpr long SUB_MAX_BLOCKS = 1 << 16;
 constexpr int SUB_ANCHOR = 8;          // bins between two sincospi anchors of the rotation recurrence (srp_phat's)
 constexpr int SUB_MAX_NFFT = 1 << 24;
 
@@ -39,11 +38,6 @@ constexpr int SUB_MAX_NFFT = 1 << 24;
 constexpr int MUSIC_BAD_SPECTRUM = 1;  // a non-finite eigenvector or eigenvalue inside the band
 constexpr int MUSIC_SILENT = 2;        // no counted bin: every eigenvalue inside the band is 0
 constexpr int MUSIC_BAD_GEOMETRY = 4;  // a non-finite microphone or candidate coordinate
-
-struct SubOpOr {
-  static __device__ __forceinline__ int f(int a, int b) { return a | b; }
-  static __device__ __forceinline__ int wave(int v) { return wave_or(v); }
-};
 
 // --------------------------------------------------------------------------------------------------------- eigendecomposition
 __global__ __launch_bounds__(SUB_THREADS) void sub_eigh_kernel(const double2* A, double* lam, double2* V, int* status, long n, int D) {
@@ -83,21 +77,21 @@ __global__ __launch_bounds__(SUB_THREADS) void music_status_kernel(const double2
   const double2* Vg = V + ((long)b * F + f_lo) * (D * D);
   for (long e = tid; e < nb * D * D; e += SUB_THREADS) {
     const double2 x = Vg[e];
-    if (!he_finite(x.x) || !he_finite(x.y)) seen |= 1;
+    if (!is_finite(x.x) || !is_finite(x.y)) seen |= 1;
   }
   const double* lg = lam + ((long)b * F + f_lo) * D;
   for (long e = tid; e < nb * D; e += SUB_THREADS) {
     const double x = lg[e];
-    if (!he_finite(x)) seen |= 1;
+    if (!is_finite(x)) seen |= 1;
     if (x != 0.0) seen |= 2;
   }
   const double* m = mics + (long)b * mics_stride;
   for (int e = tid; e < 3 * D; e += SUB_THREADS)
-    if (!he_finite(m[e])) seen |= 4;
+    if (!is_finite(m[e])) seen |= 4;
   const double* q = cand + (long)b * cand_stride;
   for (long e = tid; e < 3L * G; e += SUB_THREADS)
-    if (!he_finite(q[e])) seen |= 4;
-  seen = block_sum<kSequential, false, SubOpOr>(seen, s_flag);
+    if (!is_finite(q[e])) seen |= 4;
+  seen = block_sum<kSequential, false, OpOr>(seen, s_flag);
   if (tid == 0)
     status[b] = ((seen & 1) ? MUSIC_BAD_SPECTRUM : 0) | ((seen & 2) ? 0 : MUSIC_SILENT) | ((seen & 4) ? MUSIC_BAD_GEOMETRY : 0);
 }
@@ -234,9 +228,8 @@ extern "C" int alvq_eigh_f64(const double* A, double* lam, double* V, int* statu
   ALVQ_REQUIRE(A && lam && V && status, ALVQ_EINVAL, "%s: null pointer", who);
   ALVQ_REQUIRE(n_matrices >= 1 && n_matrices <= INT_MAX, ALVQ_EINVAL, "%s: n_matrices=%ld (need 1 <= n_matrices <= 2^31 - 1)", who,
                (long)n_matrices);
-  ALVQ_REQUIRE(D >= 1 && D <= HE_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 1 <= D <= 8)", who, D);
-  const long blocks = ((long)n_matrices + SUB_WAVES - 1) / SUB_WAVES;
-  hipLaunchKernelGGL(sub_eigh_kernel, dim3((unsigned)(blocks < SUB_MAX_BLOCKS ? blocks : SUB_MAX_BLOCKS)), dim3(SUB_THREADS), 0,
+  ALVQ_TRY(check_mics(who, D));
+  hipLaunchKernelGGL(sub_eigh_kernel, capped_grid(((long)n_matrices + SUB_WAVES - 1) / SUB_WAVES), dim3(SUB_THREADS), 0,
                      (hipStream_t)stream, (const double2*)A, lam, (double2*)V, status, (long)n_matrices, D);
   return check_launch(who);
 }
@@ -248,7 +241,7 @@ extern "C" int alvq_music_f64(const double* V, const double* lam, const double* 
   ALVQ_REQUIRE(V && lam && mics && cand && null && best && status, ALVQ_EINVAL, "%s: null pointer", who);
   ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && F <= SUB_MAX_NFFT && (long)B * F <= INT_MAX, ALVQ_EINVAL,
                "%s: B=%d F=%d (need 1 <= B <= 65535, 1 <= F <= 2^24, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 2 && D <= HE_MAX_D, ALVQ_EINVAL, "%s: D=%d (need 2 <= D <= 8)", who, D);
+  ALVQ_TRY(check_mics(who, D, 2));
   ALVQ_REQUIRE(K >= 1 && K <= D - 1, ALVQ_EINVAL, "%s: K=%d (need 1 <= K <= D - 1 = %d)", who, K, D - 1);
   ALVQ_REQUIRE(G >= 1 && (long)B * G <= INT_MAX, ALVQ_EINVAL, "%s: G=%d (need G >= 1, B G <= 2^31 - 1)", who, G);
   ALVQ_REQUIRE(n_fft >= 2 && n_fft <= SUB_MAX_NFFT, ALVQ_EINVAL, "%s: n_fft=%d (need 2 <= n_fft <= 2^24)", who, n_fft);
@@ -263,15 +256,9 @@ extern "C" int alvq_music_f64(const double* V, const double* lam, const double* 
   const MusicArgs args{(const double2*)V, lam, mics, cand, null, status, G, F, K, f_lo, f_hi, mics_stride, cand_stride,
                        fs / (double)n_fft, c};
   const dim3 grid((unsigned)(((long)G + SUB_THREADS - 1) / SUB_THREADS), (unsigned)B);
-  switch (D) {
-    case 2: hipLaunchKernelGGL(music_map_kernel<2>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    case 3: hipLaunchKernelGGL(music_map_kernel<3>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    case 4: hipLaunchKernelGGL(music_map_kernel<4>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    case 5: hipLaunchKernelGGL(music_map_kernel<5>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    case 6: hipLaunchKernelGGL(music_map_kernel<6>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    case 7: hipLaunchKernelGGL(music_map_kernel<7>, grid, dim3(SUB_THREADS), 0, s, args); break;
-    default: hipLaunchKernelGGL(music_map_kernel<8>, grid, dim3(SUB_THREADS), 0, s, args); break;
-  }
+#define SUB_CALL(N) hipLaunchKernelGGL(music_map_kernel<N>, grid, dim3(SUB_THREADS), 0, s, args)
+  ALVQ_FOR_2_TO_8(D, SUB_CALL)
+#undef SUB_CALL
   hipLaunchKernelGGL(music_argmin_kernel, dim3(B), dim3(SUB_THREADS), 0, s, (const double*)null, (const int*)status, best, G);
   return check_launch(who);
 }

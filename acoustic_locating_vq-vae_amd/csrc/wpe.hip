@@ -26,15 +26,13 @@
 #include <climits>
 #include <cmath>
 
-#include "alvq_common.h"
+#include "array_wave.h"
 
 namespace alvq {
 
 constexpr int WPE_THREADS = 256;
 constexpr int WPE_WAVES = WPE_THREADS / kWave;
 constexpr int WPE_MAX_M = 64;
-constexpr int WPE_MAX_D = 8;
-constexpr int WPE_MAX_T = 65535;
 constexpr int WPE_LDS_LIMIT = 160 * 1024 - 256;      // dynamic LDS: the 160 KiB less the static reduction scratch
 
 // status values of alvq_wpe_*
@@ -59,20 +57,9 @@ inline bool wpe_row_in_lds(int D, int T, int taps) {
   return wpe_matrix_doubles(D, taps) * 8 + 16L * (D + 1) * T <= WPE_LDS_LIMIT;
 }
 
-template <typename R> struct WpeCplx;
-template <> struct WpeCplx<float> { typedef float2 type; };
-template <> struct WpeCplx<double> { typedef double2 type; };
-
-__device__ __forceinline__ double2 wpe_mul(double2 a, double2 b) {          // a b
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 wpe_mul_conj(double2 a, double2 b) {     // a conj(b); imaginary part exactly 0 for a == b
-  return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
-}
-
 template <typename R, bool ROW_LDS>
 __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
-  typedef typename WpeCplx<R>::type C;
+  typedef typename Cplx<R>::type C;
   extern __shared__ __attribute__((aligned(16))) unsigned char wpe_smem[];
   __shared__ double s_max[WPE_WAVES];
   __shared__ int s_flag[WPE_WAVES];
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
       const int dc = c % D, sc = a.delay + c / D;
       double2 acc = make_double2(0.0, 0.0);
       for (int t = (sr > sc ? sr : sc) + lane; t < T; t += kWave) {
-        const double2 p = wpe_mul_conj(ldx(dr, t - sr), ldx(dc, t - sc));
+        const double2 p = cmul_conj(ldx(dr, t - sr), ldx(dc, t - sc));
         const double wt = w[t];
         acc.x += p.x * wt;
         acc.y += p.y * wt;
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
       for (int e = tid; e < n; e += WPE_THREADS) {
         const int r = k + 1 + e / wd, c = k + 1 + e % wd;
         if (c > r) continue;
-        const double2 p = wpe_mul_conj(A[r * M + k], A[c * M + k]);
+        const double2 p = cmul_conj(A[r * M + k], A[c * M + k]);
         double2 v = A[r * M + c];
         v.x -= p.x;
         v.y -= p.y;
@@ -204,7 +191,7 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
       __syncthreads();
       for (int e = tid; e < D * k; e += WPE_THREADS) {
         const int d = e / k, j = e - d * k;
-        const double2 p = wpe_mul(A[(M + d) * M + k], A[k * M + j]);
+        const double2 p = cmul(A[(M + d) * M + k], A[k * M + j]);
         double2 v = A[(M + d) * M + j];
         v.x -= p.x;
         v.y -= p.y;
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
         const int kmax = t - a.delay + 1 < a.taps ? t - a.delay + 1 : a.taps;        // taps whose frame exists
         for (int k = 0; k < kmax; ++k)
           for (int d2 = 0; d2 < D; ++d2) {
-            const double2 p = wpe_mul(A[(M + d) * M + k * D + d2], ldx(d2, t - a.delay - k));
+            const double2 p = cmul(A[(M + d) * M + k * D + d2], ldx(d2, t - a.delay - k));
             y.x -= p.x;
             y.y -= p.y;
           }
@@ -250,18 +237,16 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(WpeArgs a) {
 using namespace alvq;
 
 static int wpe_check_dims(const char* who, int B, int D, int F, int T, int taps) {
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && (long)B * F <= INT_MAX, ALVQ_EINVAL,
-               "%s: B=%d F=%d (need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1)", who, B, F);
-  ALVQ_REQUIRE(D >= 1 && D <= WPE_MAX_D && taps >= 1 && (long)D * taps <= WPE_MAX_M, ALVQ_EINVAL,
+  ALVQ_TRY(check_bins(who, B, F));
+  ALVQ_REQUIRE(D >= 1 && D <= kMaxMics && taps >= 1 && (long)D * taps <= WPE_MAX_M, ALVQ_EINVAL,
                "%s: D=%d taps=%d (need 1 <= D <= 8, taps >= 1, D taps <= 64)", who, D, taps);
-  ALVQ_REQUIRE(T >= 1 && T <= WPE_MAX_T, ALVQ_EINVAL, "%s: T=%d (need 1 <= T <= 65535)", who, T);
-  return ALVQ_OK;
+  return check_frames(who, T);
 }
 
 // q and w of every bin (2 T doubles each) where a bin's rows do not fit in LDS; nothing otherwise
 extern "C" int64_t alvq_wpe_workspace_bytes(int B, int D, int F, int T, int taps) {
-  if (B < 1 || B > 65535 || F < 1 || (long)B * F > INT_MAX || D < 1 || D > WPE_MAX_D || taps < 1 || (long)D * taps > WPE_MAX_M ||
-      T < 1 || T > WPE_MAX_T)
+  if (B < 1 || B > 65535 || F < 1 || (long)B * F > INT_MAX || D < 1 || D > kMaxMics || taps < 1 || (long)D * taps > WPE_MAX_M ||
+      T < 1 || T > kMaxFrames)
     return -1;
   return wpe_row_in_lds(D, T, taps) ? 0 : (int64_t)B * F * 2 * T * 8;
 }

@@ -8,7 +8,9 @@ dispatch picks: ``python3 tools/ab_bits.py tiles`` repeats the convolution entri
 every forcing of the dispatch options (TILE_FORCINGS), which reaches every instantiation of every forward kernel family.
 ``python3 tools/ab_bits.py reduce`` fingerprints the entry points behind csrc/block_reduce.h's workgroup reductions and scans
 (losses, quantiser, gradient clipping, k-means, EMA codebook, t-SNE, spectrogram statistics, speech metrics, WPE, the layout
-kernels that raise the fp16 range flag) on small seeded inputs."""
+kernels that raise the fp16 range flag) on small seeded inputs.  ``python3 tools/ab_bits.py array`` fingerprints the
+microphone-array families that share csrc/array_wave.h (AuxIVA, ILRMA, cACGMM, SRP-PHAT and MUSIC, beamforming and GEV, WPE,
+separation scoring, permutation alignment) on the cases of tests/helpers/size_sweep_cases.py."""
 import hashlib
 import json
 import os
@@ -168,6 +170,95 @@ def reduce():
     return {"reduce:" + k: v for k, v in out.items()}
 
 
+def array():
+    """The microphone-array families behind csrc/array_wave.h, on the inputs of their own ``tests/helpers/*_ref.py`` builders:
+    every case of size_sweep_cases.py (every compiled D, K, J and L) and beamform_ref.PARITY (both covariance kernels at
+    every D), in complex64 and complex128 where the family takes both; one WPE, one scoring and one alignment case.  Every
+    hash covers the status words."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import numpy as np
+    import align_ref as AR
+    import beamform_ref as BR
+    import cacgmm_ref as CR
+    import ilrma_ref as LR
+    import iva_ref as IR
+    import separation_metrics_ref as MR
+    import size_sweep_cases as S
+    import srp_ref as SR
+    import subspace_ref as UR
+    import wpe_ref as WR
+    from acoustic_locating_vq_vae import beamforming as BF
+    from acoustic_locating_vq_vae import dereverberation as DR
+    from acoustic_locating_vq_vae import localization as LOC
+    from acoustic_locating_vq_vae import separation as SEP
+    from acoustic_locating_vq_vae import speech_metrics as SM
+
+    dev = lambda a: torch.tensor(np.ascontiguousarray(a)).cuda()
+    def leaves(r):                                                    # the tensors of a result, its nested results included
+        if torch.is_tensor(r):
+            return [torch.view_as_real(r.resolve_conj()) if r.is_complex() else r]
+        return [t for part in r for t in leaves(part)] if isinstance(r, tuple) else []
+
+    flat = lambda *results: digest(*leaves(results))
+    precisions = ((np.complex64, "c64"), (np.complex128, "c128"))
+    out = {}
+    for shape in S.IVA:
+        for cdtype, tag in precisions:
+            x = dev(IR.parity_case(shape).X.astype(cdtype))
+            res = {model: flat(SEP.auxiva(x, shape[4], model, ref=shape[1] - 1)) for model in IR.MODELS}
+            res["masks"] = flat(SEP.masks(x))
+            out["auxiva:%s:%s" % (tag, shape[:4])] = res
+    for shape in S.ILRMA_WALK:
+        starts = [dev(a) for a in LR.parity_start(shape)]
+        for cdtype, tag in precisions:
+            x = dev(LR.parity_case(shape).X.astype(cdtype))
+            out["ilrma:%s:%s" % (tag, shape[:5])] = {"all": flat(SEP.ilrma(x, *starts, iterations=shape[5], ref=shape[1] - 1))}
+    for shape in S.CACGMM:
+        c = CR.parity_case(shape)
+        for cdtype, tag in precisions:
+            out["cacgmm:%s:%s" % (tag, shape[:5])] = {"all": flat(SEP.cacgmm(dev(c.X.astype(cdtype)), dev(c.init), shape[5]))}
+    for shape in S.SRP:
+        B, D, T, G, f_lo, f_hi, n_fft = shape
+        c = SR.parity_case(shape)
+        mics, cand = dev(c.mics), dev(c.cand)
+        for cdtype, tag in precisions:
+            x = dev(c.X.astype(cdtype))
+            res = {"psi": flat(LOC.cross_spectra(x, band=(f_lo, f_hi))),
+                   "srp": flat(LOC.srp_phat(x, mics, cand, fs=SR.FS, n_fft=n_fft, c=SR.C, band=(f_lo, f_hi))),
+                   "gcc": flat(LOC.gcc_phat(x, min(8, n_fft // 2), band=(f_lo, f_hi), n_fft=n_fft))}
+            for K in UR.music_orders(D):
+                res["music K=%d" % K] = flat(LOC.music(x, mics, cand, K, n_fft=n_fft, band=(f_lo, f_hi)))
+            out["srp:%s:%s" % (tag, shape)] = res
+    for shape in S.BEAMFORM + BR.PARITY:
+        B, D, F, T, loading = shape
+        c = BR.parity_case(shape)
+        A, noise, speech = dev(c.A), dev(c.masks["runs"]), dev(c.masks["uniform"])
+        for cdtype, tag in precisions:
+            x = dev(c.X.astype(cdtype))
+            cov_n, cov_s, cov = (BF.spatial_covariance(x, m) for m in (noise, speech, None))
+            w = BF.weights("mvdr", cov_n.cov, A, loading=loading)
+            res = {"cov": flat(cov_n, cov_s, cov), "das": flat(BF.weights("das", steering=A)), "mvdr": flat(w),
+                   "souden": flat(BF.weights("souden", cov_n.cov, speech_cov=cov_s.cov, ref=D - 1, loading=loading)),
+                   "apply": flat(BF.apply(x, w.w))}
+            for ref in sorted({0, D - 1}):
+                res["gev ref %d" % ref] = flat(BF.gev(x, noise, speech, ref=ref, loading=loading))
+            out["beamform:%s:%s" % (tag, shape[:4])] = res
+    B, D, F, T, taps, delay = 2, 2, 3, 200, 4, 2
+    for cdtype, tag in precisions:
+        x = dev(WR.case(B, D, F, T, taps, delay, 0).X.astype(cdtype))
+        out["wpe:%s:%s" % (tag, (B, D, F, T, taps))] = {"all": flat(DR.wpe(x, taps, delay, 3, 0))}
+    shape = S.SCORING[3]                                              # (K, J, n) = (4, 7, 257)
+    c = MR.case(shape)
+    for dtype, tag in ((np.float32, "f32"), (np.float64, "f64")):
+        s, e = dev(c.references.astype(dtype)), dev(c.estimates.astype(dtype))
+        out["scoring:%s:%s" % (tag, shape)] = {"table": flat(SM.pairwise_si_sdr(s, e)), "pit": flat(SM.pit_si_sdr(s, e)),
+                                               "bss_eval": flat(SM.si_bss_eval(s, e))}
+    shape = S.ALIGN[6]                                                # K = 7: a thread of the search takes more than one trip
+    p = dev(AR.parity_case(shape).P)
+    out["align:%s" % (shape[:4],)] = {str(n): flat(SEP.align_permutations(p, n)) for n in (1, 3)}
+    return {"array:" + k: v for k, v in out.items()}
+
+
 def main():
     modes = sys.argv[1:] or ["f16mx", "bf16", "bf16x3", "f16"]
     out = dsp() if "dsp" in modes else {}
@@ -175,7 +266,9 @@ def main():
         out.update(tiles())
     if "reduce" in modes:
         out.update(reduce())
-    modes = [m for m in modes if m not in ("dsp", "tiles", "reduce")]
+    if "array" in modes:
+        out.update(array())
+    modes = [m for m in modes if m not in ("dsp", "tiles", "reduce", "array")]
     shapes = [(2, 7, 16, 13, 3), (3, 72, 136, 95, 1), (2, 201, 1024, 500, 3), (2, 1024, 128, 500, 3), (2, 1024, 1024, 201, 1),
               (5, 130, 130, 129, 3), (4, 1024, 1024, 500, 1), (4, 1024, 1024, 500, 3), (3, 1024, 201, 500, 3), (2, 500, 1024, 201, 3)]
     for mode in modes:
