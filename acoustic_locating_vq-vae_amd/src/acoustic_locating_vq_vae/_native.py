@@ -28,7 +28,13 @@ _i32 = ctypes.c_int
 _i64 = ctypes.c_int64
 _f32 = ctypes.c_float
 
-_SIGNATURES = {
+def _signatures(table):
+    """``alvq_<stem>_f32|f64`` stands for two entry points of one signature, ``alvq_<stem>_f32`` and ``alvq_<stem>_f64``."""
+    return {name: sig for key, sig in table.items()
+            for name in ([key[:-7] + "f32", key[:-7] + "f64"] if key.endswith("f32|f64") else [key])}
+
+
+_SIGNATURES = _signatures({
     "alvq_version": (ctypes.c_char_p, []),
     "alvq_last_error": (ctypes.c_char_p, []),
     "alvq_set_option": (_i32, [ctypes.c_char_p, _i64]),
@@ -58,10 +64,8 @@ _SIGNATURES = {
     "alvq_adam_dev_f32": (_i32, [_c_void_p] * 4 + [_i64, _c_void_p, _f32, _f32, _f32, _c_void_p, _c_void_p]),
     "alvq_adam_advance_f32": (_i32, [_c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_void_p, _c_void_p]),
     "alvq_range_flag_to_slot": (_i32, [_c_void_p, _c_void_p]),
-    "alvq_stft_power_f32": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
-    "alvq_stft_power_f64": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
-    "alvq_stft_complex_f32": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
-    "alvq_stft_complex_f64": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
+    "alvq_stft_power_f32|f64": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
+    "alvq_stft_complex_f32|f64": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
     "alvq_fir_same_f64": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _c_void_p]),
     "alvq_spec_rir_wiener_f64": (_i32, [_c_void_p] * 7 + [_i32, _i32, _i32, _c_void_p]),
     "alvq_rows_to_nlc": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p]),
@@ -113,59 +117,42 @@ _SIGNATURES = {
     "alvq_indices_to_i32": (_i32, [_c_void_p] * 3 + [_i64, _i32, _c_void_p]),
     "alvq_embedding_bag_fwd_f32": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p] * 2),
     "alvq_embedding_bag_bwd_f32": (_i32, [_c_void_p] * 4 + [_i32] * 5 + [_c_void_p] * 2),
-    "alvq_istft_f32": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
-    "alvq_istft_f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_istft_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
     "alvq_griffin_lim_workspace_bytes": (_i64, [_i32] * 4),
-    "alvq_griffin_lim_f32": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
-    "alvq_griffin_lim_f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_griffin_lim_f32|f64": (_i32, [_c_void_p] * 4 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_rir_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [ctypes.c_double] * 3 + [_c_void_p] + [ctypes.c_double] * 2
                      + [_i32] * 2 + [_c_void_p]),
     "alvq_rir_rooms_f64": (_i32, [_c_void_p] * 6 + [_i32] * 2 + [ctypes.c_double] * 2 + [_i32] * 2 + [_c_void_p]),
-    "alvq_edc_f32": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
-    "alvq_edc_f64": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
-    "alvq_room_acoustics_f32": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
-    "alvq_room_acoustics_f64": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
-    "alvq_resample_poly_f32": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
-    "alvq_resample_poly_f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
+    "alvq_edc_f32|f64": (_i32, [_c_void_p] * 2 + [_i32] * 2 + [_c_void_p]),
+    "alvq_room_acoustics_f32|f64": (_i32, [_c_void_p] * 4 + [_i32] * 2 + [ctypes.c_double] + [_i32] * 3 + [_c_void_p]),
+    "alvq_resample_poly_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
     "alvq_stoi_workspace_bytes": (_i64, [_i32] * 2),
     "alvq_stoi_f64": (_i32, [_c_void_p] * 8 + [_i32] * 2 + [_c_void_p]),
-    "alvq_si_sdr_f32": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
-    "alvq_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
-    "alvq_lsd_f32": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
-    "alvq_lsd_f64": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
-    "alvq_pairwise_si_sdr_f32": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
-    "alvq_pairwise_si_sdr_f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_si_sdr_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 2 + [_c_void_p]),
+    "alvq_lsd_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_double, _c_void_p]),
+    "alvq_pairwise_si_sdr_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
     "alvq_assign_f64": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
-    "alvq_si_bss_eval_f32": (_i32, [_c_void_p] * 7 + [_i32] * 4 + [_c_void_p]),
-    "alvq_si_bss_eval_f64": (_i32, [_c_void_p] * 7 + [_i32] * 4 + [_c_void_p]),
+    "alvq_si_bss_eval_f32|f64": (_i32, [_c_void_p] * 7 + [_i32] * 4 + [_c_void_p]),
     "alvq_wpe_workspace_bytes": (_i64, [_i32] * 5),
-    "alvq_wpe_f32": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
-    "alvq_wpe_f64": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
-    "alvq_phat_cross_spectra_f32": (_i32, [_c_void_p] * 3 + [_i32] * 6 + [_c_void_p]),
-    "alvq_phat_cross_spectra_f64": (_i32, [_c_void_p] * 3 + [_i32] * 6 + [_c_void_p]),
+    "alvq_wpe_f32|f64": (_i32, [_c_void_p] * 4 + [_i32] * 8 + [ctypes.c_double] * 2 + [_c_void_p]),
+    "alvq_phat_cross_spectra_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 6 + [_c_void_p]),
     "alvq_gcc_phat_f64": (_i32, [_c_void_p] * 2 + [_i32] * 6 + [_c_void_p]),
     "alvq_srp_phat_f64": (_i32, [_c_void_p] * 6 + [_i32] * 3 + [_i64] * 2 + [ctypes.c_double, _i32, ctypes.c_double, _i32, _i32,
                                                                             _c_void_p]),
-    "alvq_spatial_covariance_f32": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
-    "alvq_spatial_covariance_f64": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
+    "alvq_spatial_covariance_f32|f64": (_i32, [_c_void_p] * 4 + [_i32] * 4 + [_c_void_p]),
     "alvq_steering_vectors_f64": (_i32, [_c_void_p] * 4 + [_i32] * 3 + [ctypes.c_double, _i32, ctypes.c_double, _i32, _i32, _c_void_p]),
     "alvq_beamform_weights_f64": (_i32, [_c_void_p] * 5 + [_i32] * 5 + [ctypes.c_double, _c_void_p]),
-    "alvq_beamform_apply_f32": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
-    "alvq_beamform_apply_f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
+    "alvq_beamform_apply_f32|f64": (_i32, [_c_void_p] * 3 + [_i32] * 4 + [_c_void_p]),
     "alvq_beamform_gev_f64": (_i32, [_c_void_p] * 6 + [_i32] * 4 + [ctypes.c_double, _c_void_p]),
     "alvq_eigh_f64": (_i32, [_c_void_p] * 4 + [_i64, _i32, _c_void_p]),
     "alvq_music_f64": (_i32, [_c_void_p] * 7 + [_i32] * 5 + [ctypes.c_double, _i32, ctypes.c_double] + [_i32] * 4 + [_c_void_p]),
     "alvq_auxiva_workspace_bytes": (_i64, [_i32] * 4),
-    "alvq_auxiva_f32": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
-    "alvq_auxiva_f64": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
-    "alvq_separation_masks_f32": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
-    "alvq_separation_masks_f64": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
+    "alvq_auxiva_f32|f64": (_i32, [_c_void_p] * 6 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
+    "alvq_separation_masks_f32|f64": (_i32, [_c_void_p] * 2 + [_i32] * 4 + [_c_void_p]),
     "alvq_ilrma_workspace_bytes": (_i64, [_i32] * 5),
-    "alvq_ilrma_f32": (_i32, [_c_void_p] * 10 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
-    "alvq_ilrma_f64": (_i32, [_c_void_p] * 10 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
+    "alvq_ilrma_f32|f64": (_i32, [_c_void_p] * 10 + [_i32] * 7 + [ctypes.c_double, _c_void_p]),
     "alvq_cacgmm_workspace_bytes": (_i64, [_i32] * 5),
-    "alvq_cacgmm_f32": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
-    "alvq_cacgmm_f64": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
+    "alvq_cacgmm_f32|f64": (_i32, [_c_void_p] * 9 + [_i32] * 6 + [ctypes.c_double, _c_void_p]),
     "alvq_align_workspace_bytes": (_i64, [_i32] * 4),
     "alvq_align_permutations_f64": (_i32, [_c_void_p] * 7 + [_i32] * 5 + [_c_void_p]),
     "alvq_permute_bins": (_i32, [_c_void_p] * 3 + [_i32] * 5 + [_c_void_p]),
@@ -192,7 +179,7 @@ _SIGNATURES = {
                                            _c_void_p, _i64, _i64, ctypes.c_double]),
     "alvq_grad_clip_workspace_bytes": (_i64, [_i64]),
     "alvq_grad_clip_f32": (_i32, [_c_void_p, _i64, _c_void_p, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p]),
-}
+})
 
 EXPORTS = tuple(_SIGNATURES)
 
@@ -791,20 +778,63 @@ def range_flag_to_slot(slot):
     _check(lib().alvq_range_flag_to_slot(_ptr(slot, name="slot"), _stream()), "alvq_range_flag_to_slot")
 
 
+# ----------------------------------------------------------------------------------------------- signal and array wrappers
+def _call(name, *args):
+    """The checked call of the entry point ``name`` on the current stream (its last argument)."""
+    _check(getattr(lib(), name)(*args, _stream()), name)
+
+
 def _call_real(stem, real, *args):
-    """The checked call of ``alvq_<stem>_f32`` or ``alvq_<stem>_f64``, chosen by the real dtype of the call's tensors, on the
-    current stream (the entry points' last argument)."""
+    """``_call`` of ``alvq_<stem>_f32`` or ``alvq_<stem>_f64``, chosen by the real dtype of the call's tensors."""
     sfx = {torch.float32: "f32", torch.float64: "f64"}.get(real)
     if sfx is None:
         raise RuntimeError("alvq_%s: float32 or float64 only (got %s)" % (stem, real))
-    name = "alvq_%s_%s" % (stem, sfx)
-    _check(getattr(lib(), name)(*args, _stream()), name)
+    _call("alvq_%s_%s" % (stem, sfx), *args)
+
+
+def _empty(like, dtype, *shape):
+    """An uninitialised output on like's device."""
+    return torch.empty(shape, device=like.device, dtype=dtype)
+
+
+def _scratch(nbytes, like, bad_dims, reuse=None):
+    """nbytes of scratch on like's device, ``reuse`` where that is large enough.  nbytes is what a ``*_workspace_bytes``
+    entry point returned: negative is its verdict on the dims, raised with the caller's ``bad_dims`` text."""
+    if nbytes < 0:
+        raise RuntimeError(bad_dims)
+    if reuse is not None and reuse.numel() >= nbytes:
+        return reuse
+    return torch.empty((nbytes,), device=like.device, dtype=torch.uint8)
+
+
+def _spec4_real(spec4d, who):
+    """(real dtype, (B, D, F, T), the contiguous interleaved view) of a complex (B, D, F, T) spectrogram."""
+    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
+        raise RuntimeError("%s: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
+                           % (who, spec4d.dtype, tuple(spec4d.shape)))
+    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
+    return real, tuple(spec4d.shape), torch.view_as_real(spec4d.resolve_conj().contiguous())
+
+
+def _c128(t, shape, who, name):
+    """The contiguous interleaved view of a complex128 tensor of the given shape."""
+    if t.dtype != torch.complex128 or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s: %s must be complex128 %s (got %s %s)" % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
+    return torch.view_as_real(t.resolve_conj().contiguous())
+
+
+def _positions(who, name, t, B, n):
+    """Positions (n, 3) that serve every item, or (B, n, 3) -- n a count, or a letter where any will do -> (the contiguous
+    tensor, whether it holds a row per item)."""
+    if t.dim() not in (2, 3) or t.shape[-1] != 3 or (t.dim() == 3 and t.shape[0] != B) or (isinstance(n, int) and t.shape[-2] != n):
+        raise RuntimeError("%s: %s must be (%s, 3) or (%d, %s, 3) (got %s)" % (who, name, n, B, n, tuple(t.shape)))
+    return t.contiguous(), t.dim() == 3
 
 
 def stft_power(wave, n_fft=400, hop=160):
     """Power spectrogram of (B,S) waveforms, fp32 or fp64 (the reference's echoed signal is float64)."""
     B, S = wave.shape
-    power = torch.empty((B, n_fft // 2 + 1, 1 + S // hop), device=wave.device, dtype=wave.dtype)
+    power = _empty(wave, wave.dtype, B, n_fft // 2 + 1, 1 + S // hop)
     _call_real("stft_power", wave.dtype, _ptr(wave, wave.dtype, "wave"), _ptr(power, wave.dtype), B, S, n_fft, hop)
     return power
 
@@ -813,7 +843,7 @@ def stft_complex(wave, n_fft=400, hop=160):
     """Complex STFT (B, n_fft/2+1, T) of (B,S) waveforms: complex64 for fp32 input, complex128 for fp64."""
     B, S = wave.shape
     F, T = n_fft // 2 + 1, 1 + S // hop
-    out = torch.empty((B, F, T, 2), device=wave.device, dtype=wave.dtype)
+    out = _empty(wave, wave.dtype, B, F, T, 2)
     _call_real("stft_complex", wave.dtype, _ptr(wave, wave.dtype, "wave"), _ptr(out, wave.dtype), B, S, n_fft, hop)
     return torch.view_as_complex(out)
 
@@ -827,9 +857,8 @@ def fir_same(wave, h):
         if h.shape[0] != B:
             raise RuntimeError("fir_same: %d impulse responses for %d waveforms" % (h.shape[0], B))
         stride, Nh = h.shape[1], h.shape[1]
-    out = torch.empty((B, S), device=wave.device, dtype=torch.float64)
-    _check(lib().alvq_fir_same_f64(_ptr(wave, name="wave"), _ptr(h, torch.float64, "h"), _ptr(out, torch.float64), B, S, Nh,
-                                   stride, _stream()), "alvq_fir_same_f64")
+    out = _empty(wave, torch.float64, B, S)
+    _call("alvq_fir_same_f64", _ptr(wave, name="wave"), _ptr(h, torch.float64, "h"), _ptr(out, torch.float64), B, S, Nh, stride)
     return out
 
 
@@ -838,17 +867,15 @@ def spec_rir_wiener(speech_spec, echoed_spec):
     if speech_spec.dtype != torch.complex64 or echoed_spec.dtype != torch.complex128 or speech_spec.shape != echoed_spec.shape:
         raise RuntimeError("spec_rir_wiener: expected complex64 and complex128 tensors of one shape")
     B, F, T = speech_spec.shape
-    dev = speech_spec.device
     sr, er = torch.view_as_real(speech_spec), torch.view_as_real(echoed_spec)
-    speech_pow = torch.empty((B, F, T), device=dev, dtype=torch.float32)
-    echoed_pow = torch.empty((B, F, T), device=dev, dtype=torch.float64)
-    rir_pow = torch.empty((B, F, T), device=dev, dtype=torch.float64)
-    wiener = torch.empty((B, F), device=dev, dtype=torch.float64)
-    ws = torch.empty((B, F), device=dev, dtype=torch.float64)
-    _check(lib().alvq_spec_rir_wiener_f64(_ptr(sr, name="speech_spec"), _ptr(er, torch.float64, "echoed_spec"), _ptr(speech_pow),
-                                          _ptr(echoed_pow, torch.float64), _ptr(rir_pow, torch.float64),
-                                          _ptr(wiener, torch.float64), _ptr(ws, torch.float64), B, F, T, _stream()),
-           "alvq_spec_rir_wiener_f64")
+    speech_pow = _empty(speech_spec, torch.float32, B, F, T)
+    echoed_pow = _empty(speech_spec, torch.float64, B, F, T)
+    rir_pow = _empty(speech_spec, torch.float64, B, F, T)
+    wiener = _empty(speech_spec, torch.float64, B, F)
+    ws = _empty(speech_spec, torch.float64, B, F)
+    _call("alvq_spec_rir_wiener_f64", _ptr(sr, name="speech_spec"), _ptr(er, torch.float64, "echoed_spec"), _ptr(speech_pow),
+          _ptr(echoed_pow, torch.float64), _ptr(rir_pow, torch.float64), _ptr(wiener, torch.float64), _ptr(ws, torch.float64),
+          B, F, T)
     return speech_pow, echoed_pow, rir_pow, wiener
 
 
@@ -868,8 +895,8 @@ def istft(spec, n_fft=400, hop=160, length=None):
     B, T, real = _spec_dims(spec, n_fft, "istft")
     length = hop * (T - 1) if length is None else int(length)
     sr = torch.view_as_real(spec.resolve_conj().contiguous())
-    wave = torch.empty((B, length), device=spec.device, dtype=real)
-    ws = torch.empty((B, T, n_fft), device=spec.device, dtype=real)
+    wave = _empty(spec, real, B, length)
+    ws = _empty(spec, real, B, T, n_fft)
     _call_real("istft", real, _ptr(sr, real, "spec"), _ptr(wave, real), _ptr(ws, real), B, T, n_fft, hop, length)
     return wave
 
@@ -882,11 +909,9 @@ def griffin_lim(mag, angles, n_iter, momentum, n_fft, hop, length):
         raise RuntimeError("griffin_lim: mag must be %s of shape %s (got %s %s)" % (real, tuple(angles.shape), mag.dtype,
                                                                                    tuple(mag.shape)))
     ar = torch.view_as_real(angles.resolve_conj().contiguous())
-    wave = torch.empty((B, length), device=mag.device, dtype=real)
-    nbytes = lib().alvq_griffin_lim_workspace_bytes(B, T, n_fft, 8 if real == torch.float64 else 4)
-    if nbytes < 0:
-        raise RuntimeError("griffin_lim: bad dims (B=%d T=%d n_fft=%d)" % (B, T, n_fft))
-    ws = torch.empty((nbytes,), device=mag.device, dtype=torch.uint8)
+    wave = _empty(mag, real, B, length)
+    ws = _scratch(lib().alvq_griffin_lim_workspace_bytes(B, T, n_fft, 8 if real == torch.float64 else 4), mag,
+                  "griffin_lim: bad dims (B=%d T=%d n_fft=%d)" % (B, T, n_fft))
     _call_real("griffin_lim", real, _ptr(mag, real, "mag"), _ptr(ar, real, "angles"), _ptr(wave, real), _ptr(ws, torch.uint8), B, T,
                n_fft, hop, int(length), int(n_iter), float(momentum))
     return wave
@@ -902,11 +927,10 @@ def rir(src, rcv, L, beta, c, fs, nsample, order=-1, hp_filter=True):
     if len(L) != 3 or len(beta) != 6:
         raise RuntimeError("rir: need 3 room dimensions and 6 reflection coefficients (got %d and %d)" % (len(L), len(beta)))
     B = src.shape[0]
-    h = torch.empty((B, int(nsample)), device=src.device, dtype=torch.float64)
+    h = _empty(src, torch.float64, B, int(nsample))
     beta_c = (ctypes.c_double * 6)(*beta)
-    _check(lib().alvq_rir_f64(_ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"), _ptr(h, torch.float64), B,
-                              int(nsample), L[0], L[1], L[2], ctypes.cast(beta_c, _c_void_p), float(c), float(fs), int(order),
-                              int(bool(hp_filter)), _stream()), "alvq_rir_f64")
+    _call("alvq_rir_f64", _ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"), _ptr(h, torch.float64), B,
+          int(nsample), L[0], L[1], L[2], ctypes.cast(beta_c, _c_void_p), float(c), float(fs), int(order), int(bool(hp_filter)))
     return h
 
 
@@ -918,12 +942,11 @@ def rir_rooms(src, rcv, room, beta, c, fs, nsample, order=-1, hp_filter=True):
     if src.dim() != 2 or src.shape[1] != 3 or rcv.shape != src.shape or room.shape != src.shape or tuple(beta.shape) != (B, 6):
         raise RuntimeError("rir_rooms: src, rcv, room must be (B, 3) and beta (B, 6) (got %s, %s, %s, %s)"
                            % (tuple(src.shape), tuple(rcv.shape), tuple(room.shape), tuple(beta.shape)))
-    h = torch.empty((B, int(nsample)), device=src.device, dtype=torch.float64)
-    status = torch.empty((B,), device=src.device, dtype=torch.int32)
-    _check(lib().alvq_rir_rooms_f64(_ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"),
-                                    _ptr(room, torch.float64, "room"), _ptr(beta, torch.float64, "beta"), _ptr(h, torch.float64),
-                                    _ptr(status, torch.int32, "status"), B, int(nsample), float(c), float(fs), int(order),
-                                    int(bool(hp_filter)), _stream()), "alvq_rir_rooms_f64")
+    h = _empty(src, torch.float64, B, int(nsample))
+    status = _empty(src, torch.int32, B)
+    _call("alvq_rir_rooms_f64", _ptr(src, torch.float64, "src"), _ptr(rcv, torch.float64, "rcv"),
+          _ptr(room, torch.float64, "room"), _ptr(beta, torch.float64, "beta"), _ptr(h, torch.float64),
+          _ptr(status, torch.int32, "status"), B, int(nsample), float(c), float(fs), int(order), int(bool(hp_filter)))
     return h, status
 
 
@@ -936,7 +959,7 @@ def _responses(h, who):
 def edc(h):
     """Energy decay curves (alvq_edc_f32 / _f64): h (B, n) float32 or float64 on the GPU -> (B, n) float64 dB."""
     B, n = _responses(h, "edc")
-    out = torch.empty((B, n), device=h.device, dtype=torch.float64)
+    out = _empty(h, torch.float64, B, n)
     _call_real("edc", h.dtype, _ptr(h, h.dtype, "h"), _ptr(out, torch.float64), B, n)
     return out
 
@@ -946,9 +969,8 @@ def room_acoustics(h, fs, k50, k80, kdirect):
     float64 with columns t30 t20 edt c50 c80 d50 drr, onset (B,) int32, status (B,) int32).  status is the kernel's per-row
     flag (include/alvq.h) and is not read here."""
     B, n = _responses(h, "room_acoustics")
-    out = torch.empty((B, 7), device=h.device, dtype=torch.float64)
-    onset = torch.empty((B,), device=h.device, dtype=torch.int32)
-    status = torch.empty((B,), device=h.device, dtype=torch.int32)
+    out = _empty(h, torch.float64, B, 7)
+    onset, status = _empty(h, torch.int32, B), _empty(h, torch.int32, B)
     _call_real("room_acoustics", h.dtype, _ptr(h, h.dtype, "h"), _ptr(out, torch.float64), _ptr(onset, torch.int32),
                _ptr(status, torch.int32), B, n, float(fs), int(k50), int(k80), int(kdirect))
     return out, onset, status
@@ -968,7 +990,7 @@ def resample_poly(x, h, up, down):
     B, n = _responses(x, "resample_poly")
     if h.dim() != 1 or h.shape[0] % 2 != 1:
         raise RuntimeError("resample_poly: h must hold an odd number of taps (got %s)" % (tuple(h.shape),))
-    y = torch.empty((B, -(-n * up // down)), device=x.device, dtype=torch.float64)
+    y = _empty(x, torch.float64, B, -(-n * up // down))
     _call_real("resample_poly", x.dtype, _ptr(x, x.dtype, "x"), _ptr(h, torch.float64, "h"), _ptr(y, torch.float64), B, n, int(up),
                int(down), h.shape[0] // 2)
     return y
@@ -981,26 +1003,20 @@ def stoi(clean, degraded, band_lo, band_hi):
     B, n = _row_pair(clean, degraded, "stoi")
     if len(band_lo) != 15 or len(band_hi) != 15:
         raise RuntimeError("stoi: need 15 band edges each (got %d and %d)" % (len(band_lo), len(band_hi)))
-    nbytes = lib().alvq_stoi_workspace_bytes(B, n)
-    if nbytes < 0:
-        raise RuntimeError("stoi: bad dims (B=%d n=%d; need 1 <= B <= 65535, 2 <= n <= 2^24)" % (B, n))
-    dev = clean.device
-    value = torch.empty((B,), device=dev, dtype=torch.float64)
-    kept = torch.empty((B,), device=dev, dtype=torch.int32)
-    status = torch.empty((B,), device=dev, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    ws = _scratch(lib().alvq_stoi_workspace_bytes(B, n), clean,
+                  "stoi: bad dims (B=%d n=%d; need 1 <= B <= 65535, 2 <= n <= 2^24)" % (B, n))
+    value, kept, status = _empty(clean, torch.float64, B), _empty(clean, torch.int32, B), _empty(clean, torch.int32, B)
     lo_c, hi_c = (ctypes.c_int * 15)(*[int(v) for v in band_lo]), (ctypes.c_int * 15)(*[int(v) for v in band_hi])
-    _check(lib().alvq_stoi_f64(_ptr(clean, torch.float64, "clean"), _ptr(degraded, torch.float64, "degraded"),
-                               ctypes.cast(lo_c, _c_void_p), ctypes.cast(hi_c, _c_void_p), _ptr(value, torch.float64),
-                               _ptr(kept, torch.int32), _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, n, _stream()),
-           "alvq_stoi_f64")
+    _call("alvq_stoi_f64", _ptr(clean, torch.float64, "clean"), _ptr(degraded, torch.float64, "degraded"),
+          ctypes.cast(lo_c, _c_void_p), ctypes.cast(hi_c, _c_void_p), _ptr(value, torch.float64), _ptr(kept, torch.int32),
+          _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, n)
     return value, kept, status
 
 
 def si_sdr(reference, estimate):
     """Scale-invariant SDR (alvq_si_sdr_f32 / _f64): two (B, n) tensors of one real dtype on the GPU -> (B,) float64 dB."""
     B, n = _row_pair(reference, estimate, "si_sdr")
-    out = torch.empty((B,), device=reference.device, dtype=torch.float64)
+    out = _empty(reference, torch.float64, B)
     _call_real("si_sdr", reference.dtype, _ptr(reference, reference.dtype, "reference"), _ptr(estimate, reference.dtype, "estimate"),
                _ptr(out, torch.float64), B, n)
     return out
@@ -1013,7 +1029,7 @@ def lsd(p, q, eps):
         raise RuntimeError("lsd: expected two float32 or two float64 (B, F, T) tensors of one shape (got %s %s and %s %s)"
                            % (p.dtype, tuple(p.shape), q.dtype, tuple(q.shape)))
     B, F, T = p.shape
-    out = torch.empty((B,), device=p.device, dtype=torch.float64)
+    out = _empty(p, torch.float64, B)
     _call_real("lsd", p.dtype, _ptr(p, p.dtype, "p"), _ptr(q, p.dtype, "q"), _ptr(out, torch.float64), B, F, T, float(eps))
     return out
 
@@ -1032,7 +1048,7 @@ def pairwise_si_sdr(references, estimates):
     """The SI-SDR of every pair (alvq_pairwise_si_sdr_f32 / _f64): references (B, K, n) and estimates (B, J, n) of one real
     dtype on the GPU -> (B, K, J) float64 dB."""
     B, K, J, n = _source_rows(references, estimates, "pairwise_si_sdr")
-    table = torch.empty((B, K, J), device=references.device, dtype=torch.float64)
+    table = _empty(references, torch.float64, B, K, J)
     _call_real("pairwise_si_sdr", references.dtype, _ptr(references, references.dtype, "references"),
                _ptr(estimates, references.dtype, "estimates"), _ptr(table, torch.float64), B, K, J, n)
     return table
@@ -1045,11 +1061,11 @@ def assign(table, maximize):
     if table.dim() != 3 or table.dtype != torch.float64:
         raise RuntimeError("assign: expected a float64 (B, K, J) table (got %s %s)" % (table.dtype, tuple(table.shape)))
     B, K, J = table.shape
-    perm = torch.empty((B, K), device=table.device, dtype=torch.int32)
-    total = torch.empty((B,), device=table.device, dtype=torch.float64)
-    status = torch.empty((B,), device=table.device, dtype=torch.int32)
-    _check(lib().alvq_assign_f64(_ptr(table, torch.float64, "table"), _ptr(perm, torch.int32), _ptr(total, torch.float64),
-                                 _ptr(status, torch.int32), B, K, J, 1 if maximize else 0, _stream()), "alvq_assign_f64")
+    perm = _empty(table, torch.int32, B, K)
+    total = _empty(table, torch.float64, B)
+    status = _empty(table, torch.int32, B)
+    _call("alvq_assign_f64", _ptr(table, torch.float64, "table"), _ptr(perm, torch.int32), _ptr(total, torch.float64),
+          _ptr(status, torch.int32), B, K, J, 1 if maximize else 0)
     return perm, total, status
 
 
@@ -1059,34 +1075,27 @@ def si_bss_eval(references, estimates, perm):
     B, K, J, n = _source_rows(references, estimates, "si_bss_eval")
     if perm.dtype != torch.int32 or tuple(perm.shape) != (B, K):
         raise RuntimeError("si_bss_eval: expected an int32 (%d, %d) perm (got %s %s)" % (B, K, perm.dtype, tuple(perm.shape)))
-    dev = references.device
-    sdr, sir, sar = (torch.empty((B, K), device=dev, dtype=torch.float64) for _ in range(3))
-    status = torch.empty((B,), device=dev, dtype=torch.int32)
+    sdr, sir, sar = (_empty(references, torch.float64, B, K) for _ in range(3))
+    status = _empty(references, torch.int32, B)
     _call_real("si_bss_eval", references.dtype, _ptr(references, references.dtype, "references"),
                _ptr(estimates, references.dtype, "estimates"), _ptr(perm, torch.int32, "perm"), _ptr(sdr, torch.float64),
                _ptr(sir, torch.float64), _ptr(sar, torch.float64), _ptr(status, torch.int32), B, K, J, n)
     return sdr, sir, sar, status
 
 
-# ----------------------------------------------------------------------------------------------- t-SNE
+# ----------------------------------------------------------------------------------------------- dereverberation
 def wpe(spec4d, taps, delay, iterations, psd_context, eps, loading):
     """WPE dereverberation (alvq_wpe_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 on the GPU -> (out of the same
     shape and dtype, status (B, F) int32).  status is the kernel's per-bin flag (include/alvq.h) and is not read here."""
-    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
-        raise RuntimeError("wpe: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
-                           % (spec4d.dtype, tuple(spec4d.shape)))
-    B, D, F, T = spec4d.shape
-    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "wpe")
     nbytes = lib().alvq_wpe_workspace_bytes(B, D, F, T, int(taps))
-    if nbytes < 0:
-        raise RuntimeError("wpe: bad dims (B=%d D=%d F=%d T=%d taps=%d; need 1 <= B <= 65535, 1 <= D <= 8, D taps <= 64, "
-                           "1 <= T <= 65535)" % (B, D, F, T, taps))
-    xr = torch.view_as_real(spec4d.resolve_conj().contiguous())
+    ws = _scratch(nbytes, spec4d, "wpe: bad dims (B=%d D=%d F=%d T=%d taps=%d; need 1 <= B <= 65535, 1 <= D <= 8, D taps <= 64, "
+                  "1 <= T <= 65535)" % (B, D, F, T, taps))
     out = torch.empty_like(xr)
-    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=spec4d.device, dtype=torch.uint8) if nbytes else None
-    _call_real("wpe", real, _ptr(xr, real, "spec"), _ptr(out, real), _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T,
-               int(taps), int(delay), int(iterations), int(psd_context), float(eps), float(loading))
+    status = _empty(spec4d, torch.int32, B, F)
+    _call_real("wpe", real, _ptr(xr, real, "spec"), _ptr(out, real), _ptr(status, torch.int32),
+               _ptr(ws if nbytes else None, torch.uint8), B, D, F, T, int(taps), int(delay), int(iterations), int(psd_context),
+               float(eps), float(loading))
     return torch.view_as_complex(out), status
 
 
@@ -1095,14 +1104,9 @@ def phat_cross_spectra(spec4d, f_lo, f_hi):
     """PHAT-weighted cross-spectra of the microphone pairs (alvq_phat_cross_spectra_f32 / _f64): spec4d (B, D, F, T) complex64 /
     complex128 on the GPU -> (psi (B, D (D - 1) / 2, F) complex128, 0 outside the bins f_lo .. f_hi; status (B,) int32).
     status is the kernel's per-item flag (include/alvq.h) and is not read here."""
-    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
-        raise RuntimeError("phat_cross_spectra: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
-                           % (spec4d.dtype, tuple(spec4d.shape)))
-    B, D, F, T = spec4d.shape
-    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
-    xr = torch.view_as_real(spec4d.resolve_conj().contiguous())
-    psi = torch.empty((B, D * (D - 1) // 2, F, 2), device=spec4d.device, dtype=torch.float64)
-    status = torch.empty((B,), device=spec4d.device, dtype=torch.int32)
+    real, (B, D, F, T), xr = _spec4_real(spec4d, "phat_cross_spectra")
+    psi = _empty(spec4d, torch.float64, B, D * (D - 1) // 2, F, 2)
+    status = _empty(spec4d, torch.int32, B)
     _call_real("phat_cross_spectra", real, _ptr(xr, real, "spec"), _ptr(psi, torch.float64), _ptr(status, torch.int32), B, D, F, T,
                int(f_lo), int(f_hi))
     return torch.view_as_complex(psi), status
@@ -1123,9 +1127,9 @@ def gcc_phat(psi, n_fft, max_lag, f_lo, f_hi):
     """GCC-PHAT at the integer lags -max_lag .. max_lag (alvq_gcc_phat_f64): psi (B, P, F) complex128 on the GPU ->
     (B, P, 2 max_lag + 1) float64."""
     B, D, pr = _psi_dims(psi, int(n_fft), "gcc_phat")
-    r = torch.empty((B, psi.shape[1], 2 * int(max_lag) + 1), device=psi.device, dtype=torch.float64)
-    _check(lib().alvq_gcc_phat_f64(_ptr(pr, torch.float64, "psi"), _ptr(r, torch.float64), B, D, int(n_fft), int(max_lag), int(f_lo),
-                                   int(f_hi), _stream()), "alvq_gcc_phat_f64")
+    r = _empty(psi, torch.float64, B, psi.shape[1], 2 * int(max_lag) + 1)
+    _call("alvq_gcc_phat_f64", _ptr(pr, torch.float64, "psi"), _ptr(r, torch.float64), B, D, int(n_fft), int(max_lag),
+          int(f_lo), int(f_hi))
     return r
 
 
@@ -1134,39 +1138,17 @@ def srp_phat(psi, mics, cand, fs, n_fft, c, f_lo, f_hi):
     cand (G, 3) or (B, G, 3), float64, all on the GPU -> (map (B, G) float64, best (B,) int32, status (B,) int32).  A
     two-dimensional mics / cand serves every item.  status is the kernel's per-item flag (include/alvq.h) and is not read here."""
     B, D, pr = _psi_dims(psi, int(n_fft), "srp_phat")
-    if mics.dim() not in (2, 3) or tuple(mics.shape[-2:]) != (D, 3) or (mics.dim() == 3 and mics.shape[0] != B):
-        raise RuntimeError("srp_phat: mics must be (%d, 3) or (%d, %d, 3) (got %s)" % (D, B, D, tuple(mics.shape)))
-    if cand.dim() not in (2, 3) or cand.shape[-1] != 3 or (cand.dim() == 3 and cand.shape[0] != B):
-        raise RuntimeError("srp_phat: cand must be (G, 3) or (%d, G, 3) (got %s)" % (B, tuple(cand.shape)))
-    mics, cand = mics.contiguous(), cand.contiguous()
+    mics, mics_per_item = _positions("srp_phat", "mics", mics, B, D)
+    cand, cand_per_item = _positions("srp_phat", "cand", cand, B, "G")
     G = cand.shape[-2]
-    out = torch.empty((B, G), device=psi.device, dtype=torch.float64)
-    best = torch.empty((B,), device=psi.device, dtype=torch.int32)
-    status = torch.empty((B,), device=psi.device, dtype=torch.int32)
-    _check(lib().alvq_srp_phat_f64(_ptr(pr, torch.float64, "psi"), _ptr(mics, torch.float64, "mics"), _ptr(cand, torch.float64, "cand"),
-                                   _ptr(out, torch.float64), _ptr(best, torch.int32), _ptr(status, torch.int32), B, D, G,
-                                   3 * D if mics.dim() == 3 else 0, 3 * G if cand.dim() == 3 else 0, float(fs), int(n_fft),
-                                   float(c), int(f_lo), int(f_hi), _stream()), "alvq_srp_phat_f64")
+    out, best, status = _empty(psi, torch.float64, B, G), _empty(psi, torch.int32, B), _empty(psi, torch.int32, B)
+    _call("alvq_srp_phat_f64", _ptr(pr, torch.float64, "psi"), _ptr(mics, torch.float64, "mics"),
+          _ptr(cand, torch.float64, "cand"), _ptr(out, torch.float64), _ptr(best, torch.int32), _ptr(status, torch.int32), B, D,
+          G, 3 * D if mics_per_item else 0, 3 * G if cand_per_item else 0, float(fs), int(n_fft), float(c), int(f_lo), int(f_hi))
     return out, best, status
 
 
 # ----------------------------------------------------------------------------------------------- beamforming
-def _spec4_real(spec4d, who):
-    """(real dtype, (B, D, F, T), the contiguous interleaved view) of a complex (B, D, F, T) spectrogram."""
-    if spec4d.dim() != 4 or spec4d.dtype not in (torch.complex64, torch.complex128):
-        raise RuntimeError("%s: expected a complex64 / complex128 (B, D, F, T) spectrogram (got %s %s)"
-                           % (who, spec4d.dtype, tuple(spec4d.shape)))
-    real = torch.float64 if spec4d.dtype == torch.complex128 else torch.float32
-    return real, tuple(spec4d.shape), torch.view_as_real(spec4d.resolve_conj().contiguous())
-
-
-def _c128(t, shape, who, name):
-    """The contiguous interleaved view of a complex128 tensor of the given shape."""
-    if t.dtype != torch.complex128 or tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s: %s must be complex128 %s (got %s %s)" % (who, name, tuple(shape), t.dtype, tuple(t.shape)))
-    return torch.view_as_real(t.resolve_conj().contiguous())
-
-
 def spatial_covariance(spec4d, mask=None):
     """Mask-weighted spatial covariances (alvq_spatial_covariance_f32 / _f64): spec4d (B, D, F, T) complex64 / complex128 and
     mask (B, F, T) float64 or None on the GPU -> (Phi (B, F, D, D) complex128, status (B, F) int32).  status is the kernel's
@@ -1177,8 +1159,8 @@ def spatial_covariance(spec4d, mask=None):
             raise RuntimeError("spatial_covariance: mask must be float64 (%d, %d, %d) (got %s %s)"
                                % (B, F, T, mask.dtype, tuple(mask.shape)))
         mask = mask.contiguous()
-    phi = torch.empty((B, F, D, D, 2), device=spec4d.device, dtype=torch.float64)
-    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
+    phi = _empty(spec4d, torch.float64, B, F, D, D, 2)
+    status = _empty(spec4d, torch.int32, B, F)
     _call_real("spatial_covariance", real, _ptr(xr, real, "spec"), _ptr(mask, torch.float64, "mask"), _ptr(phi, torch.float64),
                _ptr(status, torch.int32), B, D, F, T)
     return torch.view_as_complex(phi), status
@@ -1190,15 +1172,13 @@ def steering_vectors(mics, src, F, fs, n_fft, c, ref):
     if src.dim() != 2 or src.shape[1] != 3:
         raise RuntimeError("steering_vectors: src must be (B, 3) (got %s)" % (tuple(src.shape),))
     B = src.shape[0]
-    if mics.dim() not in (2, 3) or mics.shape[-1] != 3 or (mics.dim() == 3 and mics.shape[0] != B):
-        raise RuntimeError("steering_vectors: mics must be (D, 3) or (%d, D, 3) (got %s)" % (B, tuple(mics.shape)))
-    mics, src = mics.contiguous(), src.contiguous()
-    D = mics.shape[-2]
-    A = torch.empty((B, D, int(F), 2), device=src.device, dtype=torch.float64)
-    status = torch.empty((B,), device=src.device, dtype=torch.int32)
-    _check(lib().alvq_steering_vectors_f64(_ptr(mics, torch.float64, "mics"), _ptr(src, torch.float64, "src"), _ptr(A, torch.float64),
-                                           _ptr(status, torch.int32), B, D, int(F), float(fs), int(n_fft), float(c), int(ref),
-                                           1 if mics.dim() == 3 else 0, _stream()), "alvq_steering_vectors_f64")
+    mics, per_item = _positions("steering_vectors", "mics", mics, B, "D")
+    src, D = src.contiguous(), mics.shape[-2]
+    A = _empty(src, torch.float64, B, D, int(F), 2)
+    status = _empty(src, torch.int32, B)
+    _call("alvq_steering_vectors_f64", _ptr(mics, torch.float64, "mics"), _ptr(src, torch.float64, "src"),
+          _ptr(A, torch.float64), _ptr(status, torch.int32), B, D, int(F), float(fs), int(n_fft), float(c), int(ref),
+          int(per_item))
     return torch.view_as_complex(A), status
 
 
@@ -1219,13 +1199,11 @@ def beamform_weights(mode, B, D, F, phi_n=None, phi_s=None, steering=None, ref=0
         if wanted and t is None:
             raise RuntimeError("%s: mode %d needs %s" % (who, mode, name))
         views.append(_c128(t, shape, who, name) if wanted else None)
-    device = next(v for v in views if v is not None).device
-    W = torch.empty((B, F, D, 2), device=device, dtype=torch.float64)
-    status = torch.empty((B, F), device=device, dtype=torch.int32)
-    _check(lib().alvq_beamform_weights_f64(_ptr(views[0], torch.float64, "phi_n"), _ptr(views[1], torch.float64, "phi_s"),
-                                           _ptr(views[2], torch.float64, "steering"), _ptr(W, torch.float64),
-                                           _ptr(status, torch.int32), B, D, F, int(mode), int(ref), float(loading), _stream()),
-           "alvq_beamform_weights_f64")
+    first = next(v for v in views if v is not None)
+    W, status = _empty(first, torch.float64, B, F, D, 2), _empty(first, torch.int32, B, F)
+    _call("alvq_beamform_weights_f64", _ptr(views[0], torch.float64, "phi_n"), _ptr(views[1], torch.float64, "phi_s"),
+          _ptr(views[2], torch.float64, "steering"), _ptr(W, torch.float64), _ptr(status, torch.int32), B, D, F, int(mode),
+          int(ref), float(loading))
     return torch.view_as_complex(W), status
 
 
@@ -1234,7 +1212,7 @@ def beamform_apply(spec4d, w):
     GPU -> (B, F, T) of spec4d's dtype."""
     real, (B, D, F, T), xr = _spec4_real(spec4d, "beamform_apply")
     wr = _c128(w, (B, F, D), "beamform_apply", "w")
-    out = torch.empty((B, F, T, 2), device=spec4d.device, dtype=real)
+    out = _empty(spec4d, real, B, F, T, 2)
     _call_real("beamform_apply", real, _ptr(xr, real, "spec"), _ptr(wr, torch.float64, "w"), _ptr(out, real), B, D, F, T)
     return torch.view_as_complex(out)
 
@@ -1247,13 +1225,10 @@ def beamform_gev(phi_n, phi_s, ref=0, loading=0.0):
         raise RuntimeError("%s: phi_n must be (B, F, D, D) (got %s)" % (who, tuple(phi_n.shape)))
     B, F, D, _ = phi_n.shape
     pn, ps = _c128(phi_n, (B, F, D, D), who, "phi_n"), _c128(phi_s, (B, F, D, D), who, "phi_s")
-    W = torch.empty((B, F, D, 2), device=phi_n.device, dtype=torch.float64)
-    rtf = torch.empty((B, F, D, 2), device=phi_n.device, dtype=torch.float64)
-    gain = torch.empty((B, F), device=phi_n.device, dtype=torch.float64)
-    status = torch.empty((B, F), device=phi_n.device, dtype=torch.int32)
-    _check(lib().alvq_beamform_gev_f64(_ptr(pn, torch.float64, "phi_n"), _ptr(ps, torch.float64, "phi_s"), _ptr(W, torch.float64),
-                                       _ptr(rtf, torch.float64), _ptr(gain, torch.float64), _ptr(status, torch.int32), B, D, F,
-                                       int(ref), float(loading), _stream()), "alvq_beamform_gev_f64")
+    W, rtf = _empty(phi_n, torch.float64, B, F, D, 2), _empty(phi_n, torch.float64, B, F, D, 2)
+    gain, status = _empty(phi_n, torch.float64, B, F), _empty(phi_n, torch.int32, B, F)
+    _call("alvq_beamform_gev_f64", _ptr(pn, torch.float64, "phi_n"), _ptr(ps, torch.float64, "phi_s"), _ptr(W, torch.float64),
+          _ptr(rtf, torch.float64), _ptr(gain, torch.float64), _ptr(status, torch.int32), B, D, F, int(ref), float(loading))
     return torch.view_as_complex(W), torch.view_as_complex(rtf), gain, status
 
 
@@ -1266,15 +1241,12 @@ def auxiva(spec4d, iterations, model, ref, eps, w0=None):
     GPU -> (Y of spec4d's shape and dtype, W (B, F, D, D) complex128, status (B, F) int32).  status is the kernels' per-bin
     flag (include/alvq.h) and is not read here."""
     real, (B, D, F, T), xr = _spec4_real(spec4d, "auxiva")
-    nbytes = lib().alvq_auxiva_workspace_bytes(B, D, F, T)
-    if nbytes < 0:
-        raise RuntimeError("auxiva: bad dims (B=%d D=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, "
-                           "1 <= T <= 65535)" % (B, D, F, T))
+    ws = _scratch(lib().alvq_auxiva_workspace_bytes(B, D, F, T), spec4d,
+                  "auxiva: bad dims (B=%d D=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, 1 <= T <= 65535)"
+                  % (B, D, F, T))
     w0r = None if w0 is None else _c128(w0, (B, F, D, D), "auxiva", "w0")
     out = torch.empty_like(xr)
-    W = torch.empty((B, F, D, D, 2), device=spec4d.device, dtype=torch.float64)
-    status = torch.empty((B, F), device=spec4d.device, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=spec4d.device, dtype=torch.uint8)
+    W, status = _empty(spec4d, torch.float64, B, F, D, D, 2), _empty(spec4d, torch.int32, B, F)
     _call_real("auxiva", real, _ptr(xr, real, "spec"), _ptr(w0r, torch.float64, "w0"), _ptr(W, torch.float64), _ptr(out, real),
                _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, D, F, T, int(model), int(iterations), int(ref), float(eps))
     return torch.view_as_complex(out), torch.view_as_complex(W), status
@@ -1292,18 +1264,14 @@ def ilrma(spec4d, basis0, activations0, iterations, ref, floor, w0=None):
     if activations0.dtype != torch.float64 or tuple(activations0.shape) != (B, D, L, T):
         raise RuntimeError("ilrma: activations0 must be float64 (%d, %d, %d, %d) (got %s %s)"
                            % (B, D, L, T, activations0.dtype, tuple(activations0.shape)))
-    nbytes = lib().alvq_ilrma_workspace_bytes(B, D, L, F, T)
-    if nbytes < 0:
-        raise RuntimeError("ilrma: bad dims (B=%d D=%d L=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, "
-                           "1 <= L <= 16, 1 <= T <= 65535)" % (B, D, L, F, T))
+    ws = _scratch(lib().alvq_ilrma_workspace_bytes(B, D, L, F, T), spec4d,
+                  "ilrma: bad dims (B=%d D=%d L=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= D <= 8, 1 <= L <= 16, "
+                  "1 <= T <= 65535)" % (B, D, L, F, T))
     w0r = None if w0 is None else _c128(w0, (B, F, D, D), "ilrma", "w0")
-    dev = spec4d.device
     b0, a0 = basis0.contiguous(), activations0.contiguous()
     out = torch.empty_like(xr)
-    W = torch.empty((B, F, D, D, 2), device=dev, dtype=torch.float64)
+    W, status = _empty(spec4d, torch.float64, B, F, D, D, 2), _empty(spec4d, torch.int32, B, F)
     basis, activations = torch.empty_like(b0), torch.empty_like(a0)
-    status = torch.empty((B, F), device=dev, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
     _call_real("ilrma", real, _ptr(xr, real, "spec"), _ptr(w0r, torch.float64, "w0"), _ptr(b0, torch.float64, "basis0"),
                _ptr(a0, torch.float64, "activations0"), _ptr(W, torch.float64), _ptr(basis, torch.float64),
                _ptr(activations, torch.float64), _ptr(out, real), _ptr(status, torch.int32), _ptr(ws, torch.uint8),
@@ -1315,7 +1283,7 @@ def separation_masks(spec4d):
     """Ratio masks (alvq_separation_masks_f32 / _f64): spec4d (B, K, F, T) complex64 / complex128 on the GPU -> (B, K, F, T)
     float64."""
     real, (B, K, F, T), yr = _spec4_real(spec4d, "separation_masks")
-    M = torch.empty((B, K, F, T), device=spec4d.device, dtype=torch.float64)
+    M = _empty(spec4d, torch.float64, B, K, F, T)
     _call_real("separation_masks", real, _ptr(yr, real, "spec"), _ptr(M, torch.float64), B, K, F, T)
     return M
 
@@ -1331,17 +1299,12 @@ def cacgmm(spec4d, init, iterations, floor, quadratic0=None):
     if quadratic0 is not None and (quadratic0.dtype != torch.float64 or quadratic0.shape != init.shape):
         raise RuntimeError("cacgmm: quadratic0 must be float64 %s (got %s %s)" % (tuple(init.shape), quadratic0.dtype,
                                                                                  tuple(quadratic0.shape)))
-    nbytes = lib().alvq_cacgmm_workspace_bytes(B, D, K, F, T)
-    if nbytes < 0:
-        raise RuntimeError("cacgmm: bad dims (B=%d D=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 2 <= D <= 8, "
-                           "1 <= K <= 8, 1 <= T <= 65535)" % (B, D, K, F, T))
-    dev = spec4d.device
-    masks = torch.empty((B, K, F, T), device=dev, dtype=torch.float64)
-    quadratic = torch.empty((B, K, F, T), device=dev, dtype=torch.float64)
-    prior = torch.empty((B, K, T), device=dev, dtype=torch.float64)
-    cov = torch.empty((B, F, K, D, D, 2), device=dev, dtype=torch.float64)
-    status = torch.empty((B, F), device=dev, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    ws = _scratch(lib().alvq_cacgmm_workspace_bytes(B, D, K, F, T), spec4d,
+                  "cacgmm: bad dims (B=%d D=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 2 <= D <= 8, 1 <= K <= 8, "
+                  "1 <= T <= 65535)" % (B, D, K, F, T))
+    masks, quadratic = _empty(spec4d, torch.float64, B, K, F, T), _empty(spec4d, torch.float64, B, K, F, T)
+    prior, cov = _empty(spec4d, torch.float64, B, K, T), _empty(spec4d, torch.float64, B, F, K, D, D, 2)
+    status = _empty(spec4d, torch.int32, B, F)
     g0, q0 = init.contiguous(), None if quadratic0 is None else quadratic0.contiguous()
     _call_real("cacgmm", real, _ptr(xr, real, "spec"), _ptr(g0, torch.float64, "init"),
                _ptr(q0, torch.float64, "quadratic0"), _ptr(masks, torch.float64), _ptr(prior, torch.float64),
@@ -1359,21 +1322,15 @@ def align_permutations(profile, iterations, perm0=None):
     B, K, F, T = profile.shape
     if perm0 is not None and (perm0.dtype != torch.int32 or tuple(perm0.shape) != (B, F, K)):
         raise RuntimeError("align_permutations: perm0 must be int32 %s (got %s %s)" % ((B, F, K), perm0.dtype, tuple(perm0.shape)))
-    nbytes = lib().alvq_align_workspace_bytes(B, K, F, T)
-    if nbytes < 0:
-        raise RuntimeError("align_permutations: bad dims (B=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, "
-                           "1 <= K <= 8, 2 <= T <= 65535)" % (B, K, F, T))
-    dev = profile.device
+    ws = _scratch(lib().alvq_align_workspace_bytes(B, K, F, T), profile,
+                  "align_permutations: bad dims (B=%d K=%d F=%d T=%d; need 1 <= B <= 65535, B F <= 2^31 - 1, 1 <= K <= 8, "
+                  "2 <= T <= 65535)" % (B, K, F, T))
     p, p0 = profile.contiguous(), None if perm0 is None else perm0.contiguous()
-    perm = torch.empty((B, F, K), device=dev, dtype=torch.int32)
-    score = torch.empty((B, F), device=dev, dtype=torch.float64)
-    changed = torch.empty((B,), device=dev, dtype=torch.int32)
-    status = torch.empty((B, F), device=dev, dtype=torch.int32)
-    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
-    _check(lib().alvq_align_permutations_f64(_ptr(p, torch.float64, "profile"), _ptr(p0, torch.int32, "perm0"),
-                                             _ptr(perm, torch.int32), _ptr(score, torch.float64), _ptr(changed, torch.int32),
-                                             _ptr(status, torch.int32), _ptr(ws, torch.uint8), B, K, F, T, int(iterations),
-                                             _stream()), "alvq_align_permutations_f64")
+    perm, score = _empty(profile, torch.int32, B, F, K), _empty(profile, torch.float64, B, F)
+    changed, status = _empty(profile, torch.int32, B), _empty(profile, torch.int32, B, F)
+    _call("alvq_align_permutations_f64", _ptr(p, torch.float64, "profile"), _ptr(p0, torch.int32, "perm0"),
+          _ptr(perm, torch.int32), _ptr(score, torch.float64), _ptr(changed, torch.int32), _ptr(status, torch.int32),
+          _ptr(ws, torch.uint8), B, K, F, T, int(iterations))
     return perm, score, changed, status
 
 
@@ -1388,8 +1345,8 @@ def permute_bins(x, perm):
         raise RuntimeError("permute_bins: perm must be int32 %s (got %s %s)" % ((B, F, K), perm.dtype, tuple(perm.shape)))
     xc, pc = x.resolve_conj().contiguous(), perm.contiguous()
     out = torch.empty_like(xc)
-    _check(lib().alvq_permute_bins(_ptr(xc, x.dtype, "x"), _ptr(pc, torch.int32, "perm"), _ptr(out, x.dtype), B, K, F, T,
-                                   x.element_size(), _stream()), "alvq_permute_bins")
+    _call("alvq_permute_bins", _ptr(xc, x.dtype, "x"), _ptr(pc, torch.int32, "perm"), _ptr(out, x.dtype), B, K, F, T,
+          x.element_size())
     return out
 
 
@@ -1402,11 +1359,9 @@ def eigh(cov):
         raise RuntimeError("eigh: cov must be (n, D, D) (got %s)" % (tuple(cov.shape),))
     n, D, _ = cov.shape
     ar = _c128(cov, (n, D, D), "eigh", "cov")
-    lam = torch.empty((n, D), device=cov.device, dtype=torch.float64)
-    V = torch.empty((n, D, D, 2), device=cov.device, dtype=torch.float64)
-    status = torch.empty((n,), device=cov.device, dtype=torch.int32)
-    _check(lib().alvq_eigh_f64(_ptr(ar, torch.float64, "cov"), _ptr(lam, torch.float64), _ptr(V, torch.float64),
-                               _ptr(status, torch.int32), n, D, _stream()), "alvq_eigh_f64")
+    lam, V, status = _empty(cov, torch.float64, n, D), _empty(cov, torch.float64, n, D, D, 2), _empty(cov, torch.int32, n)
+    _call("alvq_eigh_f64", _ptr(ar, torch.float64, "cov"), _ptr(lam, torch.float64), _ptr(V, torch.float64),
+          _ptr(status, torch.int32), n, D)
     return lam, torch.view_as_complex(V), status
 
 
@@ -1420,31 +1375,25 @@ def music(vectors, values, mics, cand, n_sources, fs, n_fft, c, f_lo, f_hi):
     vr = _c128(vectors, (B, F, D, D), "music", "vectors")
     if values.dtype != torch.float64 or tuple(values.shape) != (B, F, D):
         raise RuntimeError("music: values must be float64 %s (got %s %s)" % ((B, F, D), values.dtype, tuple(values.shape)))
-    if mics.dim() not in (2, 3) or tuple(mics.shape[-2:]) != (D, 3) or (mics.dim() == 3 and mics.shape[0] != B):
-        raise RuntimeError("music: mics must be (%d, 3) or (%d, %d, 3) (got %s)" % (D, B, D, tuple(mics.shape)))
-    if cand.dim() not in (2, 3) or cand.shape[-1] != 3 or (cand.dim() == 3 and cand.shape[0] != B):
-        raise RuntimeError("music: cand must be (G, 3) or (%d, G, 3) (got %s)" % (B, tuple(cand.shape)))
-    values, mics, cand = values.contiguous(), mics.contiguous(), cand.contiguous()
-    G = cand.shape[-2]
-    out = torch.empty((B, G), device=vectors.device, dtype=torch.float64)
-    best = torch.empty((B,), device=vectors.device, dtype=torch.int32)
-    status = torch.empty((B,), device=vectors.device, dtype=torch.int32)
-    _check(lib().alvq_music_f64(_ptr(vr, torch.float64, "vectors"), _ptr(values, torch.float64, "values"),
-                                _ptr(mics, torch.float64, "mics"), _ptr(cand, torch.float64, "cand"), _ptr(out, torch.float64),
-                                _ptr(best, torch.int32), _ptr(status, torch.int32), B, D, F, G, int(n_sources), float(fs), int(n_fft),
-                                float(c), int(f_lo), int(f_hi), 1 if mics.dim() == 3 else 0, 1 if cand.dim() == 3 else 0, _stream()),
-           "alvq_music_f64")
+    mics, mics_per_item = _positions("music", "mics", mics, B, D)
+    cand, cand_per_item = _positions("music", "cand", cand, B, "G")
+    values, G = values.contiguous(), cand.shape[-2]
+    out, best, status = _empty(vectors, torch.float64, B, G), _empty(vectors, torch.int32, B), _empty(vectors, torch.int32, B)
+    _call("alvq_music_f64", _ptr(vr, torch.float64, "vectors"), _ptr(values, torch.float64, "values"),
+          _ptr(mics, torch.float64, "mics"), _ptr(cand, torch.float64, "cand"), _ptr(out, torch.float64),
+          _ptr(best, torch.int32), _ptr(status, torch.int32), B, D, F, G, int(n_sources), float(fs), int(n_fft), float(c),
+          int(f_lo), int(f_hi), int(mics_per_item), int(cand_per_item))
     return out, best, status
 
 
+# ----------------------------------------------------------------------------------------------- t-SNE
 def tsne_code_sqdist(codes):
     """int32 (N, L) code sequences -> (N, N) fp32 squared distances of their one-hot expansions (alvq_tsne_code_sqdist_f32)."""
     if codes.dim() != 2:
         raise RuntimeError("tsne_code_sqdist: codes must be (N, L) (got %s)" % (tuple(codes.shape),))
     N, L = codes.shape
-    d2 = torch.empty((N, N), device=codes.device, dtype=torch.float32)
-    _check(lib().alvq_tsne_code_sqdist_f32(_ptr(codes, torch.int32, "codes"), _ptr(d2), N, L, _stream()),
-           "alvq_tsne_code_sqdist_f32")
+    d2 = _empty(codes, torch.float32, N, N)
+    _call("alvq_tsne_code_sqdist_f32", _ptr(codes, torch.int32, "codes"), _ptr(d2), N, L)
     return d2
 
 
@@ -1453,14 +1402,10 @@ def tsne_affinities(P, perplexity):
     N = P.shape[0]
     if P.dim() != 2 or P.shape[1] != N:
         raise RuntimeError("tsne_affinities: P must be (N, N) (got %s)" % (tuple(P.shape),))
-    nbytes = lib().alvq_tsne_affinities_workspace_bytes(N)
-    if nbytes < 0:
-        raise RuntimeError("tsne_affinities: N=%d out of range" % N)
-    beta = torch.empty((N,), device=P.device, dtype=torch.float64)
-    S = torch.empty((N,), device=P.device, dtype=torch.float64)
-    ws = torch.empty((nbytes,), device=P.device, dtype=torch.uint8)
-    _check(lib().alvq_tsne_affinities_f32(_ptr(P, name="P"), _ptr(beta, torch.float64), _ptr(S, torch.float64),
-                                          _ptr(ws, torch.uint8), N, float(perplexity), _stream()), "alvq_tsne_affinities_f32")
+    ws = _scratch(lib().alvq_tsne_affinities_workspace_bytes(N), P, "tsne_affinities: N=%d out of range" % N)
+    beta, S = _empty(P, torch.float64, N), _empty(P, torch.float64, N)
+    _call("alvq_tsne_affinities_f32", _ptr(P, name="P"), _ptr(beta, torch.float64), _ptr(S, torch.float64),
+          _ptr(ws, torch.uint8), N, float(perplexity))
     return beta, S
 
 
@@ -1473,16 +1418,11 @@ def tsne_descend(P, Y, update, gains, grad, stats, n_iter, exaggeration, momentu
             raise RuntimeError("tsne_descend: %s must be (%d, 2) (got %s)" % (name, N, tuple(t.shape)))
     if P.shape != (N, N) or stats.numel() < 2:
         raise RuntimeError("tsne_descend: P must be (%d, %d) and stats hold 2 values" % (N, N))
-    nbytes = lib().alvq_tsne_descend_workspace_bytes(N)
-    if nbytes < 0:
-        raise RuntimeError("tsne_descend: N=%d out of range" % N)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((nbytes,), device=Y.device, dtype=torch.uint8)
+    workspace = _scratch(lib().alvq_tsne_descend_workspace_bytes(N), Y, "tsne_descend: N=%d out of range" % N, workspace)
     f64 = torch.float64
-    _check(lib().alvq_tsne_descend_f64(_ptr(P, name="P"), _ptr(Y, f64, "Y"), _ptr(update, f64, "update"),
-                                       _ptr(gains, f64, "gains"), _ptr(grad, f64, "grad"), _ptr(stats, f64, "stats"),
-                                       _ptr(workspace, torch.uint8, "workspace"), N, int(n_iter), float(exaggeration),
-                                       float(momentum), float(learning_rate), _stream()), "alvq_tsne_descend_f64")
+    _call("alvq_tsne_descend_f64", _ptr(P, name="P"), _ptr(Y, f64, "Y"), _ptr(update, f64, "update"), _ptr(gains, f64, "gains"),
+          _ptr(grad, f64, "grad"), _ptr(stats, f64, "stats"), _ptr(workspace, torch.uint8, "workspace"), N, int(n_iter),
+          float(exaggeration), float(momentum), float(learning_rate))
     return workspace
 
 
@@ -1919,17 +1859,13 @@ def kmeans_update(x, labels, labels_old, centers_old, centers_new, counts, stats
         raise RuntimeError("kmeans_update: centres must be (%d, %d) and labels (%d,)" % (K, D, N))
     if labels_old is not None and labels_old.shape != (N,):
         raise RuntimeError("kmeans_update: labels_old must be (%d,)" % N)
-    nbytes = lib().alvq_kmeans_update_workspace_bytes(N, K, D)
-    if nbytes < 0:
-        raise RuntimeError("kmeans_update: N=%d, K=%d, D=%d out of range" % (N, K, D))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
+    workspace = _scratch(lib().alvq_kmeans_update_workspace_bytes(N, K, D), x,
+                         "kmeans_update: N=%d, K=%d, D=%d out of range" % (N, K, D), workspace)
     i64 = torch.int64
-    _check(lib().alvq_kmeans_update_f32(_ptr(x, name="x"), _ptr(labels, i64, "labels"), _ptr(labels_old, i64, "labels_old"),
-                                        _ptr(centers_old, name="centers_old"), _ptr(centers_new, name="centers_new"),
-                                        _ptr(counts, torch.int32, "counts"), _ptr(stats, torch.float64, "stats"),
-                                        _ptr(flags, torch.int32, "flags"), _ptr(workspace, torch.uint8, "workspace"), N, K, D,
-                                        float(tol), _stream()), "alvq_kmeans_update_f32")
+    _call("alvq_kmeans_update_f32", _ptr(x, name="x"), _ptr(labels, i64, "labels"), _ptr(labels_old, i64, "labels_old"),
+          _ptr(centers_old, name="centers_old"), _ptr(centers_new, name="centers_new"), _ptr(counts, torch.int32, "counts"),
+          _ptr(stats, torch.float64, "stats"), _ptr(flags, torch.int32, "flags"), _ptr(workspace, torch.uint8, "workspace"), N,
+          K, D, float(tol))
     return workspace
 
 
@@ -1939,25 +1875,20 @@ def kmeans_inertia(x, labels, centers):
     K = centers.shape[0]
     if centers.shape != (K, D) or labels.shape != (N,):
         raise RuntimeError("kmeans_inertia: centres must be (K, %d) and labels (%d,)" % (D, N))
-    out = torch.empty((1,), device=x.device, dtype=torch.float64)
+    out = _empty(x, torch.float64, 1)
     ws = torch.empty((lib().alvq_kmeans_inertia_workspace_bytes(N),), device=x.device, dtype=torch.uint8)
-    _check(lib().alvq_kmeans_inertia_f32(_ptr(x, name="x"), _ptr(labels, torch.int64, "labels"), _ptr(centers, name="centers"),
-                                         _ptr(out, torch.float64), _ptr(ws, torch.uint8), N, K, D, _stream()),
-           "alvq_kmeans_inertia_f32")
+    _call("alvq_kmeans_inertia_f32", _ptr(x, name="x"), _ptr(labels, torch.int64, "labels"), _ptr(centers, name="centers"),
+          _ptr(out, torch.float64), _ptr(ws, torch.uint8), N, K, D)
     return out
 
 
 def kmeans_col_stats(x):
     """(mean (D,) fp32, var_mean (1,) fp64) of the rows of x (alvq_kmeans_col_stats_f32)."""
     N, D = _rows(x, "kmeans_col_stats: x")
-    nbytes = lib().alvq_kmeans_col_stats_workspace_bytes(N, D)
-    if nbytes < 0:
-        raise RuntimeError("kmeans_col_stats: N=%d, D=%d out of range" % (N, D))
-    mean = torch.empty((D,), device=x.device, dtype=torch.float32)
-    var_mean = torch.empty((1,), device=x.device, dtype=torch.float64)
-    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
-    _check(lib().alvq_kmeans_col_stats_f32(_ptr(x, name="x"), _ptr(mean), _ptr(var_mean, torch.float64), _ptr(ws, torch.uint8),
-                                           N, D, _stream()), "alvq_kmeans_col_stats_f32")
+    ws = _scratch(lib().alvq_kmeans_col_stats_workspace_bytes(N, D), x, "kmeans_col_stats: N=%d, D=%d out of range" % (N, D))
+    mean, var_mean = _empty(x, torch.float32, D), _empty(x, torch.float64, 1)
+    _call("alvq_kmeans_col_stats_f32", _ptr(x, name="x"), _ptr(mean), _ptr(var_mean, torch.float64), _ptr(ws, torch.uint8), N,
+          D)
     return mean, var_mean
 
 
@@ -1967,8 +1898,7 @@ def kmeans_add_rows(x, v, alpha, out=None):
     if v.shape != (D,):
         raise RuntimeError("kmeans_add_rows: v must be (%d,)" % D)
     out = torch.empty_like(x) if out is None else out
-    _check(lib().alvq_kmeans_add_rows_f32(_ptr(x, name="x"), _ptr(v, name="v"), _ptr(out, name="out"), N, D, float(alpha),
-                                          _stream()), "alvq_kmeans_add_rows_f32")
+    _call("alvq_kmeans_add_rows_f32", _ptr(x, name="x"), _ptr(v, name="v"), _ptr(out, name="out"), N, D, float(alpha))
     return out
 
 
@@ -1980,13 +1910,8 @@ def kmeans_plusplus(x, K, first, uniforms):
     if K > 1 and (uniforms is None or uniforms.shape[0] != K - 1):
         raise RuntimeError("kmeans_plusplus: uniforms must be (%d, T)" % (K - 1))
     T = max(T, 1)
-    nbytes = lib().alvq_kmeans_plusplus_workspace_bytes(N, T)
-    if nbytes < 0:
-        raise RuntimeError("kmeans_plusplus: N=%d, T=%d out of range" % (N, T))
-    centers = torch.empty((K, D), device=x.device, dtype=torch.float32)
-    indices = torch.empty((K,), device=x.device, dtype=torch.int64)
-    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
-    _check(lib().alvq_kmeans_plusplus_f32(_ptr(x, name="x"), _ptr(uniforms if K > 1 else None, torch.float64, "uniforms"),
-                                          _ptr(centers), indices.data_ptr(), _ptr(ws, torch.uint8), N, K, D, T, int(first),
-                                          _stream()), "alvq_kmeans_plusplus_f32")
+    ws = _scratch(lib().alvq_kmeans_plusplus_workspace_bytes(N, T), x, "kmeans_plusplus: N=%d, T=%d out of range" % (N, T))
+    centers, indices = _empty(x, torch.float32, K, D), _empty(x, torch.int64, K)
+    _call("alvq_kmeans_plusplus_f32", _ptr(x, name="x"), _ptr(uniforms if K > 1 else None, torch.float64, "uniforms"),
+          _ptr(centers), indices.data_ptr(), _ptr(ws, torch.uint8), N, K, D, T, int(first))
     return centers, indices

@@ -31,39 +31,17 @@ import collections
 import torch
 
 from . import _native as N
+from . import _rules as rules
 from . import localization as LOC
-from .dereverberation import _nonneg
+from ._rules import MAX_FRAMES, MAX_MICROPHONES  # noqa: F401 -- public here
 from .front_end import HOP, N_FFT, SOUND_SPEED
-from .localization import _int_in, _on_gpu, _positive
 
 Cov = collections.namedtuple("Cov", "cov status")
 Weights = collections.namedtuple("Weights", "w status")
 Beam = collections.namedtuple("Beam", "spec weights status")
 Gev = collections.namedtuple("Gev", "w rtf gain status")
 
-MAX_MICROPHONES = 8
-MAX_FRAMES = 65535
 METHODS = {"das": N.BEAMFORM_DAS, "mvdr": N.BEAMFORM_MVDR, "souden": N.BEAMFORM_SOUDEN}
-
-
-def _bins(who, what, B, F):
-    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1:
-        raise ValueError("%s: need 1 <= B <= 65535, F >= 1 and B F <= 2^31 - 1, got %s" % (who, what))
-
-
-def _spec4(who, spec):
-    """spec as (B, D, F, T), checked; whether it came with a batch dimension."""
-    if not isinstance(spec, torch.Tensor) or spec.dim() not in (3, 4):
-        raise ValueError("%s: spec must be a (D, F, T) or (B, D, F, T) tensor" % who)
-    if spec.dtype not in (torch.complex64, torch.complex128):
-        raise ValueError("%s: spec must be complex64 or complex128, got %s" % (who, spec.dtype))
-    x = spec[None] if spec.dim() == 3 else spec
-    B, D, F, T = x.shape
-    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1 or T < 1 or T > MAX_FRAMES:
-        raise ValueError("%s: need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1 and 1 <= T <= 65535, got shape %s" % (who, tuple(spec.shape)))
-    if D < 1 or D > MAX_MICROPHONES:
-        raise ValueError("%s: need 1 <= D <= 8 microphones, got D = %d" % (who, D))
-    return x, spec.dim() == 4
 
 
 def _mask3(who, name, mask, dims, batched):
@@ -94,16 +72,14 @@ def steering_vectors(mics, source, F, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, ref=
     if mics.dim() == 3 and mics.shape[0] != B:
         raise ValueError("%s: mics holds %d items, source %d" % (who, mics.shape[0], B))
     D = mics.shape[-2]
-    if D < 1 or D > MAX_MICROPHONES:
-        raise ValueError("%s: need 1 <= D <= 8 microphones, got D = %d" % (who, D))
-    _int_in(who, "F", F, 1, 2 ** 24)
-    _bins(who, "B = %d, F = %d" % (B, F), B, F)
-    _positive(who, "fs", fs)
-    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-    _positive(who, "c", c)
-    _int_in(who, "ref", ref, 0, D - 1)
-    _on_gpu(who, mics, "mics")
-    _on_gpu(who, source, "source")
+    rules.microphones(who, D)
+    rules.int_in(who, "F", F, 1, 2 ** 24)
+    rules.bins(who, "B = %d, F = %d" % (B, F), B, F)
+    rules.positive(who, "fs", fs)
+    rules.int_in(who, "n_fft", n_fft, 2, 2 ** 24)
+    rules.positive(who, "c", c)
+    rules.int_in(who, "ref", ref, 0, D - 1)
+    rules.all_on_gpu(who, mics=mics, source=source)
     src = source.expand(B, 3) if source.dim() == 1 else source
     A, status = N.steering_vectors(mics, src, F, fs, n_fft, c, ref)
     return (A, status) if batched else (A[0], status[0])
@@ -114,14 +90,11 @@ def spatial_covariance(spec, mask=None):
     weights >= 0, on the GPU -> ``Cov(cov, status)``: cov (B, F, D, D) complex128, exactly Hermitian, and status (B, F) int32
     (no B for a (D, F, T) spec)."""
     who = "spatial_covariance"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     if mask is not None:
         mask = _mask3(who, "mask", mask, x.shape, batched)
-    _on_gpu(who, x, "spec")
-    if mask is not None:
-        _on_gpu(who, mask, "mask")
-    cov, status = N.spatial_covariance(x, mask)
-    return Cov(cov, status) if batched else Cov(cov[0], status[0])
+    rules.all_on_gpu(who, spec=x, mask=mask)
+    return rules.unbatch(Cov(*N.spatial_covariance(x, mask)), batched)
 
 
 def weights(method, noise_cov=None, steering=None, speech_cov=None, ref=0, loading=1e-6):
@@ -155,30 +128,26 @@ def weights(method, noise_cov=None, steering=None, speech_cov=None, ref=0, loadi
         if t is not None and tuple(t.shape) != (B, F, D, D):
             raise ValueError("%s: %s must be %s, got %s" % (who, name, (B, F, D, D) if batched else (F, D, D),
                                                            tuple(t.shape) if batched else tuple(t.shape[1:])))
-    if D < 1 or D > MAX_MICROPHONES:
-        raise ValueError("%s: need 1 <= D <= 8 microphones, got D = %d" % (who, D))
-    _bins(who, "B = %d, F = %d" % (B, F), B, F)
-    _int_in(who, "ref", ref, 0, D - 1)
-    _nonneg(who, "loading", loading)
-    for name, t, _ in used:
-        _on_gpu(who, t, name)
-    w, status = N.beamform_weights(METHODS[method], B, D, F, noise_cov, speech_cov, steering, ref, float(loading))
-    return Weights(w, status) if batched else Weights(w[0], status[0])
+    rules.microphones(who, D)
+    rules.bins(who, "B = %d, F = %d" % (B, F), B, F)
+    rules.int_in(who, "ref", ref, 0, D - 1)
+    rules.nonneg(who, "loading", loading)
+    rules.all_on_gpu(who, noise_cov=noise_cov, steering=steering, speech_cov=speech_cov)
+    out = Weights(*N.beamform_weights(METHODS[method], B, D, F, noise_cov, speech_cov, steering, ref, float(loading)))
+    return rules.unbatch(out, batched)
 
 
 def apply(spec, w):
     """y = w^H x: spec (D, F, T) or (B, D, F, T), complex64 or complex128, and w (F, D) or (B, F, D) complex128 on the GPU ->
     (F, T) or (B, F, T) of spec's dtype."""
     who = "apply"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     B, D, F, T = x.shape
     want = (B, F, D) if batched else (F, D)
     if not isinstance(w, torch.Tensor) or w.dtype != torch.complex128 or tuple(w.shape) != want:
         raise ValueError("%s: w must be a complex128 %s tensor for spec %s" % (who, want, tuple(spec.shape)))
-    _on_gpu(who, x, "spec")
-    _on_gpu(who, w, "w")
-    y = N.beamform_apply(x, w if batched else w[None])
-    return y if batched else y[0]
+    rules.all_on_gpu(who, spec=x, w=w)
+    return rules.unbatch(N.beamform_apply(x, w if batched else w[None]), batched)
 
 
 def _geometry_rules(who, dims, batched, mics, source, fs, n_fft, c, ref):
@@ -190,10 +159,10 @@ def _geometry_rules(who, dims, batched, mics, source, fs, n_fft, c, ref):
     if not isinstance(source, torch.Tensor) or source.dtype != torch.float64 \
             or tuple(source.shape) not in (((3,), (B, 3)) if batched else ((3,),)):
         raise ValueError("%s: source must be a float64 (3,)%s tensor" % (who, " or (%d, 3)" % B if batched else ""))
-    _positive(who, "fs", fs)
-    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-    _positive(who, "c", c)
-    _int_in(who, "ref", ref, 0, D - 1)
+    rules.positive(who, "fs", fs)
+    rules.int_in(who, "n_fft", n_fft, 2, 2 ** 24)
+    rules.positive(who, "c", c)
+    rules.int_in(who, "ref", ref, 0, D - 1)
 
 
 def _mvdr_rules(who, dims, batched, mics, source, noise_mask, speech_mask, ref, loading, fs, n_fft, c):
@@ -210,17 +179,11 @@ def _mvdr_rules(who, dims, batched, mics, source, noise_mask, speech_mask, ref, 
         noise_mask = _mask3(who, "noise_mask", noise_mask, dims, batched)
     if speech_mask is not None:
         speech_mask = _mask3(who, "speech_mask", speech_mask, dims, batched)
-    _int_in(who, "ref", ref, 0, dims[1] - 1)
-    _nonneg(who, "loading", loading)
+    rules.int_in(who, "ref", ref, 0, dims[1] - 1)
+    rules.nonneg(who, "loading", loading)
     if geometry:
         _geometry_rules(who, dims, batched, mics, source, fs, n_fft, c, ref)
     return geometry, noise_mask, speech_mask
-
-
-def _all_on_gpu(who, **tensors):
-    for name, t in tensors.items():
-        if t is not None:
-            _on_gpu(who, t, name)
 
 
 def _steer(x, mics, source, fs, n_fft, c, ref):
@@ -247,19 +210,15 @@ def _mvdr(x, geometry, mics, source, noise_mask, speech_mask, ref, loading, fs, 
     return Beam(apply(x, w.w), w.w, status | w.status)
 
 
-def _unbatch(beam, batched):
-    return beam if batched else Beam(beam.spec[0], beam.weights[0], beam.status[0])
-
-
 def delay_and_sum(spec, mics, source, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, ref=0):
     """Delay-and-sum towards source: spec (D, F, T) or (B, D, F, T), mics (D, 3) or (B, D, 3), source (3,) or (B, 3) ->
     ``Beam(spec, weights, status)``: ``apply(spec, weights("das", steering=A).w)`` with A = ``steering_vectors(mics, source,
     F, ...)``; status (B, F) is 0.  A non-finite coordinate gives a NaN item: ``steering_vectors`` tells."""
     who = "delay_and_sum"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     _geometry_rules(who, x.shape, batched, mics, source, fs, n_fft, c, ref)
-    _all_on_gpu(who, spec=x, mics=mics, source=source)
-    return _unbatch(_das(x, mics, source, fs, n_fft, c, ref), batched)
+    rules.all_on_gpu(who, spec=x, mics=mics, source=source)
+    return rules.unbatch(_das(x, mics, source, fs, n_fft, c, ref), batched)
 
 
 def mvdr(spec, mics=None, source=None, noise_mask=None, speech_mask=None, ref=0, loading=1e-6, fs=16000, n_fft=N_FFT,
@@ -274,11 +233,11 @@ def mvdr(spec, mics=None, source=None, noise_mask=None, speech_mask=None, ref=0,
     coordinate makes the item's A NaN, so the denominator of every one of its bins is NaN: status 2 and the reference
     microphone in all of them (``steering_vectors`` names the cause, its bit 4; it is not repeated here)."""
     who = "mvdr"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     geometry, noise_mask, speech_mask = _mvdr_rules(who, x.shape, batched, mics, source, noise_mask, speech_mask, ref, loading, fs,
                                                     n_fft, c)
-    _all_on_gpu(who, spec=x, mics=mics, source=source, noise_mask=noise_mask, speech_mask=speech_mask)
-    return _unbatch(_mvdr(x, geometry, mics, source, noise_mask, speech_mask, ref, loading, fs, n_fft, c), batched)
+    rules.all_on_gpu(who, spec=x, mics=mics, source=source, noise_mask=noise_mask, speech_mask=speech_mask)
+    return rules.unbatch(_mvdr(x, geometry, mics, source, noise_mask, speech_mask, ref, loading, fs, n_fft, c), batched)
 
 
 def gev_weights(noise_cov, speech_cov, ref=0, loading=1e-6):
@@ -303,15 +262,12 @@ def gev_weights(noise_cov, speech_cov, ref=0, loading=1e-6):
         if tuple(t.shape) != (B, F, D, D):
             raise ValueError("%s: %s must be %s, got %s" % (who, name, (B, F, D, D) if batched else (F, D, D),
                                                            tuple(t.shape) if batched else tuple(t.shape[1:])))
-    if D < 1 or D > MAX_MICROPHONES:
-        raise ValueError("%s: need 1 <= D <= 8 microphones, got D = %d" % (who, D))
-    _bins(who, "B = %d, F = %d" % (B, F), B, F)
-    _int_in(who, "ref", ref, 0, D - 1)
-    _nonneg(who, "loading", loading)
-    _on_gpu(who, pn, "noise_cov")
-    _on_gpu(who, ps, "speech_cov")
-    out = Gev(*N.beamform_gev(pn, ps, ref, float(loading)))
-    return out if batched else Gev(*(t[0] for t in out))
+    rules.microphones(who, D)
+    rules.bins(who, "B = %d, F = %d" % (B, F), B, F)
+    rules.int_in(who, "ref", ref, 0, D - 1)
+    rules.nonneg(who, "loading", loading)
+    rules.all_on_gpu(who, noise_cov=pn, speech_cov=ps)
+    return rules.unbatch(Gev(*N.beamform_gev(pn, ps, ref, float(loading))), batched)
 
 
 def gev(spec, noise_mask, speech_mask, ref=0, loading=1e-6):
@@ -319,17 +275,17 @@ def gev(spec, noise_mask, speech_mask, ref=0, loading=1e-6):
     spatial_covariance(spec, speech_mask).cov, ref, loading).w)`` -> ``Beam(spec, weights, status)`` as ``mvdr`` returns it,
     status the covariances' OR the weights'."""
     who = "gev"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     if noise_mask is None or speech_mask is None:
         raise ValueError("%s: both noise_mask and speech_mask are needed" % who)
     noise_mask = _mask3(who, "noise_mask", noise_mask, x.shape, batched)
     speech_mask = _mask3(who, "speech_mask", speech_mask, x.shape, batched)
-    _int_in(who, "ref", ref, 0, x.shape[1] - 1)
-    _nonneg(who, "loading", loading)
-    _all_on_gpu(who, spec=x, noise_mask=noise_mask, speech_mask=speech_mask)
+    rules.int_in(who, "ref", ref, 0, x.shape[1] - 1)
+    rules.nonneg(who, "loading", loading)
+    rules.all_on_gpu(who, spec=x, noise_mask=noise_mask, speech_mask=speech_mask)
     noise, speech = spatial_covariance(x, noise_mask), spatial_covariance(x, speech_mask)
     w = gev_weights(noise.cov, speech.cov, ref=ref, loading=loading)
-    return _unbatch(Beam(apply(x, w.w), w.w, noise.status | speech.status | w.status), batched)
+    return rules.unbatch(Beam(apply(x, w.w), w.w, noise.status | speech.status | w.status), batched)
 
 
 def locate_and_beamform(spec, mics, candidates, ref=0, loading=1e-6, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=None):
@@ -352,29 +308,20 @@ def beamform_waves(waves, mics=None, source=None, method="mvdr", noise_mask=None
     "mvdr") or ``delay_and_sum(spec, mics, source, ...)`` (method "das") on spec = ``N.stft_complex`` of the B D rows, which
     has F = n_fft / 2 + 1 bins and T = 1 + S / hop frames: the masks are (B, F, T).  Their rules, under this function's name."""
     who = "beamform_waves"
-    if not isinstance(waves, torch.Tensor) or waves.dim() != 3:
-        raise ValueError("%s: waves must be a (B, D, S) tensor" % who)
-    if waves.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s: waves must be float32 or float64, got %s" % (who, waves.dtype))
+    rules.waves3(who, waves)
     if method not in ("mvdr", "das"):
         raise ValueError("%s: method must be 'mvdr' or 'das', got %r" % (who, method))
     if method == "das" and (noise_mask is not None or speech_mask is not None):
         raise ValueError("%s: method 'das' takes no mask" % who)
+    dims = rules.stft_dims(who, waves, n_fft, hop)
     B, D, S = waves.shape
-    if B < 1 or B > 65535 or D < 1 or D > MAX_MICROPHONES or S < 1:
-        raise ValueError("%s: need 1 <= B <= 65535, 1 <= D <= 8 and S >= 1, got shape %s" % (who, tuple(waves.shape)))
-    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-    _int_in(who, "hop", hop, 1, n_fft)
-    dims = (B, D, n_fft // 2 + 1, 1 + S // hop)
-    if dims[3] > MAX_FRAMES or B * dims[2] > 2 ** 31 - 1:
-        raise ValueError("%s: need B F <= 2^31 - 1 and T = 1 + S / hop <= 65535, got F = %d, T = %d" % (who, dims[2], dims[3]))
     geometry = True
     if method == "das":
         _geometry_rules(who, dims, True, mics, source, fs, n_fft, c, ref)
     else:
         geometry, noise_mask, speech_mask = _mvdr_rules(who, dims, True, mics, source, noise_mask, speech_mask, ref, loading, fs,
                                                         n_fft, c)
-    _all_on_gpu(who, waves=waves, mics=mics, source=source, noise_mask=noise_mask, speech_mask=speech_mask)
+    rules.all_on_gpu(who, waves=waves, mics=mics, source=source, noise_mask=noise_mask, speech_mask=speech_mask)
     spec = N.stft_complex(waves.reshape(B * D, S).contiguous(), n_fft, hop).view(dims)
     if method == "das":
         beam = _das(spec, mics, source, fs, n_fft, c, ref)

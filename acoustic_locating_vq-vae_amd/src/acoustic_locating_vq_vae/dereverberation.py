@@ -26,32 +26,20 @@ power at all in the bin, or 2 = a Cholesky pivot <= 0 or not finite (always wher
 Nothing here reads it: the caller does, when it can sync.
 """
 import collections
-import math
 
-import numpy as np
 import torch
 
 from . import _native as N
+from . import _rules as rules
+from ._rules import MAX_FRAMES, MAX_MICROPHONES  # noqa: F401 -- public here
 from .front_end import HOP, N_FFT
 
 WPE = collections.namedtuple("WPE", "spec status")
 
-MAX_MICROPHONES = 8
 MAX_FILTER = 64          # D taps
 MAX_DELAY = 64
 MAX_ITERATIONS = 16
 MAX_PSD_CONTEXT = 64
-MAX_FRAMES = 65535
-
-
-def _int_in(who, name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or v > hi:
-        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
-
-
-def _nonneg(who, name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0):
-        raise ValueError("%s: %s must be a finite number >= 0, got %r" % (who, name, v))
 
 
 def wpe(spec, taps=10, delay=3, iterations=3, psd_context=0, eps=1e-10, loading=1e-10):
@@ -62,20 +50,18 @@ def wpe(spec, taps=10, delay=3, iterations=3, psd_context=0, eps=1e-10, loading=
         raise ValueError("wpe: spec must be an (F, T), (B, F, T) or (B, D, F, T) tensor")
     if spec.dtype not in (torch.complex64, torch.complex128):
         raise ValueError("wpe: spec must be complex64 or complex128, got %s" % spec.dtype)
-    _int_in("wpe", "taps", taps, 1, MAX_FILTER)
-    _int_in("wpe", "delay", delay, 0, MAX_DELAY)
-    _int_in("wpe", "iterations", iterations, 1, MAX_ITERATIONS)
-    _int_in("wpe", "psd_context", psd_context, 0, MAX_PSD_CONTEXT)
-    _nonneg("wpe", "eps", eps)
-    _nonneg("wpe", "loading", loading)
+    rules.int_in("wpe", "taps", taps, 1, MAX_FILTER)
+    rules.int_in("wpe", "delay", delay, 0, MAX_DELAY)
+    rules.int_in("wpe", "iterations", iterations, 1, MAX_ITERATIONS)
+    rules.int_in("wpe", "psd_context", psd_context, 0, MAX_PSD_CONTEXT)
+    rules.nonneg("wpe", "eps", eps)
+    rules.nonneg("wpe", "loading", loading)
     x = {2: spec[None, None], 3: spec[:, None], 4: spec}[spec.dim()]
-    B, D, F, T = x.shape
-    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1 or T < 1 or T > MAX_FRAMES:
-        raise ValueError("wpe: need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1 and 1 <= T <= 65535, got shape %s" % (tuple(spec.shape),))
+    rules.frames("wpe", x.shape, spec.shape)
+    D = x.shape[1]
     if D < 1 or D > MAX_MICROPHONES or D * taps > MAX_FILTER:
         raise ValueError("wpe: need 1 <= D <= 8 microphones and D taps <= 64, got D = %d, taps = %d" % (D, taps))
-    if not x.is_cuda:
-        raise RuntimeError("wpe: spec must live on the GPU (got %s); the HIP path has no CPU fallback" % (x.device,))
+    rules.on_gpu("wpe", x, "spec")
     out, status = N.wpe(x, taps, delay, iterations, psd_context, float(eps), float(loading))
     if spec.dim() == 2:
         return WPE(out[0, 0], status[0])
@@ -89,8 +75,7 @@ def dereverberate(wave, n_fft=N_FFT, hop=HOP, **wpe_kwargs):
         raise ValueError("dereverberate: wave must be an (S,) or (B, S) tensor")
     if wave.dtype not in (torch.float32, torch.float64):
         raise ValueError("dereverberate: wave must be float32 or float64, got %s" % wave.dtype)
-    if not wave.is_cuda:
-        raise RuntimeError("dereverberate: wave must live on the GPU (got %s); the HIP path has no CPU fallback" % (wave.device,))
+    rules.on_gpu("dereverberate", wave, "wave")
     rows = (wave[None] if wave.dim() == 1 else wave).contiguous()
     out = N.istft(wpe(N.stft_complex(rows, n_fft, hop), **wpe_kwargs).spec, n_fft, hop, rows.shape[1])
     return out[0] if wave.dim() == 1 else out

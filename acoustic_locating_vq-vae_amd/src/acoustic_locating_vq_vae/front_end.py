@@ -47,6 +47,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import _rules as rules
 from .data_preprocessing import SPEC_FRAMES
 
 N_FFT, HOP = 400, 160        # genereate_dataset.py:73-74 at fs = 16 kHz
@@ -100,8 +101,7 @@ def griffin_lim(spec, power=2.0, n_iter=32, momentum=0.99, length=None, init=Non
         raise ValueError("griffin_lim: n_iter must be >= 0, got %r" % (n_iter,))
     if power <= 0:
         raise ValueError("griffin_lim: power must be > 0, got %r" % (power,))
-    if not spec.is_cuda:
-        raise RuntimeError("griffin_lim: spec must live on the GPU (got %s); the HIP path has no CPU fallback" % spec.device)
+    rules.on_gpu("griffin_lim", spec, "spec")
     cdtype = torch.complex128 if spec.dtype == torch.float64 else torch.complex64
     length = hop * (T - 1) if length is None else int(length)
     mag = (spec if power == 1.0 else spec.pow(1.0 / power)).contiguous()

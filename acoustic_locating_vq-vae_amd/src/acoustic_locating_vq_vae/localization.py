@@ -24,49 +24,18 @@ it can sync.  The band is given in bins, (f_lo, f_hi) inclusive; None means (1, 
 import collections
 import math
 
-import numpy as np
 import torch
 
 from . import _native as N
+from . import _rules as rules
 from . import front_end as FE
+from ._rules import MAX_FRAMES, MAX_MICROPHONES  # noqa: F401 -- public here
 from .front_end import N_FFT, SOUND_SPEED
 
 GCC = collections.namedtuple("GCC", "corr lags")
 SRP = collections.namedtuple("SRP", "map best status")
 Ring = collections.namedtuple("Ring", "theta source map status")
 Music = collections.namedtuple("Music", "null best status values")
-
-MAX_MICROPHONES = 8
-MAX_FRAMES = 65535
-
-
-def _int_in(who, name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or v > hi:
-        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
-
-
-def _positive(who, name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
-        raise ValueError("%s: %s must be a finite number > 0, got %r" % (who, name, v))
-
-
-def _spec4(who, spec, n_fft=None):
-    """spec as (B, D, F, T), checked; whether it came with a batch dimension."""
-    if not isinstance(spec, torch.Tensor) or spec.dim() not in (3, 4):
-        raise ValueError("%s: spec must be a (D, F, T) or (B, D, F, T) tensor" % who)
-    if spec.dtype not in (torch.complex64, torch.complex128):
-        raise ValueError("%s: spec must be complex64 or complex128, got %s" % (who, spec.dtype))
-    x = spec[None] if spec.dim() == 3 else spec
-    B, D, F, T = x.shape
-    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1 or T < 1 or T > MAX_FRAMES:
-        raise ValueError("%s: need 1 <= B <= 65535, F >= 1, B F <= 2^31 - 1 and 1 <= T <= 65535, got shape %s" % (who, tuple(spec.shape)))
-    if D < 2 or D > MAX_MICROPHONES:
-        raise ValueError("%s: need 2 <= D <= 8 microphones, got D = %d" % (who, D))
-    if n_fft is not None:
-        _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-        if F != n_fft // 2 + 1:
-            raise ValueError("%s: %d frequency bins, n_fft=%d has %d" % (who, F, n_fft, n_fft // 2 + 1))
-    return x, spec.dim() == 4
 
 
 def _band(who, band, F):
@@ -77,47 +46,31 @@ def _band(who, band, F):
     if not isinstance(band, (tuple, list)) or len(band) != 2:
         raise ValueError("%s: band must be (f_lo, f_hi) in bins, got %r" % (who, band))
     lo, hi = band
-    _int_in(who, "band[0]", lo, 0, F - 1)
-    _int_in(who, "band[1]", hi, lo, F - 1)
+    rules.int_in(who, "band[0]", lo, 0, F - 1)
+    rules.int_in(who, "band[1]", hi, lo, F - 1)
     return int(lo), int(hi)
-
-
-def _on_gpu(who, t, name="spec"):
-    if not t.is_cuda:
-        raise RuntimeError("%s: %s must live on the GPU (got %s); the HIP path has no CPU fallback" % (who, name, t.device))
-
-
-def _geometry(who, name, t, B, rows=None):
-    """A float64 (n, 3) or (B, n, 3) tensor of positions."""
-    if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3) or t.shape[-1] != 3 or t.dtype != torch.float64:
-        raise ValueError("%s: %s must be a float64 (n, 3) or (B, n, 3) tensor" % (who, name))
-    if t.dim() == 3 and t.shape[0] != B:
-        raise ValueError("%s: %s holds %d items, spec %d" % (who, name, t.shape[0], B))
-    if t.shape[-2] < 1 or (rows is not None and t.shape[-2] != rows):
-        raise ValueError("%s: %s must hold %s positions, got %d" % (who, name, rows if rows is not None else ">= 1", t.shape[-2]))
 
 
 def cross_spectra(spec, band=None):
     """PHAT-weighted cross-spectra: spec (D, F, T) or (B, D, F, T), complex64 or complex128 on the GPU -> (P, F) or (B, P, F)
     complex128, 0 outside the band."""
-    x, batched = _spec4("cross_spectra", spec)
+    x, batched = rules.spec4("cross_spectra", spec, 2)
     lo, hi = _band("cross_spectra", band, x.shape[2])
-    _on_gpu("cross_spectra", x)
-    psi, _ = N.phat_cross_spectra(x, lo, hi)
-    return psi if batched else psi[0]
+    rules.on_gpu("cross_spectra", x, "spec")
+    return rules.unbatch(N.phat_cross_spectra(x, lo, hi)[0], batched)
 
 
 def gcc_phat(spec, max_lag, band=None, n_fft=N_FFT):
     """GCC-PHAT of every microphone pair at the integer lags -max_lag .. max_lag: ``GCC(corr, lags)`` with corr
     (B, P, 2 max_lag + 1) float64 (no B for a (D, F, T) spec) and lags (2 max_lag + 1,) int64, both on the GPU."""
-    x, batched = _spec4("gcc_phat", spec, n_fft)
-    _int_in("gcc_phat", "max_lag", max_lag, 0, n_fft // 2)
+    x, batched = rules.spec4("gcc_phat", spec, 2, n_fft)
+    rules.int_in("gcc_phat", "max_lag", max_lag, 0, n_fft // 2)
     lo, hi = _band("gcc_phat", band, x.shape[2])
-    _on_gpu("gcc_phat", x)
+    rules.on_gpu("gcc_phat", x, "spec")
     psi, _ = N.phat_cross_spectra(x, lo, hi)
     corr = N.gcc_phat(psi, n_fft, max_lag, lo, hi)
     lags = torch.arange(-int(max_lag), int(max_lag) + 1, device=x.device)
-    return GCC(corr if batched else corr[0], lags)
+    return GCC(rules.unbatch(corr, batched), lags)
 
 
 def tdoa(spec, max_lag, fs=16000, band=None, n_fft=N_FFT):
@@ -125,7 +78,7 @@ def tdoa(spec, max_lag, fs=16000, band=None, n_fft=N_FFT):
     minus the arrival at j.  The arg-max lag of ``gcc_phat`` (the lowest on ties) plus the vertex of the parabola through the
     peak and its neighbours, delta = 0.5 (r[-1] - r[+1]) / (r[-1] - 2 r[0] + r[+1]), where the peak is interior and that
     denominator is < 0; delta = 0 otherwise."""
-    _positive("tdoa", "fs", fs)
+    rules.positive("tdoa", "fs", fs)
     corr, lags = gcc_phat(spec, max_lag, band, n_fft)
     n = corr.shape[-1]
     # the lowest index of the maximum (torch.argmax does not promise which of several it returns); 0 for a row with a NaN
@@ -146,34 +99,29 @@ def srp_phat(spec, mics, candidates, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=
     """The SRP-PHAT map: spec (D, F, T) or (B, D, F, T) complex64 / complex128, microphones mics (D, 3) or (B, D, 3) and
     candidates (G, 3) or (B, G, 3), float64, all on the GPU -> ``SRP(map, best, status)``: map (B, G) float64, best (B,) int32
     (the arg-max, the lowest index on ties; -1 with a status), status (B,) int32 -- (G,) and two scalars for a (D, F, T) spec."""
-    x, batched = _spec4("srp_phat", spec, n_fft)
-    B, D = x.shape[0], x.shape[1]
-    _positive("srp_phat", "fs", fs)
-    _positive("srp_phat", "c", c)
-    lo, hi = _band("srp_phat", band, x.shape[2])
-    _geometry("srp_phat", "mics", mics, B, D)
-    _geometry("srp_phat", "candidates", candidates, B)
-    if B * candidates.shape[-2] > 2 ** 31 - 1:
-        raise ValueError("srp_phat: need B G <= 2^31 - 1, got B = %d, G = %d" % (B, candidates.shape[-2]))
-    _on_gpu("srp_phat", x)
-    _on_gpu("srp_phat", mics, "mics")
-    _on_gpu("srp_phat", candidates, "candidates")
+    x, batched = rules.spec4("srp_phat", spec, 2, n_fft)
+    lo, hi = _map_rules("srp_phat", x.shape[0], x.shape[1], x.shape[2], mics, candidates, fs, c, band)
+    rules.all_on_gpu("srp_phat", spec=x, mics=mics, candidates=candidates)
     psi, _ = N.phat_cross_spectra(x, lo, hi)
-    out, best, status = N.srp_phat(psi, mics, candidates, fs, n_fft, c, lo, hi)
-    return SRP(out, best, status) if batched else SRP(out[0], best[0], status[0])
+    return rules.unbatch(SRP(*N.srp_phat(psi, mics, candidates, fs, n_fft, c, lo, hi)), batched)
 
 
-def _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band):
-    """The rules ``music`` and ``music_from_covariance`` share, ValueErrors only -> the band in bins."""
-    _int_in(who, "n_sources", n_sources, 1, D - 1)
-    _positive(who, "fs", fs)
-    _positive(who, "c", c)
+def _map_rules(who, B, D, F, mics, candidates, fs, c, band):
+    """The rules of a map over candidates for D microphones and F bins, ValueErrors only -> the band in bins."""
+    rules.positive(who, "fs", fs)
+    rules.positive(who, "c", c)
     lo, hi = _band(who, band, F)
-    _geometry(who, "mics", mics, B, D)
-    _geometry(who, "candidates", candidates, B)
+    rules.positions(who, "mics", mics, B, D)
+    rules.positions(who, "candidates", candidates, B)
     if B * candidates.shape[-2] > 2 ** 31 - 1:
         raise ValueError("%s: need B G <= 2^31 - 1, got B = %d, G = %d" % (who, B, candidates.shape[-2]))
     return lo, hi
+
+
+def _music_rules(who, B, D, F, mics, candidates, n_sources, fs, c, band):
+    """The rules ``music`` and ``music_from_covariance`` share, ValueErrors only -> the band in bins."""
+    rules.int_in(who, "n_sources", n_sources, 1, D - 1)
+    return _map_rules(who, B, D, F, mics, candidates, fs, c, band)
 
 
 def _music(cov, cov_status, mics, candidates, n_sources, fs, n_fft, c, lo, hi):
@@ -203,15 +151,12 @@ def music(spec, mics, candidates, n_sources=1, fs=16000, n_fft=N_FFT, c=SOUND_SP
     (B, F, D) float64, the eigenvalues ascending: their profile tells how many sources there are -- (G,), two scalars and
     (F, D) for a (D, F, T) spec."""
     who = "music"
-    x, batched = _spec4(who, spec, n_fft)
+    x, batched = rules.spec4(who, spec, 2, n_fft)
     B, D, F = x.shape[0], x.shape[1], x.shape[2]
-    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band)
-    _on_gpu(who, x)
-    _on_gpu(who, mics, "mics")
-    _on_gpu(who, candidates, "candidates")
+    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, c, band)
+    rules.all_on_gpu(who, spec=x, mics=mics, candidates=candidates)
     cov, cov_status = N.spatial_covariance(x, None)
-    out = _music(cov, cov_status, mics, candidates, n_sources, fs, n_fft, c, lo, hi)
-    return out if batched else Music(out.null[0], out.best[0], out.status[0], out.values[0])
+    return rules.unbatch(_music(cov, cov_status, mics, candidates, n_sources, fs, n_fft, c, lo, hi), batched)
 
 
 def music_from_covariance(cov, mics, candidates, n_sources=1, fs=16000, n_fft=N_FFT, c=SOUND_SPEED, band=None):
@@ -226,24 +171,18 @@ def music_from_covariance(cov, mics, candidates, n_sources=1, fs=16000, n_fft=N_
     B, F, D = y.shape[0], y.shape[1], y.shape[2]
     if y.shape[3] != D or D < 2 or D > MAX_MICROPHONES:
         raise ValueError("%s: need square covariances of 2 <= D <= 8 microphones, got shape %s" % (who, tuple(cov.shape)))
-    if B < 1 or B > 65535 or F < 1 or B * F > 2 ** 31 - 1:
-        raise ValueError("%s: need 1 <= B <= 65535, F >= 1 and B F <= 2^31 - 1, got shape %s" % (who, tuple(cov.shape)))
-    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-    if F != n_fft // 2 + 1:
-        raise ValueError("%s: %d frequency bins, n_fft=%d has %d" % (who, F, n_fft, n_fft // 2 + 1))
-    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, n_fft, c, band)
-    _on_gpu(who, y, "cov")
-    _on_gpu(who, mics, "mics")
-    _on_gpu(who, candidates, "candidates")
-    out = _music(y, None, mics, candidates, n_sources, fs, n_fft, c, lo, hi)
-    return out if batched else Music(out.null[0], out.best[0], out.status[0], out.values[0])
+    rules.bins(who, "shape %s" % (tuple(cov.shape),), B, F)
+    rules.n_fft_bins(who, n_fft, F)
+    lo, hi = _music_rules(who, B, D, F, mics, candidates, n_sources, fs, c, band)
+    rules.all_on_gpu(who, cov=y, mics=mics, candidates=candidates)
+    return rules.unbatch(_music(y, None, mics, candidates, n_sources, fs, n_fft, c, lo, hi), batched)
 
 
 def ring_candidates(n_angles, receiver, room, R, z, device="cuda"):
     """The positions the dataset generator can produce, as candidates: ``(theta_grid (n,), points (n, 3))`` float64 on the GPU
     with theta_k = -pi + 2 pi k / n and points = min(receiver + (R cos theta, R sin theta, z), room)
     (``front_end.source_positions``, its clip to the room included)."""
-    _int_in("ring_candidates", "n_angles", n_angles, 1, 2 ** 31 - 1)
+    rules.int_in("ring_candidates", "n_angles", n_angles, 1, 2 ** 31 - 1)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("ring_candidates: device must be a GPU (got %s); the HIP path has no CPU fallback" % device)
@@ -263,7 +202,7 @@ def locate_on_ring(spec, mics, receiver, room, R, z, n_angles=360, method="srp",
         raise ValueError("locate_on_ring: method must be 'srp' or 'music', got %r" % (method,))
     if method == "srp" and n_sources != 1:
         raise ValueError("locate_on_ring: n_sources goes with method 'music', got %r" % (n_sources,))
-    _on_gpu("locate_on_ring", spec)
+    rules.on_gpu("locate_on_ring", spec, "spec")
     theta, points = ring_candidates(n_angles, receiver, room, R, z, spec.device)
     if method == "music":
         found = music(spec, mics, points, n_sources, **srp_kwargs)

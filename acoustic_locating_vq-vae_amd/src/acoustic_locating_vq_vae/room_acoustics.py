@@ -18,9 +18,8 @@ when it can sync.
 import collections
 import math
 
-import torch
-
 from . import _native as N
+from . import _rules as rules
 
 RoomAcoustics = collections.namedtuple("RoomAcoustics", "t30 t20 edt c50 c80 d50 drr onset status")
 
@@ -31,18 +30,10 @@ def sample_counts(fs):
 
 
 def _rows(h, who):
-    """h as a contiguous (B, n) tensor, and whether it came as (n,)."""
-    if not isinstance(h, torch.Tensor) or h.dim() not in (1, 2):
-        raise ValueError("%s: h must be an (n,) or (B, n) tensor" % who)
-    if h.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s: h must be float32 or float64, got %s" % (who, h.dtype))
-    single = h.dim() == 1
-    rows = h.unsqueeze(0) if single else h
-    if rows.shape[0] < 1 or rows.shape[1] < 2 or rows.shape[1] > 1 << 24:
-        raise ValueError("%s: need B >= 1 and 2 <= n <= 2^24, got shape %s" % (who, tuple(h.shape)))
-    if not h.is_cuda:
-        raise RuntimeError("%s: h must live on the GPU (got %s); the HIP path has no CPU fallback" % (who, h.device))
-    return rows.contiguous(), single
+    """h as a contiguous (B, n) tensor on the GPU, and whether it came with a batch dimension."""
+    rows, single = rules.rows(who, "h", h)
+    rules.on_gpu(who, h, "h")
+    return rows, not single
 
 
 def _rate(fs, who):
@@ -54,9 +45,8 @@ def _rate(fs, who):
 def energy_decay_curve(h):
     """Schroeder's energy decay curve 10 log10(sum_{s >= t} h[s]^2 / sum_s h[s]^2) in dB: h (B, n) or (n,), float32 or
     float64 on the GPU -> float64 of the same shape.  -inf where nothing follows; a row of zero or non-finite energy is NaN."""
-    rows, single = _rows(h, "energy_decay_curve")
-    out = N.edc(rows)
-    return out[0] if single else out
+    rows, batched = _rows(h, "energy_decay_curve")
+    return rules.unbatch(N.edc(rows), batched)
 
 
 def room_acoustic_parameters(h, fs=16000):
@@ -64,10 +54,9 @@ def room_acoustic_parameters(h, fs=16000):
     ``RoomAcoustics(t30, t20, edt, c50, c80, d50, drr, onset, status)`` of (B,) device tensors (0-d for an (n,) input): float64
     but onset and status, int32.  Times in s, ratios in dB.  The arithmetic is float64 for either input type."""
     fs = _rate(fs, "room_acoustic_parameters")
-    rows, single = _rows(h, "room_acoustic_parameters")
+    rows, batched = _rows(h, "room_acoustic_parameters")
     out, onset, status = N.room_acoustics(rows, fs, *sample_counts(fs))
-    cols = tuple(out[:, i] for i in range(7)) + (onset, status)
-    return RoomAcoustics(*(c[0] for c in cols)) if single else RoomAcoustics(*cols)
+    return rules.unbatch(RoomAcoustics(*out.unbind(1), onset, status), batched)
 
 
 def reverberation_time(h, fs=16000, method="t30"):

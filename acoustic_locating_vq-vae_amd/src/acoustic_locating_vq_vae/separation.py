@@ -83,10 +83,9 @@ import collections
 import torch
 
 from . import _native as N
-from .beamforming import MAX_FRAMES, MAX_MICROPHONES, _spec4
-from .dereverberation import _nonneg
+from . import _rules as rules
+from ._rules import MAX_FRAMES, MAX_MICROPHONES
 from .front_end import HOP, N_FFT
-from .localization import _int_in, _on_gpu, _positive
 
 IVA = collections.namedtuple("IVA", "spec w status")
 ILRMA = collections.namedtuple("ILRMA", "spec w basis activations status")
@@ -102,11 +101,11 @@ MAX_BASES = 16
 
 def _iva_rules(who, D, iterations, model, ref, eps):
     """The rules of the keywords for D microphones; ValueErrors only."""
-    _int_in(who, "iterations", iterations, 0, MAX_ITERATIONS)
+    rules.int_in(who, "iterations", iterations, 0, MAX_ITERATIONS)
     if not isinstance(model, str) or model not in MODELS:
         raise ValueError("%s: model must be one of 'laplace', 'gauss', got %r" % (who, model))
-    _int_in(who, "ref", ref, 0, D - 1)
-    _nonneg(who, "eps", eps)
+    rules.int_in(who, "ref", ref, 0, D - 1)
+    rules.nonneg(who, "eps", eps)
 
 
 def _start_w(who, w0, spec, dims, batched):
@@ -126,22 +125,19 @@ def auxiva(spec, iterations=20, model="laplace", ref=0, eps=1e-10, w0=None):
     heard them, of spec's shape and dtype, the demixing matrices w (B, F, D, D) complex128 and status (B, F) int32 (no B for a
     (D, F, T) spec).  ``auxiva(X, a + b).w`` equals ``auxiva(X, b, w0=auxiva(X, a).w).w`` bit for bit."""
     who = "auxiva"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     B, D, F, T = x.shape
     _iva_rules(who, D, iterations, model, ref, eps)
     w0 = _start_w(who, w0, spec, x.shape, batched)
-    _on_gpu(who, x, "spec")
-    if w0 is not None:
-        _on_gpu(who, w0, "w0")
-    out = IVA(*N.auxiva(x, int(iterations), MODELS[model], int(ref), float(eps), w0))
-    return out if batched else IVA(*(t[0] for t in out))
+    rules.all_on_gpu(who, spec=x, w0=w0)
+    return rules.unbatch(IVA(*N.auxiva(x, int(iterations), MODELS[model], int(ref), float(eps), w0)), batched)
 
 
 def _ilrma_rules(who, D, iterations, ref, floor):
     """The rules of ILRMA's keywords for D microphones; ValueErrors only."""
-    _int_in(who, "iterations", iterations, 0, MAX_ITERATIONS)
-    _int_in(who, "ref", ref, 0, D - 1)
-    _positive(who, "floor", floor)
+    rules.int_in(who, "iterations", iterations, 0, MAX_ITERATIONS)
+    rules.int_in(who, "ref", ref, 0, D - 1)
+    rules.positive(who, "floor", floor)
 
 
 def ilrma(spec, basis0, activations0, iterations=20, ref=0, floor=1e-10, w0=None):
@@ -164,7 +160,7 @@ def ilrma(spec, basis0, activations0, iterations=20, ref=0, floor=1e-10, w0=None
     of ``auxiva`` in every bin of status 0 with phi[k, t] replaced by 1 / R[k, f, t].  Then ``auxiva``'s projection onto
     microphone ``ref``.  Nothing here reads a status: the caller does, when it can sync."""
     who = "ilrma"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     B, D, F, T = x.shape
     lead = (B,) if batched else ()
     if not isinstance(basis0, torch.Tensor) or basis0.dtype != torch.float64 or basis0.dim() != len(lead) + 3 \
@@ -178,22 +174,17 @@ def ilrma(spec, basis0, activations0, iterations=20, ref=0, floor=1e-10, w0=None
     _ilrma_rules(who, D, iterations, ref, floor)
     w0 = _start_w(who, w0, spec, x.shape, batched)
     b0, a0 = (basis0, activations0) if batched else (basis0[None], activations0[None])
-    _on_gpu(who, x, "spec")
-    _on_gpu(who, b0, "basis0")
-    _on_gpu(who, a0, "activations0")
-    if w0 is not None:
-        _on_gpu(who, w0, "w0")
-    out = ILRMA(*N.ilrma(x, b0, a0, int(iterations), int(ref), float(floor), w0))
-    return out if batched else ILRMA(*(t[0] for t in out))
+    rules.all_on_gpu(who, spec=x, basis0=b0, activations0=a0, w0=w0)
+    return rules.unbatch(ILRMA(*N.ilrma(x, b0, a0, int(iterations), int(ref), float(floor), w0)), batched)
 
 
 def nmf_init(B, D, F, T, bases=2, generator=None, device="cuda"):
     """A start for ``ilrma``, the companion of ``time_masks``: (basis0 (B, D, F, bases), activations0 (B, D, bases, T)) float64
     on ``device``, uniform(0, 1) + 1e-3 from ``generator``, the basis drawn first."""
     who = "nmf_init"
-    for name, v, hi in (("B", B, 65535), ("D", D, MAX_MICROPHONES), ("F", F, 2 ** 31 - 1), ("T", T, MAX_FRAMES),
+    for name, v, hi in (("B", B, rules.MAX_BATCH), ("D", D, MAX_MICROPHONES), ("F", F, rules.MAX_BINS), ("T", T, MAX_FRAMES),
                         ("bases", bases, MAX_BASES)):
-        _int_in(who, name, v, 1, hi)
+        rules.int_in(who, name, v, 1, hi)
     basis0 = torch.rand((B, D, F, bases), dtype=torch.float64, generator=generator, device=device) + 1e-3
     activations0 = torch.rand((B, D, bases, T), dtype=torch.float64, generator=generator, device=device) + 1e-3
     return basis0, activations0
@@ -204,10 +195,9 @@ def masks(sep_spec):
     float64 of the same shape, M[:, k] = |Y_k|^2 / sum_j |Y_j|^2.  ``M[:, k]`` and ``1 - M[:, k]`` are the speech and noise
     masks of ``beamforming.mvdr`` and ``gev`` for source k."""
     who = "masks"
-    y, batched = _spec4(who, sep_spec)
-    _on_gpu(who, y, "sep_spec")
-    m = N.separation_masks(y)
-    return m if batched else m[0]
+    y, batched = rules.spec4(who, sep_spec)
+    rules.on_gpu(who, y, "sep_spec")
+    return rules.unbatch(N.separation_masks(y), batched)
 
 
 def reorder(x, perm):
@@ -223,8 +213,7 @@ def reorder(x, perm):
         raise ValueError("%s: x must be a tensor of at least %d dimensions for a perm of %d" % (who, perm.dim(), perm.dim()))
     if perm.shape[-1] < 1 or x.shape[perm.dim() - 1] < 1 or (batched and (x.shape[0] != perm.shape[0] or x.shape[0] < 1)):
         raise ValueError("%s: x %s and perm %s do not go together" % (who, tuple(x.shape), tuple(perm.shape)))
-    _on_gpu(who, x, "x")
-    _on_gpu(who, perm, "perm")
+    rules.all_on_gpu(who, x=x, perm=perm)
     index = perm.long()
     if not batched:
         return x[index]
@@ -241,23 +230,14 @@ def separate_waves(waves, iterations=20, model="laplace", ref=0, n_fft=N_FFT, ho
         raise ValueError("%s: method must be one of 'auxiva', 'ilrma', got %r" % (who, method))
     if method == "ilrma" and model != "laplace":
         raise ValueError("%s: model belongs to method 'auxiva'; with method 'ilrma' leave it at its default, got %r" % (who, model))
-    if not isinstance(waves, torch.Tensor) or waves.dim() != 3:
-        raise ValueError("%s: waves must be a (B, D, S) tensor" % who)
-    if waves.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s: waves must be float32 or float64, got %s" % (who, waves.dtype))
-    B, D, S = waves.shape
-    if B < 1 or B > 65535 or D < 1 or D > MAX_MICROPHONES or S < 1:
-        raise ValueError("%s: need 1 <= B <= 65535, 1 <= D <= 8 and S >= 1, got shape %s" % (who, tuple(waves.shape)))
-    _int_in(who, "n_fft", n_fft, 2, 2 ** 24)
-    _int_in(who, "hop", hop, 1, n_fft)
-    F, T = n_fft // 2 + 1, 1 + S // hop
-    if T > MAX_FRAMES or B * F > 2 ** 31 - 1:
-        raise ValueError("%s: need B F <= 2^31 - 1 and T = 1 + S / hop <= 65535, got F = %d, T = %d" % (who, F, T))
+    rules.waves3(who, waves)
+    B, D, F, T = rules.stft_dims(who, waves, n_fft, hop)
+    S = waves.shape[2]
     _iva_rules(who, D, iterations, model, ref, 0.0)
-    _int_in(who, "bases", bases, 1, MAX_BASES)
+    rules.int_in(who, "bases", bases, 1, MAX_BASES)
     if generator is not None and not isinstance(generator, torch.Generator):
         raise ValueError("%s: generator must be a torch.Generator or None, got %r" % (who, generator))
-    _on_gpu(who, waves, "waves")
+    rules.on_gpu(who, waves, "waves")
     spec = N.stft_complex(waves.reshape(B * D, S).contiguous(), n_fft, hop).view(B, D, F, T)
     if method == "ilrma":
         sep = ilrma(spec, *nmf_init(B, D, F, T, bases, generator, waves.device), iterations=iterations, ref=ref)
@@ -302,22 +282,17 @@ def cacgmm(spec, init, iterations=20, quadratic0=None, floor=1e-10):
     over frequency; masks whose classes have come out in a different order in every bin are repaired by
     ``align_permutations``.  Nothing here reads a status: the caller does, when it can sync."""
     who = "cacgmm"
-    x, batched = _spec4(who, spec)
+    x, batched = rules.spec4(who, spec)
     B, D, F, T = x.shape
-    if D < 2:
-        raise ValueError("%s: need 2 <= D <= 8 microphones, got D = %d" % (who, D))
+    rules.microphones(who, D, 2)
     g0 = _class_array(who, "init", init, B, F, T, batched)
     q0 = None if quadratic0 is None else _class_array(who, "quadratic0", quadratic0, B, F, T, batched, g0.shape[1])
-    _int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
-    _nonneg(who, "floor", floor)
+    rules.int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
+    rules.nonneg(who, "floor", floor)
     if floor > 1:
         raise ValueError("%s: floor must be in [0, 1], got %r" % (who, floor))
-    _on_gpu(who, x, "spec")
-    _on_gpu(who, g0, "init")
-    if q0 is not None:
-        _on_gpu(who, q0, "quadratic0")
-    out = CACGMM(*N.cacgmm(x, g0, int(iterations), float(floor), q0))
-    return out if batched else CACGMM(*(t[0] for t in out))
+    rules.all_on_gpu(who, spec=x, init=g0, quadratic0=q0)
+    return rules.unbatch(CACGMM(*N.cacgmm(x, g0, int(iterations), float(floor), q0)), batched)
 
 
 def time_masks(B, K, F, T, generator=None, device="cuda"):
@@ -325,8 +300,8 @@ def time_masks(B, K, F, T, generator=None, device="cuda"):
     over k and repeated over f -> (B, K, F, T) float64 on ``device``.  With an independent init per bin the classes of different
     bins come out in different orders, and the masks near chance across bins."""
     who = "time_masks"
-    for name, v, hi in (("B", B, 65535), ("K", K, MAX_CLASSES), ("F", F, 2 ** 31 - 1), ("T", T, MAX_FRAMES)):
-        _int_in(who, name, v, 1, hi)
+    for name, v, hi in (("B", B, rules.MAX_BATCH), ("K", K, MAX_CLASSES), ("F", F, rules.MAX_BINS), ("T", T, MAX_FRAMES)):
+        rules.int_in(who, name, v, 1, hi)
     m = torch.rand((B, K, 1, T), dtype=torch.float64, generator=generator, device=device) + 1e-3
     return (m / m.sum(dim=1, keepdim=True)).expand(B, K, F, T).contiguous()
 
@@ -345,7 +320,7 @@ def _class_rows(who, x, dtypes, what):
         raise ValueError("%s: %s must be a (K, F, T) or (B, K, F, T) tensor of %s" % (who, what, " or ".join(str(d) for d in dtypes)))
     y = x if x.dim() == 4 else x[None]
     B, K, F, T = y.shape
-    if B < 1 or B > 65535 or K < 1 or K > MAX_CLASSES or F < 1 or B * F > 2 ** 31 - 1 or T < 1 or T > MAX_FRAMES:
+    if B < 1 or B > rules.MAX_BATCH or K < 1 or K > MAX_CLASSES or F < 1 or B * F > rules.MAX_BINS or T < 1 or T > MAX_FRAMES:
         raise ValueError("%s: need 1 <= B <= 65535, 1 <= K <= 8, F >= 1, B F <= 2^31 - 1 and 1 <= T <= 65535, got shape %s"
                          % (who, tuple(x.shape)))
     return y, x.dim() == 4
@@ -373,13 +348,10 @@ def align_permutations(profile, iterations=10, perm0=None):
     B, K, F, T = p.shape
     if T < 2:
         raise ValueError("%s: need T >= 2 frames, got T = %d" % (who, T))
-    _int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
+    rules.int_in(who, "iterations", iterations, 1, MAX_ITERATIONS)
     p0 = None if perm0 is None else _bin_perm(who, "perm0", perm0, B, K, F, batched)
-    _on_gpu(who, p, "profile")
-    if p0 is not None:
-        _on_gpu(who, p0, "perm0")
-    out = ALIGN(*N.align_permutations(p, int(iterations), p0))
-    return out if batched else ALIGN(*(t[0] for t in out))
+    rules.all_on_gpu(who, profile=p, perm0=p0)
+    return rules.unbatch(ALIGN(*N.align_permutations(p, int(iterations), p0)), batched)
 
 
 def permute_bins(x, perm):
@@ -391,10 +363,8 @@ def permute_bins(x, perm):
     y, batched = _class_rows(who, x, (torch.float32, torch.float64, torch.complex64, torch.complex128), "x")
     B, K, F, _ = y.shape
     p = _bin_perm(who, "perm", perm, B, K, F, batched)
-    _on_gpu(who, y, "x")
-    _on_gpu(who, p, "perm")
-    out = N.permute_bins(y, p)
-    return out if batched else out[0]
+    rules.all_on_gpu(who, x=y, perm=p)
+    return rules.unbatch(N.permute_bins(y, p), batched)
 
 
 def permute_rows(a, perm):
@@ -409,7 +379,6 @@ def permute_rows(a, perm):
         raise ValueError("%s: perm must be an int32 (F, K) or (B, F, K) tensor" % who)
     if not isinstance(a, torch.Tensor) or a.dim() < perm.dim() or tuple(a.shape[:perm.dim()]) != tuple(perm.shape) or perm.numel() < 1:
         raise ValueError("%s: a must be a tensor of shape %s + (...) for this perm" % (who, tuple(perm.shape)))
-    _on_gpu(who, a, "a")
-    _on_gpu(who, perm, "perm")
+    rules.all_on_gpu(who, a=a, perm=perm)
     index = perm.long().reshape(tuple(perm.shape) + (1,) * (a.dim() - perm.dim())).expand(a.shape)
     return torch.gather(a, perm.dim() - 1, index)

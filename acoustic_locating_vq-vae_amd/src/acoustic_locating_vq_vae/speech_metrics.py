@@ -59,6 +59,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import _rules as rules
 
 STOI = collections.namedtuple("STOI", "value kept_frames status")
 
@@ -101,19 +102,6 @@ def _device_filter(up, down, device):
     return torch.from_numpy(resample_filter(up, down)[0]).to(device)
 
 
-def _rows(x, who, name, min_n=2):
-    """x as a contiguous (B, n) tensor, and whether it came as (n,).  The device is checked by the caller, last."""
-    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
-        raise ValueError("%s: %s must be an (n,) or (B, n) tensor" % (who, name))
-    if x.dtype not in (torch.float32, torch.float64):
-        raise ValueError("%s: %s must be float32 or float64, got %s" % (who, name, x.dtype))
-    single = x.dim() == 1
-    rows = x.unsqueeze(0) if single else x
-    if rows.shape[0] < 1 or rows.shape[0] > 65535 or rows.shape[1] < min_n or rows.shape[1] > 1 << 24:
-        raise ValueError("%s: need 1 <= B <= 65535 and %d <= n <= 2^24, got shape %s" % (who, min_n, tuple(x.shape)))
-    return rows.contiguous(), single
-
-
 def _pair(a, b, who, names, dims=(1, 2)):
     """Two tensors of one shape and dtype."""
     for t, name in zip((a, b), names):
@@ -135,10 +123,9 @@ def resample_poly(x, up, down):
     """``scipy.signal.resample_poly(x, up, down)`` with its defaults along the last axis: x (B, n) or (n,), float32 or float64
     on the GPU -> float64 with ceil(n up / down) samples a row.  max(up, down) <= 512 after reduction by their gcd."""
     _, up, down = resample_filter(up, down)
-    rows, single = _rows(x, "resample_poly", "x", min_n=1)
+    rows, single = rules.rows("resample_poly", "x", x, 1, rules.MAX_BATCH)
     _on_gpu("resample_poly", rows)
-    y = N.resample_poly(rows, _device_filter(up, down, rows.device), up, down)
-    return y[0] if single else y
+    return rules.unbatch(N.resample_poly(rows, _device_filter(up, down, rows.device), up, down), not single)
 
 
 def stoi(clean, degraded, fs=16000):
@@ -150,13 +137,12 @@ def stoi(clean, degraded, fs=16000):
     _pair(clean, degraded, "stoi", ("clean", "degraded"))
     if fs != STOI_FS:
         resample_filter(STOI_FS, fs)
-    x, single = _rows(clean, "stoi", "clean")
-    y, _ = _rows(degraded, "stoi", "degraded")
+    x, single = rules.rows("stoi", "clean", clean, max_b=rules.MAX_BATCH)
+    y, _ = rules.rows("stoi", "degraded", degraded, max_b=rules.MAX_BATCH)
     _on_gpu("stoi", x, y)
     if fs != STOI_FS:
         x, y = resample_poly(x, STOI_FS, int(fs)), resample_poly(y, STOI_FS, int(fs))
-    out = N.stoi(x.double(), y.double(), *stoi_band_edges())
-    return STOI(*(t[0] for t in out)) if single else STOI(*out)
+    return rules.unbatch(STOI(*N.stoi(x.double(), y.double(), *stoi_band_edges())), not single)
 
 
 def si_sdr(reference, estimate):
@@ -164,19 +150,17 @@ def si_sdr(reference, estimate):
     -> (B,) float64 dB (0-d for (n,) input).  +inf for an exact multiple of the reference, NaN for a reference of zero or
     non-finite energy."""
     _pair(reference, estimate, "si_sdr", ("reference", "estimate"))
-    s, single = _rows(reference, "si_sdr", "reference")
-    e, _ = _rows(estimate, "si_sdr", "estimate")
+    s, single = rules.rows("si_sdr", "reference", reference, max_b=rules.MAX_BATCH)
+    e, _ = rules.rows("si_sdr", "estimate", estimate, max_b=rules.MAX_BATCH)
     _on_gpu("si_sdr", s, e)
-    out = N.si_sdr(s, e)
-    return out[0] if single else out
+    return rules.unbatch(N.si_sdr(s, e), not single)
 
 
 def log_spectral_distance(p, q, eps=1e-10):
     """Log-spectral distance of power spectrograms p, q: (B, F, T) or (F, T), float32 or float64 on the GPU -> (B,) float64 dB
     (0-d for (F, T) input), the mean over the frames of sqrt(mean_f (10 log10((p + eps) / (q + eps)))^2).  A spectrogram pair
     with a negative or non-finite entry gives NaN."""
-    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps >= 0):
-        raise ValueError("log_spectral_distance: eps must be a finite number >= 0, got %r" % (eps,))
+    rules.nonneg("log_spectral_distance", "eps", eps)
     _pair(p, q, "log_spectral_distance", ("p", "q"), dims=(2, 3))
     if p.dtype not in (torch.float32, torch.float64):
         raise ValueError("log_spectral_distance: p and q must be float32 or float64, got %s" % p.dtype)
@@ -186,8 +170,7 @@ def log_spectral_distance(p, q, eps=1e-10):
     if B < 1 or B > 65535 or F < 1 or T < 1 or F * T > 1 << 30:
         raise ValueError("log_spectral_distance: need 1 <= B <= 65535, F, T >= 1 and F T <= 2^30, got shape %s" % (tuple(p.shape),))
     _on_gpu("log_spectral_distance", ps, qs)
-    out = N.lsd(ps.contiguous(), qs.contiguous(), float(eps))
-    return out[0] if single else out
+    return rules.unbatch(N.lsd(ps.contiguous(), qs.contiguous(), float(eps)), not single)
 
 
 # ------------------------------------------------------------------------------------------------------ separation scores
@@ -228,8 +211,7 @@ def pairwise_si_sdr(references, estimates):
     ``si_sdr(references[b, i], estimates[b, j])``; the reference row is streamed once per pass for all J estimates."""
     s, e, single = _sources(references, estimates, "pairwise_si_sdr")
     _on_gpu("pairwise_si_sdr", s, e)
-    table = N.pairwise_si_sdr(s, e)
-    return table[0] if single else table
+    return rules.unbatch(N.pairwise_si_sdr(s, e), not single)
 
 
 def assign(table, maximize=True):
@@ -249,8 +231,7 @@ def assign(table, maximize=True):
     if B < 1 or B > 65535 or K < 1 or K > J or J > MAX_SOURCES:
         raise ValueError("%s: need 1 <= B <= 65535 and 1 <= K <= J <= 8, got shape %s" % (who, tuple(table.shape)))
     _on_gpu(who, t)
-    out = ASSIGN(*N.assign(t.contiguous(), maximize))
-    return ASSIGN(*(v[0] for v in out)) if single else out
+    return rules.unbatch(ASSIGN(*N.assign(t.contiguous(), maximize)), not single)
 
 
 def _pit(s, e):
@@ -265,8 +246,7 @@ def pit_si_sdr(references, estimates):
     can be scored against, say, ``cacgmm``'s K + 1 classes.  Without B for (K, n) input."""
     s, e, single = _sources(references, estimates, "pit_si_sdr", square=True)
     _on_gpu("pit_si_sdr", s, e)
-    out = _pit(s, e)[1]
-    return PIT(*(v[0] for v in out)) if single else out
+    return rules.unbatch(_pit(s, e)[1], not single)
 
 
 def si_bss_eval(references, estimates, perm=None):
@@ -288,8 +268,7 @@ def si_bss_eval(references, estimates, perm=None):
         _on_gpu(who, perm)
         p = (perm[None] if single else perm).contiguous()
     sdr, sir, sar, status = N.si_bss_eval(s, e, p)
-    out = SIBSS(sdr, sir, sar, p, status)
-    return SIBSS(*(v[0] for v in out)) if single else out
+    return rules.unbatch(SIBSS(sdr, sir, sar, p, status), not single)
 
 
 def si_sdr_improvement(references, estimates, mixture):
@@ -304,5 +283,4 @@ def si_sdr_improvement(references, estimates, mixture):
                          % (who, s.dtype, (s.shape[2],) if single else (s.shape[0], s.shape[2]), tuple(references.shape)))
     _on_gpu(who, s, e, mixture)
     m = (mixture[None] if single else mixture)[:, None].contiguous()
-    gain = _pit(s, e)[1].value - N.pairwise_si_sdr(s, m)[:, :, 0]
-    return gain[0] if single else gain
+    return rules.unbatch(_pit(s, e)[1].value - N.pairwise_si_sdr(s, m)[:, :, 0], not single)

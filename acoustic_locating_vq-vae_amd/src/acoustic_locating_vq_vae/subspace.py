@@ -20,15 +20,11 @@ import collections
 import torch
 
 from . import _native as N
+from . import _rules as rules
 
 Eigh = collections.namedtuple("Eigh", "values vectors status")
 
 MAX_ORDER = 8
-
-
-def _on_gpu(who, t, name):
-    if not t.is_cuda:
-        raise RuntimeError("%s: %s must live on the GPU (got %s); the HIP path has no CPU fallback" % (who, name, t.device))
 
 
 def eigh(cov):
@@ -46,6 +42,6 @@ def eigh(cov):
         n *= s
     if n < 1 or n > 2 ** 31 - 1:
         raise ValueError("%s: need 1 <= the number of matrices <= 2^31 - 1, got shape %s" % (who, tuple(cov.shape)))
-    _on_gpu(who, cov, "cov")
+    rules.on_gpu(who, cov, "cov")
     values, vectors, status = N.eigh(cov.reshape(n, D, D))
     return Eigh(values.view(lead + (D,)), vectors.view(lead + (D, D)), status.view(lead))
