@@ -11,39 +11,17 @@ and nothing more is started on the device.  For the kernels' own times run `pyth
 rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-F, T = 201, 500
+from family_bench import COPY_BYTES_PER_S, F, T  # noqa: E402
+
 SHAPES = ((64, 2), (8, 8))
-ITER_LO, ITER_HI, ITER_CALL = 4, 12, 10
-COPY_BYTES_PER_S = 6.3e12
-STEP_SECONDS = 300
+ITER_CALL = 10                           # align_permutations' default, not the separators' 20 of family_bench
 STEPS = tuple("%d-%d" % s for s in SHAPES)
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    import torch
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
 
 
 def profile(B, K):
@@ -68,11 +46,9 @@ def step(name):
     from acoustic_locating_vq_vae import separation as SEP
     B, K = (int(v) for v in name.split("-"))
     P = profile(B, K)
-    lo = best_seconds(lambda: SEP.align_permutations(P, ITER_LO), 3)
-    hi = best_seconds(lambda: SEP.align_permutations(P, ITER_HI), 3)
-    call = best_seconds(lambda: SEP.align_permutations(P, ITER_CALL), 3)
+    iteration, call, outside = FB.iteration_ms(lambda n: SEP.align_permutations(P, n), iter_call=ITER_CALL)
     out = SEP.align_permutations(P, ITER_CALL)
-    copy = best_seconds(lambda: SEP.permute_bins(P, out.perm), 3)
+    copy = FB.best_seconds(lambda: SEP.permute_bins(P, out.perm), 3)
     nbytes = P.numel() * 8
     p1 = P[:1].cpu().numpy()
     t0 = time.perf_counter()
@@ -80,9 +56,9 @@ def step(name):
     cpu = (time.perf_counter() - t0) / 2
     two = SEP.align_permutations(P[:1].contiguous(), 2)
     print(json.dumps({"step": name, "B": B, "K": K, "F": F, "T": T, "profile_MB": nbytes / 1e6,
-                      "iteration_ms": (hi - lo) / (ITER_HI - ITER_LO) * 1e3,
-                      "byte_floor_ms": 2 * nbytes / COPY_BYTES_PER_S * 1e3, "call_ms_10_iterations": call * 1e3,
-                      "outside_the_iterations_ms": (lo - ITER_LO * (hi - lo) / (ITER_HI - ITER_LO)) * 1e3,
+                      "iteration_ms": iteration,
+                      "byte_floor_ms": 2 * nbytes / COPY_BYTES_PER_S * 1e3, "call_ms_10_iterations": call,
+                      "outside_the_iterations_ms": outside,
                       "permute_bins_ms": copy * 1e3, "permute_bins_byte_floor_ms": 2 * nbytes / COPY_BYTES_PER_S * 1e3,
                       "bins_with_status": int((out.status != 0).sum()), "bins_changed_by_the_last_iteration": int(out.changed.sum()),
                       "restatement_cpu_ms_per_iteration_at_B_1": cpu * 1e3,
@@ -92,17 +68,7 @@ def step(name):
 
 
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_align: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_align: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        print(done.stdout.strip().splitlines()[-1], flush=True)
+    FB.main(__file__, STEPS, step)
 
 
 if __name__ == "__main__":

@@ -10,37 +10,16 @@ and nothing more is started on the device.  For a kernel's own time run `python 
 (or fused_weights, fused_apply) once under rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-B, D, F, T = 64, 8, 201, 500
+from family_bench import COPY_BYTES_PER_S, F, T  # noqa: E402
+
+B, D = 64, 8
 LOADING = 1e-6
-COPY_BYTES_PER_S = 6.3e12
-STEP_SECONDS = 300
 STEPS = ("fused_cov", "torch_cov", "fused_weights", "torch_weights", "fused_apply", "torch_apply")
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    import torch
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
 
 
 def scene():
@@ -49,17 +28,12 @@ def scene():
     import torch
     from acoustic_locating_vq_vae import beamforming as BF
     g = torch.Generator(device="cuda").manual_seed(0)
-
-    def gauss(*shape):
-        return torch.complex(torch.randn(shape, dtype=torch.float64, device="cuda", generator=g),
-                             torch.randn(shape, dtype=torch.float64, device="cuda", generator=g))
-    centre = torch.tensor([2.5, 1.5, 1.5], dtype=torch.float64, device="cuda")
-    mics = centre + 0.05 * (2 * torch.rand((D, 3), dtype=torch.float64, device="cuda", generator=g) - 1)
+    centre, mics = FB.array_centre(), FB.array_microphones(g, D)
     angle = 6.283185307179586 * torch.rand((2, B), dtype=torch.float64, device="cuda", generator=g)
     points = centre + torch.stack((torch.cos(angle), torch.sin(angle), torch.ones_like(angle)), dim=-1)       # (2, B, 3)
     A, _ = BF.steering_vectors(mics, points[0], F)
     Bv, _ = BF.steering_vectors(mics, points[1], F)
-    X = A[..., None] * gauss(B, 1, F, T) + Bv[..., None] * gauss(B, 1, F, T) + 0.03 * gauss(B, D, F, T)
+    X = A[..., None] * FB.gauss(g, B, 1, F, T) + Bv[..., None] * FB.gauss(g, B, 1, F, T) + 0.03 * FB.gauss(g, B, D, F, T)
     mask = torch.rand((B, F, T), dtype=torch.float64, device="cuda", generator=g)
     return X, mask, A
 
@@ -102,7 +76,7 @@ def step(name):
         ours = {"cov": cov.cov, "weights": w.w, "apply": y}[what]
         out["max_abs_diff_to_fused"] = float((fn() - ours).abs().max())
         out["max_abs_fused"] = float(ours.abs().max())
-    out["seconds"] = best_seconds(fn, 10)
+    out["seconds"] = FB.best_seconds(fn, 10)
     # the bytes the launch has to move: the spectrogram once, plus the mask (covariance) or the output (application)
     moved = {"cov": X.numel() * 16 + mask.numel() * 8 + cov.cov.numel() * 16, "apply": X.numel() * 16 + w.w.numel() * 16 + y.numel() * 16,
              "weights": cov.cov.numel() * 16 + A.numel() * 16 + w.w.numel() * 16}[what]
@@ -112,26 +86,17 @@ def step(name):
     print(json.dumps(out), flush=True)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    results = {}
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_beamform: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_beamform: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        results[name] = json.loads(done.stdout.strip().splitlines()[-1])
-        print(json.dumps(results[name]), flush=True)
+def summarise(results):
     for what in ("cov", "weights", "apply"):
         fused, composed = results["fused_" + what], results["torch_" + what]
         print(json.dumps({"launch": what, "fused_ms": fused["seconds"] * 1e3, "torch_ms": composed["seconds"] * 1e3,
                           "torch_over_fused": composed["seconds"] / fused["seconds"],
                           "fused_TB_per_s": fused["bytes_per_s"] * 1e-12, "copy_TB_per_s": COPY_BYTES_PER_S * 1e-12,
                           "max_abs_diff": composed["max_abs_diff_to_fused"]}), flush=True)
+
+
+def main():
+    FB.main(__file__, STEPS, step, summarise)
 
 
 if __name__ == "__main__":

@@ -14,10 +14,8 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench  # noqa: E402,F401  (it puts the repository, the package and tests/helpers on the path)
 os.environ.setdefault("OMP_NUM_THREADS", "16")
 import numpy as np
 import torch
@@ -32,7 +30,7 @@ SPEECH_FLOATS = 16836937 + 64 * 18            # the speech model's parameters pl
 LOCATION_FLOATS = 212_500_000                 # the location head's flat buffer: 850 MB
 
 
-def timed_us(fn, calls, inner=10):
+def graph_replay_us(fn, calls, inner=10):
     """us per call of ``fn(i)`` on the device: ``inner`` calls captured into one graph (no host launch cost between them),
     replayed until ``calls`` have run."""
     for i in range(inner):
@@ -62,8 +60,8 @@ def launch_cost(n, calls, copies):
     sc = torch.zeros(N.ADAM_SCALARS, device="cuda")
     N.adam_advance(sc, 1e-3, 0.9, 0.999, 1.0)
     ws = N.grad_clip_workspace("cuda")
-    both = timed_us(lambda i: N.grad_clip(gs[i % copies], sc, float("inf"), workspace=ws), calls)
-    tiny = timed_us(lambda i: N.grad_clip(gs[0][:64], sc, float("inf"), workspace=ws), calls)   # the launches with nothing to read
+    both = graph_replay_us(lambda i: N.grad_clip(gs[i % copies], sc, float("inf"), workspace=ws), calls)
+    tiny = graph_replay_us(lambda i: N.grad_clip(gs[0][:64], sc, float("inf"), workspace=ws), calls)   # the launches with nothing to read
     return {"floats": n, "MB": round(n * 4e-6, 1), "buffers_in_turn": copies, "two_launches_us": round(both, 2),
             "empty_span_us": round(tiny, 2), "GBps": round(n * 4e-3 / both, 1), "norm": float(sc[5])}
 

@@ -11,14 +11,16 @@ and nothing more is started on the device.  For the kernels' own times run `pyth
 rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import bench_iva as BI  # noqa: E402  (it puts the package and tests/helpers on the path)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
+from family_bench import COPY_BYTES_PER_S, FP64_FLOP_PER_S, ITER_CALL, F, T  # noqa: E402
+
+SHAPES = ((64, 2), (8, 8))               # tests/bench_iva.py's, so that the two iterations stand side by side
 BASES = (2, 10)
-STEPS = tuple("%d-%d-%d" % (B, D, L) for B, D in BI.SHAPES for L in BASES)
+STEPS = tuple("%d-%d-%d" % (B, D, L) for B, D in SHAPES for L in BASES)
 
 
 def floors(B, D, L, itemsize):
@@ -26,44 +28,30 @@ def floors(B, D, L, itemsize):
     written once and read twice.  Arithmetic a frame and bin: the power pass is D^2 complex multiply-adds (8 flop each) and 3 D
     for |y|^2; the basis and the activation update are each 2 L for R, 4 for 1 / R, P / lam and g, and 4 L for the two sums, a
     source; the weights 2 L + 1 a source; the D covariances 5 D^3."""
-    frames = B * BI.F * BI.T
+    frames = B * F * T
     flop = 8 * D * D + 3 * D + D * (2 * (6 * L + 4) + 2 * L + 1) + 5 * D ** 3
-    return (2 * itemsize + 3 * 8) * D * frames / BI.COPY_BYTES_PER_S, frames * flop / BI.FP64_FLOP_PER_S
+    return (2 * itemsize + 3 * 8) * D * frames / COPY_BYTES_PER_S, frames * flop / FP64_FLOP_PER_S
 
 
 def step(name):
     import torch
     from acoustic_locating_vq_vae import separation as SEP
     B, D, L = (int(v) for v in name.split("-"))
-    X = BI.mixture(B, D, torch.complex128)
-    b0, a0 = SEP.nmf_init(B, D, BI.F, BI.T, L, generator=torch.Generator(device="cuda").manual_seed(0))
-    lo = BI.best_seconds(lambda: SEP.ilrma(X, b0, a0, BI.ITER_LO), 3)
-    hi = BI.best_seconds(lambda: SEP.ilrma(X, b0, a0, BI.ITER_HI), 3)
-    call = BI.best_seconds(lambda: SEP.ilrma(X, b0, a0, BI.ITER_CALL), 3)
-    iva_lo = BI.best_seconds(lambda: SEP.auxiva(X, BI.ITER_LO), 3)
-    iva_hi = BI.best_seconds(lambda: SEP.auxiva(X, BI.ITER_HI), 3)
-    out = SEP.ilrma(X, b0, a0, BI.ITER_CALL)
-    span = BI.ITER_HI - BI.ITER_LO
+    X = FB.mixture(B, D, D, torch.complex128)
+    b0, a0 = SEP.nmf_init(B, D, F, T, L, generator=torch.Generator(device="cuda").manual_seed(0))
+    iteration, call, outside = FB.iteration_ms(lambda n: SEP.ilrma(X, b0, a0, n))
+    auxiva_iteration, _, _ = FB.iteration_ms(lambda n: SEP.auxiva(X, n), iter_call=None)
+    out = SEP.ilrma(X, b0, a0, ITER_CALL)
     byte_floor, flop_floor = floors(B, D, L, X.element_size())
-    print(json.dumps({"step": name, "B": B, "D": D, "L": L, "F": BI.F, "T": BI.T, "dtype": "complex128",
-                      "iteration_ms": (hi - lo) / span * 1e3, "byte_floor_ms": byte_floor * 1e3, "fp64_floor_ms": flop_floor * 1e3,
-                      "call_ms_20_iterations": call * 1e3, "outside_the_iterations_ms": (lo - BI.ITER_LO * (hi - lo) / span) * 1e3,
-                      "auxiva_iteration_ms": (iva_hi - iva_lo) / span * 1e3, "bins_with_status": int((out.status != 0).sum())}),
+    print(json.dumps({"step": name, "B": B, "D": D, "L": L, "F": F, "T": T, "dtype": "complex128",
+                      "iteration_ms": iteration, "byte_floor_ms": byte_floor * 1e3, "fp64_floor_ms": flop_floor * 1e3,
+                      "call_ms_20_iterations": call, "outside_the_iterations_ms": outside,
+                      "auxiva_iteration_ms": auxiva_iteration, "bins_with_status": int((out.status != 0).sum())}),
           flush=True)
 
 
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=BI.STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_ilrma: step %s ran out of its %d s; nothing more is started" % (name, BI.STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_ilrma: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        print(done.stdout.strip().splitlines()[-1], flush=True)
+    FB.main(__file__, STEPS, step)
 
 
 if __name__ == "__main__":

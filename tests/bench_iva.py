@@ -10,57 +10,16 @@ and nothing more is started on the device.  For the kernels' own times run `pyth
 under rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-F, T = 201, 500
+from family_bench import COPY_BYTES_PER_S, FP64_FLOP_PER_S, ITER_CALL, F, T  # noqa: E402
+
 SHAPES = ((64, 2), (8, 8))
-ITER_LO, ITER_HI, ITER_CALL = 4, 12, 20
-COPY_BYTES_PER_S = 6.3e12
-FP64_FLOP_PER_S = 78.6e12
-STEP_SECONDS = 300
 STEPS = tuple("%d-%d-%s" % (B, D, c) for B, D in SHAPES for c in ("complex64", "complex128"))
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    import torch
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
-
-
-def mixture(B, D, cdtype):
-    """(B, D, F, T) on the device: iva_ref.case's recipe -- per source a per-frame activity gamma(0.3) + 1e-3 shared by all bins
-    times complex Gaussian noise, mixed by a random complex D x D matrix per bin."""
-    import torch
-    g = torch.Generator(device="cuda").manual_seed(0)
-
-    def gauss(*shape):
-        return torch.complex(torch.randn(shape, dtype=torch.float64, device="cuda", generator=g),
-                             torch.randn(shape, dtype=torch.float64, device="cuda", generator=g))
-    act = torch.distributions.Gamma(torch.tensor(0.3, dtype=torch.float64), torch.tensor(1.0, dtype=torch.float64))
-    torch.manual_seed(0)
-    activity = act.sample((B, D, 1, T)).cuda() + 1e-3
-    S = activity * gauss(B, D, F, T)
-    X = torch.einsum("bfdk,bkft->bdft", gauss(B, F, D, D), S)
-    return X.to(cdtype).contiguous()
 
 
 def floors(B, D, itemsize):
@@ -78,11 +37,9 @@ def step(name):
     from acoustic_locating_vq_vae import separation as SEP
     B, D, cname = name.split("-")
     B, D, cdtype = int(B), int(D), getattr(torch, cname)
-    X = mixture(B, D, cdtype)
-    lo = best_seconds(lambda: SEP.auxiva(X, ITER_LO), 3)
-    hi = best_seconds(lambda: SEP.auxiva(X, ITER_HI), 3)
-    call = best_seconds(lambda: SEP.auxiva(X, ITER_CALL), 3)
-    masks = best_seconds(lambda: SEP.masks(X), 10)
+    X = FB.mixture(B, D, D, cdtype)
+    iteration, call, outside = FB.iteration_ms(lambda n: SEP.auxiva(X, n))
+    masks = FB.best_seconds(lambda: SEP.masks(X), 10)
     out = SEP.auxiva(X, ITER_CALL)
     byte_floor, flop_floor = floors(B, D, X.element_size())
     x1 = X[:1].to(torch.complex128).cpu().numpy()
@@ -90,9 +47,9 @@ def step(name):
     ref = R.auxiva(x1, 2)
     cpu = (time.perf_counter() - t0) / 2
     two = SEP.auxiva(X[:1].to(torch.complex128), 2)
-    print(json.dumps({"step": name, "B": B, "D": D, "F": F, "T": T, "dtype": cname, "iteration_ms": (hi - lo) / (ITER_HI - ITER_LO) * 1e3,
-                      "byte_floor_ms": byte_floor * 1e3, "fp64_floor_ms": flop_floor * 1e3, "call_ms_20_iterations": call * 1e3,
-                      "outside_the_iterations_ms": (lo - ITER_LO * (hi - lo) / (ITER_HI - ITER_LO)) * 1e3, "masks_ms": masks * 1e3,
+    print(json.dumps({"step": name, "B": B, "D": D, "F": F, "T": T, "dtype": cname, "iteration_ms": iteration,
+                      "byte_floor_ms": byte_floor * 1e3, "fp64_floor_ms": flop_floor * 1e3, "call_ms_20_iterations": call,
+                      "outside_the_iterations_ms": outside, "masks_ms": masks * 1e3,
                       "bins_with_status": int((out.status != 0).sum()),
                       "restatement_cpu_ms_per_iteration_at_B_1": cpu * 1e3,
                       "max_rel_diff_of_w_to_restatement_at_B_1": float(np.abs(two.w.cpu().numpy() - ref.W).max() / np.abs(ref.W).max())}),
@@ -100,17 +57,7 @@ def step(name):
 
 
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_iva: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_iva: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        print(done.stdout.strip().splitlines()[-1], flush=True)
+    FB.main(__file__, STEPS, step)
 
 
 if __name__ == "__main__":

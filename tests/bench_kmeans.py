@@ -9,10 +9,8 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 os.environ.setdefault("OMP_NUM_THREADS", "16")
 import numpy as np
 import torch
@@ -22,18 +20,6 @@ from acoustic_locating_vq_vae import _native as N
 from acoustic_locating_vq_vae import kmeans as KM
 
 D, K, PEAK = 128, 1024, 157.3e12
-
-
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(reps):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) / reps
 
 
 def main():
@@ -46,15 +32,15 @@ def main():
     xc = N.kmeans_add_rows(x, mean, -1.0)
     T = 2 + int(np.log(K))
     u = torch.rand((K - 1, T), dtype=torch.float64, generator=torch.Generator().manual_seed(1))
-    seed_ms = timed(lambda: KM._kmeans_plusplus(xc, K, 0, u), 3)
+    seed_ms = FB.event_ms(lambda: KM._kmeans_plusplus(xc, K, 0, u), 3)
     init, _ = KM._kmeans_plusplus(xc, K, 0, u)
     labels = N.vq_argmin(xc, init)
     new = torch.empty_like(init)
     stats = torch.empty(1, device="cuda", dtype=torch.float64)
     flags = torch.empty(4, device="cuda", dtype=torch.int32)
     ws = N.kmeans_update(xc, labels, None, init, new, None, stats, flags, 0.0)
-    assign_ms = timed(lambda: N.vq_argmin(xc, init), 20)
-    update_ms = timed(lambda: N.kmeans_update(xc, labels, labels, init, new, None, stats, flags, 0.0, ws), 20)
+    assign_ms = FB.event_ms(lambda: N.vq_argmin(xc, init), 20)
+    update_ms = FB.event_ms(lambda: N.kmeans_update(xc, labels, labels, init, new, None, stats, flags, 0.0, ws), 20)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     km = KM.KMeans(n_clusters=K, random_state=0, max_iter=30).fit(x)
@@ -68,13 +54,13 @@ def main():
     R.update(xs, lab_s, init.double().cpu().numpy(), K)
     ref_iter_ms = (time.perf_counter() - t0) * 1e3
     small = xc[:ns].contiguous()
-    dev_iter_small = timed(lambda: N.kmeans_update(small, N.vq_argmin(small, init), None, init, torch.empty_like(init), None,
-                                                   stats, flags, 0.0), 10)
+    dev_iter_small = FB.event_ms(lambda: N.kmeans_update(small, N.vq_argmin(small, init), None, init, torch.empty_like(init),
+                                                         None, stats, flags, 0.0), 10)
     us = u[:63]
     t0 = time.perf_counter()
     R.kmeans_plusplus(xs, 64, 0, us.numpy())
     ref_pp_ms = (time.perf_counter() - t0) * 1e3
-    dev_pp_small = timed(lambda: KM._kmeans_plusplus(small, 64, 0, us), 5)
+    dev_pp_small = FB.event_ms(lambda: KM._kmeans_plusplus(small, 64, 0, us), 5)
     out = {
         "N": n, "D": D, "K": K,
         "lloyd_ms_per_iter": round(assign_ms + update_ms, 4),

@@ -12,11 +12,8 @@ import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
-import torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 from torch.utils.data import DataLoader
 
 from acoustic_locating_vq_vae.data_preprocessing import spec_dataset_preprocessing
@@ -26,13 +23,7 @@ from oracle import data_oracle as DO
 
 
 def rate(fn, steps):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
-    torch.cuda.synchronize()
-    return steps / (time.perf_counter() - t0)
+    return 1.0 / FB.wall_seconds(fn, steps)
 
 
 def main():

@@ -10,25 +10,13 @@ import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from family_bench import wall_seconds  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 import numpy as np
 import torch
 
 import rir_ref as R
 from acoustic_locating_vq_vae import front_end as FE
-
-
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps
 
 
 def main():
@@ -40,11 +28,11 @@ def main():
     theta = torch.rand(B, dtype=torch.float64, device="cuda", generator=g) * (2 * math.pi) - math.pi
     src = FE.source_positions(theta, rcv, room, cfg["R"], cfg["Z_LOC_SOURCE"])
     rcv_d = torch.tensor(rcv, dtype=torch.float64, device="cuda")
-    t_rir = timed(lambda: FE.room_impulse_responses(src, rcv_d, room, reverberation_time=T60, nsample=ns), 10)
+    t_rir = wall_seconds(lambda: FE.room_impulse_responses(src, rcv_d, room, reverberation_time=T60, nsample=ns), 10)
     # the high-pass share: the same call without it
-    t_nohp = timed(lambda: FE.room_impulse_responses(src, rcv_d, room, reverberation_time=T60, nsample=ns, hp_filter=False), 10)
+    t_nohp = wall_seconds(lambda: FE.room_impulse_responses(src, rcv_d, room, reverberation_time=T60, nsample=ns, hp_filter=False), 10)
     wave = torch.randn(B, 80000, device="cuda", generator=g)
-    t_gen = timed(lambda: FE.generate_samples(wave, theta=theta), 5)
+    t_gen = wall_seconds(lambda: FE.generate_samples(wave, theta=theta), 5)
     # images that reach the response and their taps (counted from the restatement, one item)
     beta = R.sabine_beta(room, FE.SOUND_SPEED, T60)
     src_h = src.cpu().numpy()

@@ -11,10 +11,8 @@ import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 import numpy as np
 import torch
 
@@ -23,7 +21,6 @@ from acoustic_locating_vq_vae import _native as N
 from acoustic_locating_vq_vae import front_end as FE
 from acoustic_locating_vq_vae import room_acoustics as RA
 
-HBM_BYTES_PER_S = 6.3e12
 FS = 16000.0
 
 
@@ -77,7 +74,7 @@ def main():
     for B, n, reps, rows in ((64, 6400, 200, 64), (4096, 12800, 20, 512)):
         h = responses(B, n, g)
         t = launch_seconds(h, reps)
-        bound = B * n * 8 / HBM_BYTES_PER_S
+        bound = B * n * 8 / FB.COPY_BYTES_PER_S
         cpu = host_rows_per_second(h, threads, rows)
         print(json.dumps({"B": B, "n": n, "gpu_us_per_launch": t * 1e6, "one_read_bound_us": bound * 1e6,
                           "ratio_to_bound": t / bound, "gpu_rows_per_s": B / t, "read_GB_per_s": B * n * 8 / t / 1e9,

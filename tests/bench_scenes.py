@@ -6,26 +6,13 @@ five-second crops of a resident pool, scenes drawn per batch, RIR -> FIR -> STFT
 import json
 import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from family_bench import wall_seconds  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 import torch  # noqa: E402
 
 from acoustic_locating_vq_vae import front_end as FE  # noqa: E402
 from acoustic_locating_vq_vae.rir_dataset_generator.scene_loader import SceneLoader  # noqa: E402
-
-
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps
 
 
 def main():
@@ -34,14 +21,14 @@ def main():
     ns = cfg["n_sample"]
     g = torch.Generator(device="cuda").manual_seed(0)
     same = FE.sample_scenes(B, FE.SceneConfig.from_dataset_config(), generator=g)
-    t_one = timed(lambda: FE.room_impulse_responses(same.source, same.receiver, cfg["room_dimensions"],
-                                                    reverberation_time=cfg["reverberation_time"], nsample=ns), 10)
-    t_same = timed(lambda: FE.scene_impulse_responses(same.source, same.receiver, same.room, beta=same.beta, nsample=ns), 10)
+    t_one = wall_seconds(lambda: FE.room_impulse_responses(same.source, same.receiver, cfg["room_dimensions"],
+                                                   reverberation_time=cfg["reverberation_time"], nsample=ns), 10)
+    t_same = wall_seconds(lambda: FE.scene_impulse_responses(same.source, same.receiver, same.room, beta=same.beta, nsample=ns), 10)
     rnd = FE.sample_scenes(B, FE.SceneConfig(), generator=g)
-    t_rnd = timed(lambda: FE.scene_impulse_responses(rnd.source, rnd.receiver, rnd.room, beta=rnd.beta, nsample=ns), 10)
+    t_rnd = wall_seconds(lambda: FE.scene_impulse_responses(rnd.source, rnd.receiver, rnd.room, beta=rnd.beta, nsample=ns), 10)
     waves = [torch.randn(80000 + 4000 * i, generator=torch.Generator().manual_seed(i)) for i in range(256)]
     loader = SceneLoader(waves, B, FE.SceneConfig(), seed=0)
-    t_batch = timed(lambda: next(loader), 10)
+    t_batch = wall_seconds(lambda: next(loader), 10)
     print(json.dumps({"batch": B, "nsample": ns,
                       "one_room_rirs_per_s": B / t_one, "per_item_dataset_scene_rirs_per_s": B / t_same,
                       "per_item_vs_one_room": t_one / t_same, "random_rooms_rirs_per_s": B / t_rnd,

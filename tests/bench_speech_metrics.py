@@ -11,10 +11,8 @@ import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src"), os.path.join(ROOT, "tests", "helpers")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 import numpy as np
 import scipy.signal
 import torch
@@ -22,25 +20,7 @@ import torch
 import speech_metrics_ref as R
 from acoustic_locating_vq_vae import speech_metrics as M
 
-HBM_BYTES_PER_S = 6.3e12
 B, N, FS = 64, 80000, 16000
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
 
 
 def host_row(pair):
@@ -66,15 +46,15 @@ def main():
     degraded = clean + 0.5 * torch.randn(B, N, dtype=torch.float64, device="cuda", generator=g)
     c10, d10 = M.resample_poly(clean, 10000, FS), M.resample_poly(degraded, 10000, FS)
 
-    whole = best_seconds(lambda: M.stoi(clean, degraded, fs=FS), 20)
-    resample = best_seconds(lambda: (M.resample_poly(clean, 10000, FS), M.resample_poly(degraded, 10000, FS)), 20)
-    at_10k = best_seconds(lambda: M.stoi(c10, d10, fs=10000), 20)
+    whole = FB.best_seconds(lambda: M.stoi(clean, degraded, fs=FS), 20)
+    resample = FB.best_seconds(lambda: (M.resample_poly(clean, 10000, FS), M.resample_poly(degraded, 10000, FS)), 20)
+    at_10k = FB.best_seconds(lambda: M.stoi(c10, d10, fs=10000), 20)
     got = M.stoi(clean, degraded, fs=FS)
     assert got.status.tolist() == [0] * B
     rows = 32
     cpu, values = host_rows_per_second(clean.cpu().numpy(), degraded.cpu().numpy(), threads, rows)
     err = float(np.abs(got.value[:rows].cpu().numpy() - np.array(values)).max())
-    bound = 2 * B * N * 8 / HBM_BYTES_PER_S
+    bound = 2 * B * N * 8 / FB.COPY_BYTES_PER_S
     print(json.dumps({"B": B, "n": N, "fs": FS, "gpu_us_per_call": whole * 1e6, "resample_us": resample * 1e6,
                       "stoi_at_10k_us": at_10k * 1e6, "one_read_bound_us": bound * 1e6, "ratio_to_bound": whole / bound,
                       "gpu_rows_per_s": B / whole, "cpu_rows_per_s": cpu, "cpu_threads": threads, "cpu_rows_timed": rows,

@@ -10,39 +10,21 @@ The achieved float64 rate counts 8 flops per rotation (the four fused multiply-a
 sincospi of the D phasors per candidate and bin and the D products with z_i are not counted)."""
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-B, D, F, T = 64, 8, 201, 500
+from family_bench import F, T  # noqa: E402
+
+B, D = 64, 8
 N_FFT, FS, C = 400, 16000.0, 340.0
 BAND = (8, 187)
-P, FB = D * (D - 1) // 2, BAND[1] - BAND[0] + 1
+P, F_BAND = D * (D - 1) // 2, BAND[1] - BAND[0] + 1
 FLOPS_PER_ROTATION = 8
 CHUNK = 1024                 # candidates per step of the torch composition
-STEP_SECONDS = 300
 STEPS = ("phat", "ring", "grid", "torch_phat", "torch_ring", "torch_grid")
-
-
-def best_seconds(fn, reps, rounds=5):
-    """Seconds per call of fn from device events around reps calls, the best of ``rounds``."""
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
+WARMUPS = 1                  # not family_bench's two: this script's figures in DESIGN.md were taken after one warm-up call
 
 
 def scene():
@@ -51,20 +33,16 @@ def scene():
     import math
     import torch
     g = torch.Generator(device="cuda").manual_seed(0)
-    centre = torch.tensor([2.5, 1.5, 1.5], dtype=torch.float64, device="cuda")
-    mics = centre + 0.05 * (2 * torch.rand((D, 3), dtype=torch.float64, device="cuda", generator=g) - 1)
-    theta = -math.pi + 2 * math.pi * torch.arange(360, dtype=torch.float64, device="cuda") / 360
-    ring = centre + torch.stack((torch.cos(theta), torch.sin(theta), torch.ones_like(theta)), dim=1)
+    mics, ring = FB.array_microphones(g, D), FB.candidate_ring(360)
     ax = [0.05 + 0.1 * torch.arange(n, dtype=torch.float64, device="cuda") for n in (40, 50, 30)]
     grid = torch.stack(torch.meshgrid(*ax, indexing="ij"), dim=-1).reshape(-1, 3).contiguous()
     true = torch.randint(0, 360, (B,), device="cuda", generator=g)
     r = (ring[true][:, None, :] - mics[None]).norm(dim=-1)                                    # (B, D)
     omega = 2 * math.pi * torch.arange(F, dtype=torch.float64, device="cuda") * FS / N_FFT
-    randn = lambda *s: torch.randn(s, dtype=torch.float64, device="cuda", generator=g)         # noqa: E731
-    S = torch.complex(randn(B, 1, F, T), randn(B, 1, F, T))
+    S = FB.gauss(g, B, 1, F, T)
     phase = -omega[None, None, :] * r[:, :, None] / C                                         # (B, D, F)
     X = S * torch.polar((1.0 / r)[:, :, None].expand_as(phase).contiguous(), phase)[..., None]
-    X = X + 0.1 * torch.complex(randn(B, D, F, T), randn(B, D, F, T))
+    X = X + 0.1 * FB.gauss(g, B, D, F, T)
     return X, mics, ring, grid, true
 
 
@@ -110,14 +88,14 @@ def step(name):
     psi, _ = N.phat_cross_spectra(X, *BAND)
     cand = grid if name.endswith("grid") else ring
     if name == "phat":
-        out["seconds"] = best_seconds(lambda: N.phat_cross_spectra(X, *BAND), 10)
+        out["seconds"] = FB.best_seconds(lambda: N.phat_cross_spectra(X, *BAND), 10, warmups=WARMUPS)
     elif name in ("ring", "grid"):
         run = lambda: N.srp_phat(psi, mics, cand, FS, N_FFT, C, *BAND)                        # noqa: E731
         m, best, status = run()
         out["G"] = cand.shape[0]
-        out["seconds"] = best_seconds(run, 10 if name == "ring" else 3)
+        out["seconds"] = FB.best_seconds(run, 10 if name == "ring" else 3, warmups=WARMUPS)
         out["items_with_status"] = int((status != 0).sum())
-        rotations = B * cand.shape[0] * P * FB
+        rotations = B * cand.shape[0] * P * F_BAND
         out["rotations_per_s"] = rotations / out["seconds"]
         out["float64_flops_per_s"] = FLOPS_PER_ROTATION * rotations / out["seconds"]
         if name == "ring":
@@ -126,36 +104,27 @@ def step(name):
         full = torch_phat(X)
         i, j = torch.triu_indices(D, D, offset=1)
         out["max_abs_diff_to_fused"] = float((full[:, i, j] - psi[:, :, BAND[0]:BAND[1] + 1]).abs().max())
-        out["seconds"] = best_seconds(lambda: torch_phat(X), 3)
+        out["seconds"] = FB.best_seconds(lambda: torch_phat(X), 3, warmups=WARMUPS)
     else:
         full = torch_phat(X)
         composed = torch_srp(full, mics, cand)
         out["G"] = cand.shape[0]
         out["max_abs_diff_to_fused"] = float((composed - LOC.srp_phat(X, mics, cand, FS, N_FFT, C, BAND).map).abs().max())
-        out["seconds"] = best_seconds(lambda: torch_srp(full, mics, cand), 1, rounds=3)
+        out["seconds"] = FB.best_seconds(lambda: torch_srp(full, mics, cand), 1, rounds=3, warmups=WARMUPS)
     print(json.dumps(out), flush=True)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    results = {}
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_srp: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_srp: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        results[name] = json.loads(done.stdout.strip().splitlines()[-1])
-        print(json.dumps(results[name]), flush=True)
+def summarise(results):
     ms = {k: v["seconds"] * 1e3 for k, v in results.items()}
     print(json.dumps({"phat_ms": ms["phat"], "torch_phat_ms": ms["torch_phat"], "ring_ms": ms["ring"], "torch_ring_ms": ms["torch_ring"],
                       "grid_ms": ms["grid"], "torch_grid_ms": ms["torch_grid"],
                       "torch_over_fused": {k: ms["torch_" + k] / ms[k] for k in ("phat", "ring", "grid")},
                       "grid_float64_tflops": results["grid"]["float64_flops_per_s"] / 1e12,
                       "max_abs_diff": {k: results["torch_" + k]["max_abs_diff_to_fused"] for k in ("phat", "ring", "grid")}}), flush=True)
+
+
+def main():
+    FB.main(__file__, STEPS, step, summarise)
 
 
 if __name__ == "__main__":

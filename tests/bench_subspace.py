@@ -11,38 +11,18 @@ and nothing more is started on the device.  For a kernel's own time run `python 
 (or fused_music, fused_gev) once under rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-B, D, F, T, G = 64, 8, 201, 500, 360
+from family_bench import F, T  # noqa: E402
+
+B, D, G = 64, 8, 360
 K = 2
 BAND = (8, 187)
 LOADING = 1e-6
-STEP_SECONDS = 300
 STEPS = ("fused_eigh", "torch_eigh", "fused_music", "srp_map", "fused_gev", "fused_souden", "music_whole", "srp_whole")
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    import torch
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
 
 
 def scene():
@@ -51,18 +31,11 @@ def scene():
     import torch
     from acoustic_locating_vq_vae import beamforming as BF
     g = torch.Generator(device="cuda").manual_seed(0)
-
-    def gauss(*shape):
-        return torch.complex(torch.randn(shape, dtype=torch.float64, device="cuda", generator=g),
-                             torch.randn(shape, dtype=torch.float64, device="cuda", generator=g))
-    centre = torch.tensor([2.5, 1.5, 1.5], dtype=torch.float64, device="cuda")
-    mics = centre + 0.05 * (2 * torch.rand((D, 3), dtype=torch.float64, device="cuda", generator=g) - 1)
-    theta = -3.141592653589793 + 6.283185307179586 * torch.arange(G, dtype=torch.float64, device="cuda") / G
-    cand = centre + torch.stack((torch.cos(theta), torch.sin(theta), torch.ones_like(theta)), dim=-1)        # (G, 3)
+    mics, cand = FB.array_microphones(g, D), FB.candidate_ring(G)
     pick = torch.randint(0, G, (2, B), device="cuda", generator=g)
     A, _ = BF.steering_vectors(mics, cand[pick[0]], F)
     Bv, _ = BF.steering_vectors(mics, cand[pick[1]], F)
-    X = A[..., None] * gauss(B, 1, F, T) + Bv[..., None] * gauss(B, 1, F, T) + 0.03 * gauss(B, D, F, T)
+    X = A[..., None] * FB.gauss(g, B, 1, F, T) + Bv[..., None] * FB.gauss(g, B, 1, F, T) + 0.03 * FB.gauss(g, B, D, F, T)
     mask = torch.rand((B, F, T), dtype=torch.float64, device="cuda", generator=g)
     return X, mask, mics, cand
 
@@ -110,25 +83,11 @@ def step(name):
         fn = lambda: LOC.srp_phat(X, mics, cand, c=340.0, band=BAND)                                          # noqa: E731
     else:
         sys.exit("bench_subspace: no step %r" % name)
-    out["seconds"] = best_seconds(fn, reps)
+    out["seconds"] = FB.best_seconds(fn, reps)
     print(json.dumps(out), flush=True)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    results = {}
-    for name in STEPS:
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_subspace: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_subspace: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        results[name] = json.loads(done.stdout.strip().splitlines()[-1])
-        print(json.dumps(results[name]), flush=True)
-
+def summarise(results):
     def ms(name):
         return results[name]["seconds"] * 1e3
     eigh = {"launch": "eigh", "fused_ms": ms("fused_eigh"), "matrices_per_s": B * F / results["fused_eigh"]["seconds"]}
@@ -144,6 +103,10 @@ def main():
                       "gev_over_souden": ms("fused_gev") / ms("fused_souden")}), flush=True)
     print(json.dumps({"launch": "spectrogram to map", "music_ms": ms("music_whole"), "srp_ms": ms("srp_whole"),
                       "music_over_srp": ms("music_whole") / ms("srp_whole")}), flush=True)
+
+
+def main():
+    FB.main(__file__, STEPS, step, summarise)
 
 
 if __name__ == "__main__":

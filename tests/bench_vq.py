@@ -4,10 +4,8 @@ on a 4096-row sample."""
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench  # noqa: E402,F401  (it puts the repository, the package and tests/helpers on the path)
 import torch
 from acoustic_locating_vq_vae import _native as N
 from oracle import vqvae_oracle as O

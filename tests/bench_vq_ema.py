@@ -11,10 +11,8 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 os.environ.setdefault("OMP_NUM_THREADS", "16")
 import numpy as np
 import torch
@@ -28,16 +26,8 @@ K = 1024
 SPEECH = (201, 1024, 128, 3, 1024, 0.25, K)
 
 
-def timed_us(fn, reps=200):
-    fn()
-    torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    for _ in range(reps):
-        fn()
-    ev[1].record()
-    torch.cuda.synchronize()
-    return ev[0].elapsed_time(ev[1]) * 1e3 / reps
+def us_per_call(fn):
+    return FB.event_ms(fn, 200) * 1e3
 
 
 def update_cost(n, D):
@@ -59,8 +49,8 @@ def update_cost(n, D):
     def both():
         stats()
         update()
-    return {"N": n, "K": K, "D": D, "us": round(timed_us(both), 2), "stats_us": round(timed_us(stats), 2),
-            "update_us": round(timed_us(update), 2)}
+    return {"N": n, "K": K, "D": D, "us": round(us_per_call(both), 2), "stats_us": round(us_per_call(stats), 2),
+            "update_us": round(us_per_call(update), 2)}
 
 
 def trainer(decay, raw):

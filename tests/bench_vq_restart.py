@@ -12,10 +12,8 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 os.environ.setdefault("OMP_NUM_THREADS", "16")
 import numpy as np
 import torch
@@ -29,21 +27,8 @@ K, R = 1024, 64
 SPEECH = (201, 1024, 128, 3, 1024, 0.25, K)
 
 
-def timed_us(fn, reps=200, rounds=1, reset=None):
-    fn()
-    torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ms = 0.0
-    for _ in range(rounds):
-        if reset is not None:
-            reset()
-        ev[0].record()
-        for _ in range(reps):
-            fn()
-        ev[1].record()
-        torch.cuda.synchronize()
-        ms += ev[0].elapsed_time(ev[1])
-    return ms * 1e3 / (reps * rounds)
+def us_per_call(fn, reps=200, rounds=1, reset=None):
+    return FB.event_ms(fn, reps, rounds, reset) * 1e3
 
 
 def launch_cost(n, D):
@@ -63,11 +48,11 @@ def launch_cost(n, D):
     def dead():
         N.vq_restart_dead(cand, cs, W, E, counters, 0.5)
 
-    out = {"N": n, "K": K, "D": D, "R": R, "gather_us": round(timed_us(gather), 2)}
+    out = {"N": n, "K": K, "D": D, "R": R, "gather_us": round(us_per_call(gather), 2)}
     cs.fill_(1.0)                                             # above the threshold: the scan alone
-    out["dead_idle_us"] = round(timed_us(dead), 2)
+    out["dead_idle_us"] = round(us_per_call(dead), 2)
     # every code dead: K / R calls restart R codes each before the codebook is alive again
-    out["dead_restarting_us"] = round(timed_us(dead, reps=K // R, rounds=20, reset=lambda: cs.zero_()), 2)
+    out["dead_restarting_us"] = round(us_per_call(dead, reps=K // R, rounds=20, reset=lambda: cs.zero_()), 2)
     assert int(status.item()) == 0 and counters[0].item() > 0
     return out
 

@@ -8,35 +8,16 @@ the script, and nothing more is started on the device.  For the kernel's own tim
 `python tests/bench_wpe.py --step fused` once under rocprofv3 --kernel-trace --stats."""
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import family_bench as FB  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
 
-B, D, F, T = 64, 1, 201, 500
+from family_bench import F, T  # noqa: E402
+
+B, D = 64, 1
 TAPS, DELAY, ITERATIONS, PSD_CONTEXT, EPS, LOADING = 10, 3, 3, 0, 1e-10, 1e-10
-STEP_SECONDS = 300
-
-
-def best_seconds(fn, reps):
-    """Seconds per call of fn from device events around reps calls, the best of 5."""
-    import torch
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / reps)
-    return best
+STEPS = ("fused", "torch")
 
 
 def reverberant_spectrogram():
@@ -46,12 +27,10 @@ def reverberant_spectrogram():
     g = torch.Generator(device="cuda").manual_seed(0)
     shape = (B, D, F, T)
     env = 0.05 + torch.sin(torch.arange(T, dtype=torch.float64, device="cuda") * 0.21).abs() ** 4
-    s = torch.complex(torch.randn(shape, dtype=torch.float64, device="cuda", generator=g),
-                      torch.randn(shape, dtype=torch.float64, device="cuda", generator=g)) * torch.sqrt(env / 2)
+    s = FB.gauss(g, *shape) * torch.sqrt(env / 2)
     x = s.clone()
     for k in range(8):
-        gain = 0.4 * 0.7 ** k * torch.complex(torch.randn((B, D, F, 1), dtype=torch.float64, device="cuda", generator=g),
-                                              torch.randn((B, D, F, 1), dtype=torch.float64, device="cuda", generator=g))
+        gain = 0.4 * 0.7 ** k * FB.gauss(g, B, D, F, 1)
         x[..., DELAY + k:] += gain * s[..., :T - DELAY - k]
     return x
 
@@ -89,7 +68,7 @@ def step(name):
     fused = DV.wpe(X, TAPS, DELAY, ITERATIONS, PSD_CONTEXT, EPS, LOADING)
     out = {"step": name, "B": B, "D": D, "F": F, "T": T, "taps": TAPS, "delay": DELAY, "iterations": ITERATIONS}
     if name == "fused":
-        out["seconds"] = best_seconds(lambda: DV.wpe(X, TAPS, DELAY, ITERATIONS, PSD_CONTEXT, EPS, LOADING), 10)
+        out["seconds"] = FB.best_seconds(lambda: DV.wpe(X, TAPS, DELAY, ITERATIONS, PSD_CONTEXT, EPS, LOADING), 10)
         out["bins_with_status"] = int((fused.status != 0).sum())
         terms = B * F * ITERATIONS * T * (TAPS * D * (TAPS * D + 1) / 2 + 2 * TAPS * D * D)   # correlation build and filter
         out["complex_macs_per_s"] = terms / out["seconds"]
@@ -97,27 +76,18 @@ def step(name):
         composed = torch_wpe(X)
         out["max_abs_diff_to_fused"] = float((composed - fused.spec).abs().max())
         out["max_abs_x"] = float(X.abs().max())
-        out["seconds"] = best_seconds(lambda: torch_wpe(X), 3)
+        out["seconds"] = FB.best_seconds(lambda: torch_wpe(X), 3)
     print(json.dumps(out), flush=True)
 
 
-def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--step":
-        return step(sys.argv[2])
-    results = {}
-    for name in ("fused", "torch"):
-        try:
-            done = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name], timeout=STEP_SECONDS,
-                                  stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            sys.exit("bench_wpe: step %s ran out of its %d s; nothing more is started" % (name, STEP_SECONDS))
-        if done.returncode != 0:
-            sys.exit("bench_wpe: step %s ended with status %d; nothing more is started" % (name, done.returncode))
-        results[name] = json.loads(done.stdout.strip().splitlines()[-1])
-        print(json.dumps(results[name]), flush=True)
+def summarise(results):
     print(json.dumps({"fused_ms": results["fused"]["seconds"] * 1e3, "torch_ms": results["torch"]["seconds"] * 1e3,
                       "torch_over_fused": results["torch"]["seconds"] / results["fused"]["seconds"],
                       "max_abs_diff": results["torch"]["max_abs_diff_to_fused"]}), flush=True)
+
+
+def main():
+    FB.main(__file__, STEPS, step, summarise)
 
 
 if __name__ == "__main__":

@@ -7,29 +7,18 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "acoustic_locating_vq-vae_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "src")):
-    sys.path.insert(0, p)
-import torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "helpers"))
+from family_bench import best_seconds  # noqa: E402  (it puts the repository, the package and tests/helpers on the path)
+import torch  # noqa: E402
 from acoustic_locating_vq_vae import speech_metrics as SM
 
 K = J = 8
 WINDOWS = 5
 
 
-def window_seconds(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / reps
-
-
 def best_alternating(fns, reps):
-    """Seconds per call of each of fns: windows of reps calls, the candidates taking turns, the best window of each."""
+    """Seconds per call of each of fns: windows of reps calls (family_bench's timer, one round, its warm-up done here for all
+    candidates first), the candidates taking turns, the best window of each."""
     for fn in fns:
         for _ in range(3):
             fn()
@@ -37,7 +26,7 @@ def best_alternating(fns, reps):
     best = [float("inf")] * len(fns)
     for _ in range(WINDOWS):
         for i, fn in enumerate(fns):
-            best[i] = min(best[i], window_seconds(fn, reps))
+            best[i] = min(best[i], best_seconds(fn, reps, rounds=1, warmups=0))
     return best
 
 
