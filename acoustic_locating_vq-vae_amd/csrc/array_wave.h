@@ -1,6 +1,6 @@
 // The one owner of the vocabulary the microphone-array kernels share (included by beamform.hip, subspace.hip, herm_eig.h,
-// iva_kernels.h and through it iva.hip and ilrma.hip, cacgmm.hip, wpe.hip, srp_phat.hip, separation_metrics.hip,
-// permutation_align.hip):
+// iva_kernels.h and through it iva.hip and ilrma.hip, cacgmm.hip, wpe.hip, steered_map.h and through it srp_phat.hip,
+// separation_metrics.hip, permutation_align.hip):
 //   scalars      Cplx<R> (the complex type of a real type), is_finite, the complex products cmul / cmul_conj / conj_cmul, the
 //                quotient cdiv, and cshfl, a double2 read from another lane.  The library is built with -ffp-contract=off, so
 //                every product and sum here is rounded where it is written: a helper has the bits of its expression, and

@@ -14,7 +14,8 @@
 //                    the order depends on (D, T) alone.  Every lane ends with every total; lane e < D^2 picks entry e
 //                    (the upper triangle as the negated imaginary part of the lower) and divides it by the mask's sum: one
 //                    coalesced store of the bin's matrix.
-// bf_steer_kernel    a workgroup an item, a thread an entry (d, f): two distances, one sincospi.
+// bf_steer_kernel    a workgroup an item, a thread an entry (d, f): two distances (csrc/steered_map.h's steer_delay), one
+//                    sincospi on tau_d - tau_ref.  A non-finite coordinate sets that header's geometry bit.
 // bf_das_kernel      w = a / D, a thread an entry.
 // bf_mvdr_kernel     a wave a bin, four bins a workgroup, no LDS and no barrier: lane 8 r + c holds entry (r, c) of the
 //                    loaded Phi_n and of the right-hand sides (column 0 = a, or the D columns of Phi_s), and rows and columns
@@ -38,12 +39,8 @@
 // workgroups at a time.  No atomics anywhere; a bin shares nothing with its neighbours: it has the same bits alone, in any
 // batch and on any run.
 // What the launches cost: DESIGN.md.
-#include <cfloat>
-#include <climits>
-#include <cmath>
-
-#include "array_wave.h"
 #include "herm_eig.h"
+#include "steered_map.h"
 
 namespace alvq {
 
@@ -51,10 +48,9 @@ constexpr int BF_THREADS = 256;
 constexpr int BF_WAVES = BF_THREADS / kWave;
 constexpr int BF_WAVE_T = 1024;        // rows up to this long are summed by one wave, longer ones by the workgroup
 
-// status values of alvq_spatial_covariance_* and alvq_beamform_weights_f64, and the bit of alvq_steering_vectors_f64
+// status values of alvq_spatial_covariance_* and alvq_beamform_weights_f64
 constexpr int BF_BAD_INPUT = 1;        // a non-finite X, a negative or non-finite mask value, or a mask that sums to 0
 constexpr int BF_BAD_SOLVE = 2;        // a Cholesky pivot or the denominator <= 0 or not finite
-constexpr int BF_BAD_GEOMETRY = 4;     // a non-finite coordinate (srp_phat's bit)
 
 constexpr int BF_DAS = 0, BF_MVDR = 1, BF_SOUDEN = 2;
 
@@ -181,23 +177,19 @@ __global__ __launch_bounds__(BF_THREADS) void bf_steer_kernel(const double* mics
     if (!is_finite(m[e])) bad = 1;
   const double qx = q[0], qy = q[1], qz = q[2];
   if (!is_finite(qx) || !is_finite(qy) || !is_finite(qz)) bad = 1;
-  auto tau = [&](int d) -> double {
-    const double dx = qx - m[3 * d], dy = qy - m[3 * d + 1], dz = qz - m[3 * d + 2];
-    return sqrt(dx * dx + dy * dy + dz * dz) / c;
-  };
-  const double tau_ref = tau(ref);
+  const double tau_ref = steer_delay(qx, qy, qz, m, ref, c);
   double2* out = A + (long)b * D * F;
   for (int e = tid; e < D * F; e += BF_THREADS) {
     const int d = e / F, f = e - d * F;
     double2 v = make_double2(__longlong_as_double(0x7ff8000000000000LL), __longlong_as_double(0x7ff8000000000000LL));
     if (!bad) {
       double s, cs;
-      sincospi((double)(2 * f) * fs_over_n * (tau(d) - tau_ref), &s, &cs);      // e^{-j pi x}
+      sincospi((double)(2 * f) * fs_over_n * (steer_delay(qx, qy, qz, m, d, c) - tau_ref), &s, &cs);      // e^{-j pi x}
       v = make_double2(cs, -s);
     }
     out[e] = v;
   }
-  if (tid == 0) status[b] = bad ? BF_BAD_GEOMETRY : 0;
+  if (tid == 0) status[b] = bad ? MAP_BAD_GEOMETRY : 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ weights
@@ -486,10 +478,8 @@ extern "C" int alvq_steering_vectors_f64(const double* mics, const double* src, 
   ALVQ_REQUIRE(mics && src && A && status, ALVQ_EINVAL, "%s: null pointer", who);
   ALVQ_TRY(check_bins(who, B, F));
   ALVQ_TRY(check_mics(who, D));
-  ALVQ_REQUIRE(n_fft >= 2 && n_fft <= (1 << 24) && F <= (1 << 24), ALVQ_EINVAL, "%s: n_fft=%d F=%d (need 2 <= n_fft <= 2^24, F <= 2^24)",
-               who, n_fft, F);
-  ALVQ_REQUIRE(std::isfinite(fs) && fs > 0.0 && std::isfinite(c) && c > 0.0, ALVQ_EINVAL, "%s: fs=%g c=%g must be finite and > 0",
-               who, fs, c);
+  ALVQ_TRY(check_nfft(who, n_fft, F));
+  ALVQ_TRY(check_rates(who, fs, c));
   ALVQ_REQUIRE(ref >= 0 && ref < D, ALVQ_EINVAL, "%s: ref=%d (need 0 <= ref < D = %d)", who, ref, D);
   hipLaunchKernelGGL(bf_steer_kernel, dim3(B), dim3(BF_THREADS), 0, (hipStream_t)stream, mics, src, (double2*)A, status, D, F,
                      mics_batched ? 3L * D : 0L, fs / (double)n_fft, c, ref);

@@ -34,6 +34,8 @@
 //   the arg-reductions that carry an index with their own tie rule (vq.hip's argmin kernels, relocate_kernel,
 //                   room_acoustics.hip, pm_search of assign_search.h), the __shfl_down suffix scan of room_acoustics.hip, the ballot compaction of
 //                   stoi_mask_kernel, and everything in conv_tile.h / wgrad_*.h.
+//   the arg-max of the SRP map and the arg-min of the MUSIC null share one tie rule (the lowest index of the extremum) and one
+//                   kernel, map_peak_kernel<MAXIMUM, THREADS> of steered_map.h, next to the maps it serves.
 #pragma once
 #include <hip/hip_runtime.h>
 

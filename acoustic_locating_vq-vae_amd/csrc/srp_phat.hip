@@ -14,41 +14,26 @@
 //                    bytes fit; 90 KB at P = 28 and 201 bins), so that every lane of a wave reads the same address: a broadcast,
 //                    no bank conflicts; otherwise the same values are read from global memory (uniform addresses again).
 //                    Rotations are formed per microphone, not per pair: D phasors z_d = e^{j pi x}, x = (2 f fs / n_fft) tau_d,
-//                    per (candidate, bin).  CHOSEN: a rotation recurrence along f, re-anchored every K = SRP_ANCHOR = 8 bins.
-//                    At the bins f_lo, f_lo + 8, ... the phasors come from sincospi on x itself; at the 7 bins between, from
-//                    z_d <- z_d w_d with the step w_d = e^{j pi (2 fs / n_fft) tau_d} (sincospi, once per candidate): four fused
-//                    multiply-adds in place of a sincospi, which halved the launch.  A step leaves a relative error
-//                    of at most 3 u on the phasor, so at most 21 u before the next anchor and 42 u on a pair term: the tests'
-//                    bound carries + K for it next to its slack of 32.  The pair term is
+//                    per (candidate, bin), from csrc/steered_map.h's SteerWalk<D>: a rotation recurrence along f, re-anchored
+//                    every K = 8 bins, which leaves at most 21 u on a phasor and 42 u on a pair term: the tests' bound
+//                    carries + K for it next to its slack of 32.  The pair term is
 //                    psi z_i conj(z_j), summed as  s_f = sum_i Re(z_i sum_{j > i} psi_ij conj(z_j))  with i and j rising: four
 //                    fused multiply-adds per rotation (8 flops) and four more per microphone.  S = (sum_f w_f s_f) / (P W1) with
 //                    f rising.  The order, the anchors included (they sit at f_lo + 8 n), depends on (D, f_lo, f_hi) alone, and a
 //                    thread shares nothing with its neighbours: a candidate has the same bits alone or in any grid, an item
 //                    alone or in any batch.  D is a template argument so that the phasors and the pair loops live in
 //                    registers, fully unrolled.
-// srp_argmax_kernel  one workgroup an item: a thread keeps the first maximum of its candidates g = tid, tid + 256, ...; then
-//                    (value, index) pairs meet in a butterfly and over the waves under "larger value, or equal value and lower
-//                    index", which is associative and commutative: the lowest index of the maximum, on every run.
+// The arg-max is csrc/steered_map.h's map_peak_kernel<true, 256>; the status bits, the coordinate scan and the host rules of
+// n_fft, the band, G, fs and c are that header's too.
 // What the launches cost: DESIGN.md.
-#include <cfloat>
-#include <climits>
-#include <cmath>
-
-#include "array_wave.h"
+#include "steered_map.h"
 
 namespace alvq {
 
 constexpr int PHAT_THREADS = 256;
 constexpr int PHAT_WAVES = PHAT_THREADS / kWave;
-constexpr int PHAT_MAX_NFFT = 1 << 24;
 constexpr int PHAT_LDS_LIMIT = 160 * 1024 - 256;     // dynamic LDS: the 160 KiB less the static reduction scratch
 constexpr int SRP_THREADS = 512;
-constexpr int SRP_ANCHOR = 8;          // bins between two sincospi anchors of the rotation recurrence
-
-// status bits of alvq_phat_cross_spectra_* and alvq_srp_phat_f64
-constexpr int SRP_BAD_SPECTRUM = 1;    // a non-finite psi inside the band
-constexpr int SRP_SILENT = 2;          // every psi inside the band is 0
-constexpr int SRP_BAD_GEOMETRY = 4;    // a non-finite microphone or candidate coordinate
 
 __host__ __device__ inline int phat_pairs(int D) { return D * (D - 1) / 2; }
 
@@ -127,20 +112,12 @@ __global__ __launch_bounds__(PHAT_THREADS) void phat_status_kernel(const double2
   for (int e = tid; e < P * Fb; e += PHAT_THREADS) {
     const int p = e / Fb, f = f_lo + (e - p * Fb);
     const double2 v = row[(long)p * F + f];
-    if (!(fabs(v.x) <= DBL_MAX) || !(fabs(v.y) <= DBL_MAX)) seen |= 1;
+    if (!is_finite(v.x) || !is_finite(v.y)) seen |= 1;
     if (v.x != 0.0 || v.y != 0.0) seen |= 2;
   }
-  if (mics) {
-    const double* m = mics + (long)b * mics_stride;
-    for (int e = tid; e < 3 * D; e += PHAT_THREADS)
-      if (!(fabs(m[e]) <= DBL_MAX)) seen |= 4;
-    const double* q = cand + (long)b * cand_stride;
-    for (long e = tid; e < 3L * G; e += PHAT_THREADS)
-      if (!(fabs(q[e]) <= DBL_MAX)) seen |= 4;
-  }
+  if (mics) seen |= geometry_seen<PHAT_THREADS>(mics + (long)b * mics_stride, cand + (long)b * cand_stride, D, G, tid);
   seen = block_sum<kSequential, false, OpOr>(seen, s_flag);
-  if (tid == 0)
-    status[b] = ((seen & 1) ? SRP_BAD_SPECTRUM : 0) | ((seen & 2) ? 0 : SRP_SILENT) | ((seen & 4) ? SRP_BAD_GEOMETRY : 0);
+  if (tid == 0) status[b] = map_status(seen);
 }
 
 __global__ __launch_bounds__(PHAT_THREADS) void gcc_kernel(const double2* psi, double* r, long total, int F, int n_fft, int L,
@@ -186,7 +163,7 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_map_kernel(SrpArgs a) {
 
   const int st = a.status[b];                                            // the same in every thread of the workgroup
   if (st) {
-    if (g < a.G) out[g] = (st & (SRP_BAD_SPECTRUM | SRP_BAD_GEOMETRY)) ? __longlong_as_double(0x7ff8000000000000LL) : 0.0;
+    if (g < a.G) out[g] = (st & (MAP_BAD_SPECTRUM | MAP_BAD_GEOMETRY)) ? __longlong_as_double(0x7ff8000000000000LL) : 0.0;
     return;
   }
 
@@ -201,36 +178,11 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_map_kernel(SrpArgs a) {
   }
   if (g >= a.G) return;
 
-  const double* q = a.cand + (long)b * a.cand_stride + 3 * g;
-  const double* m = a.mics + (long)b * a.mics_stride;
-  const double qx = q[0], qy = q[1], qz = q[2];
-  double tau[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    const double dx = qx - m[3 * d], dy = qy - m[3 * d + 1], dz = qz - m[3 * d + 2];
-    tau[d] = sqrt(dx * dx + dy * dy + dz * dz) / a.c;
-  }
-
-  double wc[D], ws[D], zc[D], zs[D];                                     // the step e^{j pi (2 fs / n_fft) tau_d}; z_d of the bin
-#pragma unroll
-  for (int d = 0; d < D; ++d) sincospi(2.0 * a.fs_over_n * tau[d], &ws[d], &wc[d]);
-
+  SteerWalk<D> z(a.mics + (long)b * a.mics_stride, a.cand + (long)b * a.cand_stride + 3 * g, a.c, a.fs_over_n);
   double acc = 0.0;
   for (int k = 0; k < Fb; ++k) {
     const int f = a.f_lo + k;
-    if (k % SRP_ANCHOR == 0) {                                           // the same bins in every thread
-      const double kf = (double)(2 * f) * a.fs_over_n;
-#pragma unroll
-      for (int d = 0; d < D; ++d) sincospi(kf * tau[d], &zs[d], &zc[d]);
-    } else {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {                                      // z_d <- z_d w_d
-        const double c = fma(zc[d], wc[d], -(zs[d] * ws[d]));
-        const double sn = fma(zc[d], ws[d], zs[d] * wc[d]);
-        zc[d] = c;
-        zs[d] = sn;
-      }
-    }
+    z.move(k, f, a.fs_over_n);
     const double2* row = PSI_LDS ? lds + k * P : psig + f;               // pair p at row[p] or row[p F]
     double s = 0.0;
     int p = 0;
@@ -240,59 +192,17 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_map_kernel(SrpArgs a) {
 #pragma unroll
       for (int j = i + 1; j < D; ++j, ++p) {
         const double2 v = PSI_LDS ? row[p] : row[(long)p * a.F];
-        cr = fma(v.x, zc[j], cr);
-        cr = fma(v.y, zs[j], cr);
-        ci = fma(v.y, zc[j], ci);
-        ci = fma(-v.x, zs[j], ci);
+        cr = fma(v.x, z.zc[j], cr);
+        cr = fma(v.y, z.zs[j], cr);
+        ci = fma(v.y, z.zc[j], ci);
+        ci = fma(-v.x, z.zs[j], ci);
       }
-      s += fma(-zs[i], ci, zc[i] * cr);                                  // Re(z_i (cr + j ci))
+      s += fma(-z.zs[i], ci, z.zc[i] * cr);                              // Re(z_i (cr + j ci))
     }
     const double w = (f == 0 || 2 * f == a.n_fft) ? 1.0 : 2.0;
     acc = fma(w, s, acc);
   }
   out[g] = acc / a.norm;
-}
-
-__global__ __launch_bounds__(PHAT_THREADS) void srp_argmax_kernel(const double* map, const int* status, int* best, int G) {
-  __shared__ double s_val[PHAT_WAVES];
-  __shared__ int s_idx[PHAT_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
-  if (status[b]) {                                                       // the same in every thread
-    if (tid == 0) best[b] = -1;
-    return;
-  }
-  const double* row = map + (long)b * G;
-  double bv = -INFINITY;
-  int bi = INT_MAX;
-  for (int g = tid; g < G; g += PHAT_THREADS) {                          // g rising: the first maximum of the thread's candidates
-    const double v = row[g];
-    if (v > bv) {
-      bv = v;
-      bi = g;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    s_val[wv] = bv;
-    s_idx[wv] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < PHAT_WAVES; ++w)
-      if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) {
-        bv = s_val[w];
-        bi = s_idx[w];
-      }
-    best[b] = bi == INT_MAX ? -1 : bi;
-  }
 }
 
 }  // namespace alvq
@@ -302,9 +212,7 @@ using namespace alvq;
 static int phat_check_band(const char* who, int B, int D, int F, int f_lo, int f_hi) {
   ALVQ_TRY(check_bins(who, B, F));
   ALVQ_TRY(check_mics(who, D, 2));
-  ALVQ_REQUIRE(f_lo >= 0 && f_lo <= f_hi && f_hi < F, ALVQ_EINVAL, "%s: band %d..%d (need 0 <= f_lo <= f_hi < F = %d)", who, f_lo,
-               f_hi, F);
-  return ALVQ_OK;
+  return check_band(who, f_lo, f_hi, F);
 }
 
 // W1 = the sum of w_f over the band
@@ -318,8 +226,7 @@ template <typename R>
 static int phat_launch(const char* who, const R* X, double* psi, int* status, int B, int D, int F, int T, int f_lo, int f_hi,
                        void* stream) {
   ALVQ_REQUIRE(X && psi && status, ALVQ_EINVAL, "%s: null pointer", who);
-  const int rc = phat_check_band(who, B, D, F, f_lo, f_hi);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(phat_check_band(who, B, D, F, f_lo, f_hi));
   ALVQ_TRY(check_frames(who, T));
   const size_t row_bytes = 16 * (size_t)D * T;
   const bool row_lds = option(OPT_PHAT_LDS) != 0 && row_bytes <= (size_t)PHAT_LDS_LIMIT;
@@ -350,10 +257,9 @@ extern "C" int alvq_phat_cross_spectra_f64(const double* X, double* psi, int* st
 extern "C" int alvq_gcc_phat_f64(const double* psi, double* r, int B, int D, int n_fft, int L, int f_lo, int f_hi, void* stream) {
   const char* who = "alvq_gcc_phat_f64";
   ALVQ_REQUIRE(psi && r, ALVQ_EINVAL, "%s: null pointer", who);
-  ALVQ_REQUIRE(n_fft >= 2 && n_fft <= PHAT_MAX_NFFT, ALVQ_EINVAL, "%s: n_fft=%d (need 2 <= n_fft <= 2^24)", who, n_fft);
+  ALVQ_TRY(check_nfft(who, n_fft));
   const int F = n_fft / 2 + 1;
-  const int rc = phat_check_band(who, B, D, F, f_lo, f_hi);
-  if (rc != ALVQ_OK) return rc;
+  ALVQ_TRY(phat_check_band(who, B, D, F, f_lo, f_hi));
   ALVQ_REQUIRE(L >= 0 && L <= n_fft / 2, ALVQ_EINVAL, "%s: L=%d (need 0 <= L <= n_fft / 2 = %d)", who, L, n_fft / 2);
   const long total = (long)B * phat_pairs(D) * (2L * L + 1);
   const long blocks = (total + PHAT_THREADS - 1) / PHAT_THREADS;
@@ -379,13 +285,11 @@ extern "C" int alvq_srp_phat_f64(const double* psi, const double* mics, const do
                                  int f_lo, int f_hi, void* stream) {
   const char* who = "alvq_srp_phat_f64";
   ALVQ_REQUIRE(psi && mics && cand && map && best && status, ALVQ_EINVAL, "%s: null pointer", who);
-  ALVQ_REQUIRE(n_fft >= 2 && n_fft <= PHAT_MAX_NFFT, ALVQ_EINVAL, "%s: n_fft=%d (need 2 <= n_fft <= 2^24)", who, n_fft);
+  ALVQ_TRY(check_nfft(who, n_fft));
   const int F = n_fft / 2 + 1;
-  const int rc = phat_check_band(who, B, D, F, f_lo, f_hi);
-  if (rc != ALVQ_OK) return rc;
-  ALVQ_REQUIRE(G >= 1 && (long)B * G <= INT_MAX, ALVQ_EINVAL, "%s: G=%d (need G >= 1, B G <= 2^31 - 1)", who, G);
-  ALVQ_REQUIRE(std::isfinite(fs) && fs > 0.0 && std::isfinite(c) && c > 0.0, ALVQ_EINVAL, "%s: fs=%g c=%g must be finite and > 0",
-               who, fs, c);
+  ALVQ_TRY(phat_check_band(who, B, D, F, f_lo, f_hi));
+  ALVQ_TRY(check_candidates(who, B, G));
+  ALVQ_TRY(check_rates(who, fs, c));
   ALVQ_REQUIRE((mics_stride == 0 || mics_stride >= 3L * D) && (cand_stride == 0 || cand_stride >= 3L * G), ALVQ_EINVAL,
                "%s: mics_stride=%ld cand_stride=%ld (need 0 or >= 3 D, 0 or >= 3 G)", who, (long)mics_stride, (long)cand_stride);
   const int P = phat_pairs(D), Fb = f_hi - f_lo + 1;
@@ -400,6 +304,7 @@ extern "C" int alvq_srp_phat_f64(const double* psi, const double* mics, const do
 #define SRP_CALL(N) srp_map_launch<N>(args, psi_lds, lds, grid, s)
   ALVQ_FOR_2_TO_8(D, SRP_CALL)
 #undef SRP_CALL
-  hipLaunchKernelGGL(srp_argmax_kernel, dim3(B), dim3(PHAT_THREADS), 0, s, (const double*)map, (const int*)status, best, G);
+  hipLaunchKernelGGL((map_peak_kernel<true, PHAT_THREADS>), dim3(B), dim3(PHAT_THREADS), 0, s, (const double*)map,
+                     (const int*)status, best, G);
   return check_launch(who);
 }

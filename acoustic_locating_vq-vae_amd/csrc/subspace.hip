@@ -10,34 +10,24 @@
 //                      matrices beyond, whole.
 // music_status_kernel  one workgroup an item: the OR over the item's band of V and lambda (a non-finite value; a non-zero
 //                      eigenvalue) and over its coordinates.  No atomics: wave_or, then the waves through LDS.
-// music_map_kernel<D>  srp_map_kernel's structure: a workgroup owns an item and a tile of 256 candidates, a thread a candidate,
-//                      and walks the band.  The D phasors z_d = e^{j pi x}, x = (2 f fs / n_fft) tau_d, come from that kernel's
-//                      rotation recurrence, re-anchored by sincospi every SUB_ANCHOR = 8 bins (the same K-term in the tests'
-//                      bound); a_d = conj(z_d).  The bin's eigenvalues and its K signal eigenvectors are read at addresses that
+// music_map_kernel<D>  a workgroup owns an item and a tile of 256 candidates, a thread a candidate, and walks the band.  The D
+//                      phasors z_d = e^{j pi x}, x = (2 f fs / n_fft) tau_d, come from csrc/steered_map.h's SteerWalk<D>: a
+//                      rotation recurrence, re-anchored by sincospi every 8 bins (the K-term in the tests' bound);
+//                      a_d = conj(z_d).  The bin's eigenvalues and its K signal eigenvectors are read at addresses that
 //                      do not depend on the thread (scalar loads, one fetch a wave).  p_k = sum_d conj(e_k[d]) a_d with d
 //                      rising from the first term, s = sum_k |p_k|^2 with k rising over the columns D - K .. D - 1, the bin adds
 //                      1 - s / D; bins rising; the sum is divided by the number of counted bins.  A thread shares nothing with
 //                      its neighbours: a candidate has the same bits alone or in any grid, an item alone or in any batch.
-// music_argmin_kernel  srp_argmax_kernel with the comparison turned round: the lowest index of the minimum, on every run.
+// The arg-min is csrc/steered_map.h's map_peak_kernel<false, 256>; the status bits, the coordinate scan and the host rules of
+// n_fft, the band, G, fs and c are that header's too.
 // What the launches cost: DESIGN.md.
-#include <cfloat>
-#include <climits>
-#include <cmath>
-
-#include "array_wave.h"
 #include "herm_eig.h"
+#include "steered_map.h"
 
 namespace alvq {
 
 constexpr int SUB_THREADS = 256;
 constexpr int SUB_WAVES = SUB_THREADS / kWave;
-constexpr int SUB_ANCHOR = 8;          // bins between two sincospi anchors of the rotation recurrence (srp_phat's)
-constexpr int SUB_MAX_NFFT = 1 << 24;
-
-// status bits of alvq_music_f64 (alvq_srp_phat_f64's)
-constexpr int MUSIC_BAD_SPECTRUM = 1;  // a non-finite eigenvector or eigenvalue inside the band
-constexpr int MUSIC_SILENT = 2;        // no counted bin: every eigenvalue inside the band is 0
-constexpr int MUSIC_BAD_GEOMETRY = 4;  // a non-finite microphone or candidate coordinate
 
 // --------------------------------------------------------------------------------------------------------- eigendecomposition
 __global__ __launch_bounds__(SUB_THREADS) void sub_eigh_kernel(const double2* A, double* lam, double2* V, int* status, long n, int D) {
@@ -85,15 +75,9 @@ __global__ __launch_bounds__(SUB_THREADS) void music_status_kernel(const double2
     if (!is_finite(x)) seen |= 1;
     if (x != 0.0) seen |= 2;
   }
-  const double* m = mics + (long)b * mics_stride;
-  for (int e = tid; e < 3 * D; e += SUB_THREADS)
-    if (!is_finite(m[e])) seen |= 4;
-  const double* q = cand + (long)b * cand_stride;
-  for (long e = tid; e < 3L * G; e += SUB_THREADS)
-    if (!is_finite(q[e])) seen |= 4;
+  seen |= geometry_seen<SUB_THREADS>(mics + (long)b * mics_stride, cand + (long)b * cand_stride, D, G, tid);
   seen = block_sum<kSequential, false, OpOr>(seen, s_flag);
-  if (tid == 0)
-    status[b] = ((seen & 1) ? MUSIC_BAD_SPECTRUM : 0) | ((seen & 2) ? 0 : MUSIC_SILENT) | ((seen & 4) ? MUSIC_BAD_GEOMETRY : 0);
+  if (tid == 0) status[b] = map_status(seen);
 }
 
 struct MusicArgs {
@@ -115,42 +99,18 @@ __global__ __launch_bounds__(SUB_THREADS) void music_map_kernel(MusicArgs a) {
   double* out = a.null + (long)b * a.G;
   const int st = a.status[b];                                            // the same in every thread of the workgroup
   if (st) {
-    if (g < a.G) out[g] = (st & (MUSIC_BAD_SPECTRUM | MUSIC_BAD_GEOMETRY)) ? __longlong_as_double(0x7ff8000000000000LL) : 1.0;
+    if (g < a.G) out[g] = (st & (MAP_BAD_SPECTRUM | MAP_BAD_GEOMETRY)) ? __longlong_as_double(0x7ff8000000000000LL) : 1.0;
     return;
   }
   if (g >= a.G) return;
 
-  const double* q = a.cand + (long)b * a.cand_stride + 3 * g;
-  const double* m = a.mics + (long)b * a.mics_stride;
-  const double qx = q[0], qy = q[1], qz = q[2];
-  double tau[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    const double dx = qx - m[3 * d], dy = qy - m[3 * d + 1], dz = qz - m[3 * d + 2];
-    tau[d] = sqrt(dx * dx + dy * dy + dz * dz) / a.c;
-  }
-  double wc[D], ws[D], zc[D], zs[D];                                     // the step e^{j pi (2 fs / n_fft) tau_d}; z_d of the bin
-#pragma unroll
-  for (int d = 0; d < D; ++d) sincospi(2.0 * a.fs_over_n * tau[d], &ws[d], &wc[d]);
-
+  SteerWalk<D> z(a.mics + (long)b * a.mics_stride, a.cand + (long)b * a.cand_stride + 3 * g, a.c, a.fs_over_n);
   const int Fb = a.f_hi - a.f_lo + 1;
   double acc = 0.0;
   int counted = 0;
   for (int k = 0; k < Fb; ++k) {
     const int f = a.f_lo + k;
-    if (k % SUB_ANCHOR == 0) {                                           // the same bins in every thread
-      const double kf = (double)(2 * f) * a.fs_over_n;
-#pragma unroll
-      for (int d = 0; d < D; ++d) sincospi(kf * tau[d], &zs[d], &zc[d]);
-    } else {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {                                      // z_d <- z_d w_d
-        const double cn = fma(zc[d], wc[d], -(zs[d] * ws[d]));
-        const double sn = fma(zc[d], ws[d], zs[d] * wc[d]);
-        zc[d] = cn;
-        zs[d] = sn;
-      }
-    }
+    z.move(k, f, a.fs_over_n);
     const long bin = (long)b * a.F + f;                                  // uniform addresses from here on
     const double* lg = a.lam + bin * D;
     bool live = false;
@@ -164,8 +124,8 @@ __global__ __launch_bounds__(SUB_THREADS) void music_map_kernel(MusicArgs a) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {                                      // conj(e_d) a_d, a_d = zc - j zs
         const double2 e = Vg[d * D + col];
-        const double tr = e.x * zc[d] - e.y * zs[d];
-        const double ti = -(e.x * zs[d]) - e.y * zc[d];
+        const double tr = e.x * z.zc[d] - e.y * z.zs[d];
+        const double ti = -(e.x * z.zs[d]) - e.y * z.zc[d];
         pr = d == 0 ? tr : pr + tr;
         pi = d == 0 ? ti : pi + ti;
       }
@@ -175,48 +135,6 @@ __global__ __launch_bounds__(SUB_THREADS) void music_map_kernel(MusicArgs a) {
     ++counted;
   }
   out[g] = acc / (double)counted;
-}
-
-__global__ __launch_bounds__(SUB_THREADS) void music_argmin_kernel(const double* map, const int* status, int* best, int G) {
-  __shared__ double s_val[SUB_WAVES];
-  __shared__ int s_idx[SUB_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
-  if (status[b]) {                                                       // the same in every thread
-    if (tid == 0) best[b] = -1;
-    return;
-  }
-  const double* row = map + (long)b * G;
-  double bv = INFINITY;
-  int bi = INT_MAX;
-  for (int g = tid; g < G; g += SUB_THREADS) {                           // g rising: the first minimum of the thread's candidates
-    const double v = row[g];
-    if (v < bv) {
-      bv = v;
-      bi = g;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov < bv || (ov == bv && oi < bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    s_val[wv] = bv;
-    s_idx[wv] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < SUB_WAVES; ++w)
-      if (s_val[w] < bv || (s_val[w] == bv && s_idx[w] < bi)) {
-        bv = s_val[w];
-        bi = s_idx[w];
-      }
-    best[b] = bi == INT_MAX ? -1 : bi;
-  }
 }
 
 }  // namespace alvq
@@ -239,16 +157,14 @@ extern "C" int alvq_music_f64(const double* V, const double* lam, const double* 
                               int mics_batched, int cand_batched, void* stream) {
   const char* who = "alvq_music_f64";
   ALVQ_REQUIRE(V && lam && mics && cand && null && best && status, ALVQ_EINVAL, "%s: null pointer", who);
-  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && F <= SUB_MAX_NFFT && (long)B * F <= INT_MAX, ALVQ_EINVAL,
+  ALVQ_REQUIRE(B >= 1 && B <= 65535 && F >= 1 && F <= kMaxNfft && (long)B * F <= INT_MAX, ALVQ_EINVAL,
                "%s: B=%d F=%d (need 1 <= B <= 65535, 1 <= F <= 2^24, B F <= 2^31 - 1)", who, B, F);
   ALVQ_TRY(check_mics(who, D, 2));
   ALVQ_REQUIRE(K >= 1 && K <= D - 1, ALVQ_EINVAL, "%s: K=%d (need 1 <= K <= D - 1 = %d)", who, K, D - 1);
-  ALVQ_REQUIRE(G >= 1 && (long)B * G <= INT_MAX, ALVQ_EINVAL, "%s: G=%d (need G >= 1, B G <= 2^31 - 1)", who, G);
-  ALVQ_REQUIRE(n_fft >= 2 && n_fft <= SUB_MAX_NFFT, ALVQ_EINVAL, "%s: n_fft=%d (need 2 <= n_fft <= 2^24)", who, n_fft);
-  ALVQ_REQUIRE(f_lo >= 0 && f_lo <= f_hi && f_hi < F, ALVQ_EINVAL, "%s: band %d..%d (need 0 <= f_lo <= f_hi < F = %d)", who, f_lo,
-               f_hi, F);
-  ALVQ_REQUIRE(std::isfinite(fs) && fs > 0.0 && std::isfinite(c) && c > 0.0, ALVQ_EINVAL, "%s: fs=%g c=%g must be finite and > 0",
-               who, fs, c);
+  ALVQ_TRY(check_candidates(who, B, G));
+  ALVQ_TRY(check_nfft(who, n_fft));
+  ALVQ_TRY(check_band(who, f_lo, f_hi, F));
+  ALVQ_TRY(check_rates(who, fs, c));
   const long mics_stride = mics_batched ? 3L * D : 0L, cand_stride = cand_batched ? 3L * G : 0L;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(music_status_kernel, dim3(B), dim3(SUB_THREADS), 0, s, (const double2*)V, lam, mics, cand, status, D, F, G, f_lo,
@@ -259,6 +175,7 @@ extern "C" int alvq_music_f64(const double* V, const double* lam, const double* 
 #define SUB_CALL(N) hipLaunchKernelGGL(music_map_kernel<N>, grid, dim3(SUB_THREADS), 0, s, args)
   ALVQ_FOR_2_TO_8(D, SUB_CALL)
 #undef SUB_CALL
-  hipLaunchKernelGGL(music_argmin_kernel, dim3(B), dim3(SUB_THREADS), 0, s, (const double*)null, (const int*)status, best, G);
+  hipLaunchKernelGGL((map_peak_kernel<false, SUB_THREADS>), dim3(B), dim3(SUB_THREADS), 0, s, (const double*)null,
+                     (const int*)status, best, G);
   return check_launch(who);
 }

@@ -151,7 +151,7 @@ def psi_bound(T):
     return (T + 8) * U
 
 
-ANCHOR = 8          # K: csrc/srp_phat.hip re-anchors its rotation recurrence along f every 8 bins
+ANCHOR = 8          # K: csrc/steered_map.h (kSteerAnchor) re-anchors the maps' rotation recurrence along f every 8 bins
 
 
 def map_bound(D, T, f_lo, f_hi, theta):

@@ -214,6 +214,30 @@ def test_lowest_index_wins():
     assert same_bits(got.map[0, 3], got.map[0, 41]) and same_bits(got.map[0, 3], got.map[0, len(order) - 1])
 
 
+def test_lowest_index_wins_across_trips_lanes_and_waves():
+    """600 candidates for the arg-max's 256 threads: every entry is the restatement's worst candidate but for copies of its
+    best one, placed so that the thread's own loop, the butterfly and the combine over the waves would each answer
+    differently under another tie rule.  (260, 200, 590): index 200 is thread 200 of wave 3, index 260 thread 4 of wave 0 on
+    its second trip, so a combine that prefers the lower wave or thread says 260.  (556, 300): both in thread 44, trips 2 and 1.
+    On the host the best beats the worst by more than twice the map's bound: the tie is among the copies only."""
+    shape = (1, 3, 4, 600, 8, 60, 400)
+    B, D, T, G, f_lo, f_hi, n_fft = shape
+    c = R.case(B, D, T, G, 11)
+    psi, st = R.cross_spectra(c.X, f_lo, f_hi)
+    S, _, status = R.srp_phat(psi, c.mics, c.cand, R.FS, n_fft, R.C, f_lo, f_hi, spectrum_status=st)
+    good, poor = int(np.argmax(S[0])), int(np.argmin(S[0]))
+    bound = R.map_bound(D, T, f_lo, f_hi, R.theta_max(f_hi, R.FS, n_fft, c.mics, c.cand))
+    print("%s: best %.6g, worst %.6g, bound %.3g" % (shape, S[0, good], S[0, poor], bound))
+    assert not status.any() and S[0, good] - S[0, poor] > 2 * bound
+    X = dev(c.X)
+    for copies, want in (((260, 200, 590), 200), ((556, 300), 300)):
+        grid = np.tile(c.cand[poor], (G, 1))
+        grid[list(copies)] = c.cand[good]
+        got = srp(X, c, shape, cand=dev(grid))
+        assert int(got.status[0]) == 0 and int(got.best[0]) == want, (copies, int(got.best[0]))
+        assert all(same_bits(got.map[0, copies[0]], got.map[0, g]) for g in copies[1:])
+
+
 # --------------------------------------------------------------------------------------------------------------------- tdoa
 def test_tdoa_of_a_free_field_pair():
     """Two microphones, no room, no noise: the delay is within half a sample of (r_i - r_j) / c (interpolation cannot do better

@@ -232,6 +232,30 @@ def test_music_lowest_index_on_ties():
     assert int(many[1][0]) == min(k, dup, (k + 1) % G, (k + 2) % G)
 
 
+def test_music_lowest_index_across_trips_lanes_and_waves():
+    """600 candidates for the arg-min's 256 threads: every entry is the restatement's shallowest candidate but for copies of
+    its deepest one, placed so that the thread's own loop, the butterfly and the combine over the waves would each answer
+    differently under another tie rule.  (260, 200, 590): index 200 is thread 200 of wave 3, index 260 thread 4 of wave 0 on
+    its second trip, so a combine that prefers the lower wave or thread says 260.  (556, 300): both in thread 44, trips 2 and 1.
+    On the host the deepest lies below the shallowest by more than twice the map's bound: the tie is among the copies only."""
+    B, D, T, G, f_lo, f_hi, n_fft = 1, 3, 4, 600, 8, 60, 400
+    c = srp_ref.case(B, D, T, G, 11)
+    cov, st = BR.covariance(c.X)
+    e = R.eigh(cov)
+    null, _, status = R.music(e.V, e.lam, c.mics, c.cand, 1, R.FS, n_fft, R.C, f_lo, f_hi)
+    good, poor = int(np.argmin(null[0])), int(np.argmax(null[0]))
+    bound = R.map_alone_bound(D, 1, srp_ref.theta_max(f_hi, R.FS, n_fft, c.mics, c.cand))
+    print("deepest %.6g, shallowest %.6g, bound %.3g" % (null[0, good], null[0, poor], bound))
+    assert not st.any() and not e.status.any() and not status.any() and null[0, poor] - null[0, good] > 2 * bound
+    V, lam, mics = dev(e.V), dev(e.lam), dev(c.mics)
+    for copies, want in (((260, 200, 590), 200), ((556, 300), 300)):
+        grid = np.tile(c.cand[poor], (G, 1))
+        grid[list(copies)] = c.cand[good]
+        got, best, gstatus = N.music(V, lam, mics, dev(grid), 1, R.FS, n_fft, R.C, f_lo, f_hi)
+        assert int(gstatus[0]) == 0 and int(best[0]) == want, (copies, int(best[0]))
+        assert all(same_bits(got[0, copies[0]], got[0, g]) for g in copies[1:])
+
+
 def test_music_locates_on_the_ring_in_the_room():
     """The room case of tests/test_subspace_cpu.py on the device, all four angles in one batch: array_impulse_responses ->
     array_spectrograms -> locate_on_ring(method="music"), within one candidate."""

@@ -173,7 +173,8 @@ def reduce():
 def array():
     """The microphone-array families behind csrc/array_wave.h, on the inputs of their own ``tests/helpers/*_ref.py`` builders:
     every case of size_sweep_cases.py (every compiled D, K, J and L) and beamform_ref.PARITY (both covariance kernels at
-    every D), in complex64 and complex128 where the family takes both; one WPE, one scoring and one alignment case.  Every
+    every D, with the steering vectors towards their sources), in complex64 and complex128 where the family takes both; one
+    WPE, one scoring and one alignment case.  Every
     hash covers the status words."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
     import numpy as np
@@ -233,6 +234,8 @@ def array():
         B, D, F, T, loading = shape
         c = BR.parity_case(shape)
         A, noise, speech = dev(c.A), dev(c.masks["runs"]), dev(c.masks["uniform"])
+        out["steering:%s" % (shape[:4],)] = {"ref %d" % ref: flat(BF.steering_vectors(dev(c.mics), dev(c.source), F, ref=ref))
+                                             for ref in sorted({0, D - 1})}
         for cdtype, tag in precisions:
             x = dev(c.X.astype(cdtype))
             cov_n, cov_s, cov = (BF.spatial_covariance(x, m) for m in (noise, speech, None))
